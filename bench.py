@@ -6,6 +6,7 @@
   python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c1]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
   python bench.py --gpus N --single-process     one process, the library's own N-device split behind the C ABI
+  ... --dump-outputs DIR                        also write the last timed step's compressed stream to DIR/*.npy
 
 A "step" is one pass of the block compressor over one image per rank.  The path shards by independent
 images / block rows with no data-path collective, so N ranks compress N images: weak
@@ -293,11 +294,11 @@ def parity_whole_or_crops(cfg, img, gpu_blocks, budget_s):
 
 
 def khronos_mosaic(size=4096):
-    """The reference's Khronos test images (tests/corpus/_images, fetched by tests/corpus/make_corpus.py) tiled into one
+    """The reference's Khronos test images (oracle/_ref/corpus, fetched by tests/corpus/make_corpus.py) tiled into one
     size x size RGBA8 image: the 2048^2 diffuse map in two quadrants, the 1024^2 maps (emissive, metal-roughness, base
     colour, specular-glossiness, normal, occlusion) in the other two.  None when the corpus is not there."""
     from PIL import Image
-    d = os.path.join(ROOT, "tests", "corpus", "_images", "Khronos")
+    d = os.path.join(O.CORPUS_IMAGES, "Khronos")
     names = ["LDR-RGB/ldr-rgb-diffuse.png", "LDR-RGB/ldr-rgb-emissive.png", "LDR-RGB/ldr-rgb-metalrough.png", "LDR-RGBA/ldr-rgba-base.png",
              "LDR-RGBA/ldr-rgba-diffuse.png", "LDR-RGBA/ldr-rgba-specgloss.png", "LDR-XY/ldr-xy-normal1.png", "LDR-L/ldr-l-occlusion.png"]
     if not all(os.path.exists(os.path.join(d, n)) for n in names):
@@ -326,7 +327,7 @@ def run_photo_config(lib, dev, steps, warmup):
     image beside it (whole stream, byte-compared)."""
     img = khronos_mosaic()
     if img is None:
-        return {"config": "photo", "skipped": "tests/corpus/_images not present (tests/corpus/make_corpus.py needs /root/reference)"}
+        return {"config": "photo", "skipped": "oracle/_ref/corpus not present (tests/corpus/make_corpus.py needs the reference tree)"}
     cfg = dict(CONFIGS["c2"], size=img.shape[0], label="Khronos test images tiled to %dx%d RGBA8 LDR, 6x6 block, -medium" % img.shape[:2])
     ctx = make_context(lib, cfg)
     d_img = to_device(img, dev)
@@ -459,6 +460,29 @@ def time_device_resident(lib, ctx, cfg, d_img, d_out, dev, steps, warmup, barrie
     kms = [step() for _ in range(steps)]
     barrier()
     return time.perf_counter() - t0, kms
+
+
+DUMP_MAX_BLOCKS = 1 << 19      # 2^19 blocks x 16 float32 + their float64 indices = 36 MB, under the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(dirname, blocks_u8):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step -- the compressed stream, 16 bytes
+    per block in raster order -- as DIR/blocks.npy (float32, one row of 16 byte values per block) and DIR/block_index.npy
+    (float64, the row's block number in the stream).  A stream of more than DUMP_MAX_BLOCKS blocks is written as a fixed
+    sample: DUMP_MAX_BLOCKS distinct blocks drawn with a fixed seed, in ascending order, so that two runs with the same
+    arguments write the same blocks."""
+    g = np.asarray(blocks_u8, dtype=np.uint8).reshape(-1, 16)
+    n = g.shape[0]
+    if n > DUMP_MAX_BLOCKS:
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_MAX_BLOCKS, replace=False))
+    else:
+        index = np.arange(n)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "blocks.npy"), g[index].astype(np.float32))
+    np.save(os.path.join(dirname, "block_index.npy"), index.astype(np.float64))
+    return {"dir": dirname, "blocks_total": int(n), "blocks_written": int(index.size),
+            "files": ["blocks.npy", "block_index.npy"]}
 
 
 def kernel_name_of(lib, ctx):
@@ -601,7 +625,13 @@ def main():
     ap.add_argument("--no-host-api", action="store_true", help="skip the host-pointer (PCIe-inclusive) leg")
     ap.add_argument("--single-process", action="store_true",
                     help="N GPUs from ONE process through the C ABI's own device split (host pointers, PCIe included)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the compressed stream of the last one to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     cfg = CONFIGS[args.config]
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -665,6 +695,7 @@ def main():
         value = world * texels * args.steps / elapsed / 1e6
         kernel_s = sum(kms) / len(kms) / 1e3
         gpu_blocks = d_out.cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, gpu_blocks) if args.dump_outputs else None
         roof = roofline_of(cfg, kernel_s, kernel_name_of(lib, ctx), args.config)
         out = {
             "metric": "Mtexels/s + PSNR-dB, 8192x8192 RGBA8 LDR 6x6 -medium" if args.config == "c2" else "Mtexels/s, " + cfg["label"],
@@ -684,6 +715,8 @@ def main():
                                 "launch a fixed-context build of the library, every other context gets one compiled at run time "
                                 "(extra_configs: run_time_build)"},
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_host_api:
             rate, ndev, host_blocks = time_host_api(lib, cfg, img_host, str(local_rank))
             out["value_host_api"] = {"value": round(rate, 3), "unit": "Mtexels/s", "devices": ndev,
@@ -751,13 +784,15 @@ def single_process(lib, cfg, args):
         assert lib.compress_raw(ctx, img, out) == 0
     elapsed = time.perf_counter() - t0
     lib.context_free(ctx)
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs else None
     print(json.dumps({
         "metric": "Mtexels/s, %s, single process / C-ABI device split, PCIe included" % cfg["label"],
         "value": round(h * w * args.steps / elapsed / 1e6, 3), "unit": "Mtexels/s", "n_gpus": ndev, "steps": args.steps,
         "warmup": max(args.warmup, 1), "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s x %d stacked vertically, one host image through astcenc_compress_image" % (cfg["label"], n),
-                   "devices": devices, "sharding": "block rows dealt to devices inside libastcenc_amd.so, no collectives"}}), flush=True)
+                   "devices": devices, "sharding": "block rows dealt to devices inside libastcenc_amd.so, no collectives"},
+        **({"dump_outputs": dumped} if dumped else {})}), flush=True)
 
 
 if __name__ == "__main__":

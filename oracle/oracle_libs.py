@@ -6,6 +6,7 @@
   oracle/_ref/libastcenc-avx2-gathers.so   the same with ASTCENC_X86_GATHERS=1 (the reference's x86 default); bench.py times both
   oracle/_ref/libastcenc-avx2-lto.so       the AVX2 build with -flto; bench.py reports the fastest of the three
   oracle/_ref/libastcenc-diag.so    the reference with ASTCENC_DIAGNOSTICS (-dtrace JSON): stage-level error oracle
+  oracle/_ref/corpus/               the reference's test images (tests/corpus/make_corpus.py): tests/test_corpus.py, bench.py's photo leg
   oracle/emu/_build/libastcenc_emu.so   sequential CPU build of the kernel source (a debugging aid, not independent)
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the product binding
@@ -19,6 +20,8 @@ LIB_REF_AVX2 = os.path.join(REPO, "oracle", "_ref", "libastcenc-avx2.so")
 LIB_REF_AVX2_GATHERS = os.path.join(REPO, "oracle", "_ref", "libastcenc-avx2-gathers.so")
 LIB_REF_AVX2_LTO = os.path.join(REPO, "oracle", "_ref", "libastcenc-avx2-lto.so")   # link-time optimised (the reference's release setting for its CLI)
 LIB_REF_DIAG = os.path.join(REPO, "oracle", "_ref", "libastcenc-diag.so")
+# the reference's test images, copied by tests/corpus/make_corpus.py (next to the binaries built from the same tree)
+CORPUS_IMAGES = os.path.join(REPO, "oracle", "_ref", "corpus")
 LIB_EMU = os.path.join(REPO, "oracle", "emu", "_build", "libastcenc_emu.so")
 # ... with the lanes of every lane loop in reverse order (oracle/emu/Makefile: `make reverse`), the lane-order race check
 LIB_EMU_REVERSE = os.path.join(REPO, "oracle", "emu", "_build", "libastcenc_emu_reverse.so")

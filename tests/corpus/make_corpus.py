@@ -3,8 +3,8 @@
 
 /root/reference does not exist there, and 28 MB of third-party images do not belong in this repository's history, so --
 like oracle/_ref, which is compiled from the reference's sources where they lie -- the images are COPIED from where
-they lie (/root/reference/Test/Images/{Small,Khronos,HDRIHaven}) into tests/corpus/_images/ (git-ignored, not
-gpurun-ignored: the copy travels to the GPU box with the working tree).  What IS committed: this script and
+they lie (/root/reference/Test/Images/{Small,Khronos,HDRIHaven}) into oracle/_ref/corpus/ (git-ignored; it goes wherever the
+binaries built from the same tree go, so a checkout that has them has the images too).  What IS committed: this script and
 tests/corpus/manifest.json -- every image's path, SHA-256, colour profile / format / flags as the reference's test
 harness derives them from the file name (/root/reference/Test/testlib/testset.py:117-190), and the reference's own
 recorded PSNR per block size and preset (Test/Images/<set>/astc_reference-5.0-avx2_<preset>_results.csv, the values
@@ -13,7 +13,7 @@ is present."""
 import csv, hashlib, json, os, shutil, sys
 REF = "/root/reference/Test/Images"
 HERE = os.path.dirname(os.path.abspath(__file__))
-DST = os.path.join(HERE, "_images")
+DST = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref", "corpus")
 SETS = ("Small", "Khronos", "HDRIHaven")
 EXTS = (".jpg", ".png", ".tga", ".dds", ".hdr", ".ktx")            # testset.py:71
 PRESETS = ("fastest", "fast", "medium", "thorough")
@@ -60,8 +60,11 @@ def main():
                 img = by_key.get((row["Image Set"], row["Name"]))
                 if img is not None:
                     img.setdefault("ref_coding_rate", {})["%s/%s" % (preset, row["Block Size"])] = float(row["Coding Rate"])
-    json.dump({"source": "reference Test/Images, astc_reference-5.0-avx2_*_results.csv (PSNR), astc_reference-main-avx2_*_results.csv (coding rate)", "images": images},
-              open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
+    manifest = json.dumps({"source": "reference Test/Images, astc_reference-5.0-avx2_*_results.csv (PSNR), astc_reference-main-avx2_*_results.csv (coding rate)",
+                           "images": images}, indent=1, sort_keys=True)
+    path = os.path.join(HERE, "manifest.json")
+    if open(path).read() != manifest:        # the committed manifest is rewritten only when the reference's corpus changed
+        open(path, "w").write(manifest)
     print("fetched %d images into %s" % (len(images), os.path.relpath(DST)))
     return 0
 

@@ -2,7 +2,7 @@
 """Parity and quality on the reference's image corpus (VERDICT r03 "missing" 2 / "next" 4).
 
 The 44 images of /root/reference/Test/Images/{Small,Khronos,HDRIHaven} -- luminance, XY normal maps, RGB, RGBA, sRGB and
-HDR content in png / dds / ktx / hdr containers -- fetched by tests/corpus/make_corpus.py (tests/corpus/_images travels
+HDR content in png / dds / ktx / hdr containers -- fetched by tests/corpus/make_corpus.py (oracle/_ref/corpus travels
 to the GPU box, tests/corpus/manifest.json is committed).  Real content takes the early exits that the synthetic noise of
 the bench never takes (Source/astcenc_compress_symbolic.cpp:1300-1317, :1353-1368).
 
@@ -26,10 +26,12 @@ import subprocess
 
 import pytest
 
+import oracle_libs as O
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI_AMD = os.path.join(ROOT, "oracle", "_ref", "astcenc-cli-amd")
 CLI_REF = os.path.join(ROOT, "oracle", "_ref", "astcenc-cli-ref-avx2")
-IMAGES = os.path.join(ROOT, "tests", "corpus", "_images")
+IMAGES = O.CORPUS_IMAGES
 MANIFEST = json.load(open(os.path.join(ROOT, "tests", "corpus", "manifest.json")))["images"]
 FULL = os.environ.get("ASTC_CORPUS_FULL", "0") == "1"
 

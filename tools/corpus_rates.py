@@ -9,7 +9,7 @@ import json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI_AMD = os.path.join(ROOT, "oracle", "_ref", "astcenc-cli-amd")
 CLI_REF = os.path.join(ROOT, "oracle", "_ref", "astcenc-cli-ref-avx2")
-IMAGES = os.path.join(ROOT, "tests", "corpus", "_images")
+IMAGES = os.path.join(ROOT, "oracle", "_ref", "corpus")
 MANIFEST = json.load(open(os.path.join(ROOT, "tests", "corpus", "manifest.json")))["images"]
 COMPRESS = {"ldr": "-cl", "ldrs": "-cs", "hdr": "-ch"}
 block = sys.argv[1] if len(sys.argv) > 1 else "6x6"
