@@ -319,4 +319,11 @@ struct ImageDesc {
 	                           // blocks are read from slice 0 (ref: astcenc_image.cpp:304); 0 = read the block's own slice
 };
 
+// One entry of a compressed image set (image_set.h): the image as a single call would hand it to the kernel, and where its
+// blocks go (block i of the entry: out + 16 i).
+struct ImageSetEntryDesc {
+	ImageDesc img;
+	uint8_t* out;
+};
+
 } // namespace astcd

@@ -15,6 +15,7 @@
 #include "../../include/astcenc.h"
 #include "../../include/astcenc_amd.h"
 #include "backend.h"
+#include "entry_internal.h"
 #include "host_tables.h"
 
 // sequential (host) build of the block decoder source, for astcenc_get_block_info
@@ -155,11 +156,6 @@ astcenc_error validate_flags(astcenc_profile profile, unsigned int flags)
 	return ASTCENC_SUCCESS;
 }
 
-bool swz_ok(astcenc_swz s, bool allow_z)
-{
-	return (int)s >= ASTCENC_SWZ_R && ((int)s <= ASTCENC_SWZ_1 || (allow_z && s == ASTCENC_SWZ_Z));
-}
-
 template <typename T> T clampv(T v, T lo, T hi) { return v > hi ? hi : (v > lo ? v : lo); }
 float maxf(float a, float b) { return a > b ? a : b; }
 unsigned int maxu(unsigned int a, unsigned int b) { return a > b ? a : b; }
@@ -206,44 +202,8 @@ astcenc_error validate_config(astcenc_config& config)
 	return ASTCENC_SUCCESS;
 }
 
-size_t mul_safe(size_t a, size_t b, bool& overflow)
-{
-	size_t r = a * b;
-	overflow = overflow || ((b != 0) && ((r / b) != a));
-	return r;
-}
-
-size_t block_count_axis(size_t dim, size_t block)
-{
-	size_t n = dim / block;
-	if (dim != block * n) n++;
-	return n;
-}
-
 } // namespace
 
-// ---------------------------------------------------------------------------------------------
-// Context
-// ---------------------------------------------------------------------------------------------
-struct astcenc_context {
-	astcenc_config config;            // validated copy; tune_db_limit already converted
-	unsigned int thread_count;
-	bool owns_tables;
-	const astcenc_context* parent;
-	std::vector<uint8_t>* blob;       // table blob (shared with child contexts)
-	HostTables* host_tables;
-	Backend* backend;
-
-	// caller-thread rendezvous for compress (ref: ParallelManager)
-	std::mutex lock;
-	std::condition_variable cv;
-	enum { IDLE, RUNNING, DONE } state;
-	astcenc_error result;
-	int dstate;                       // same protocol for decompress (ref: manage_decompress)
-	astcenc_error dresult;
-	std::atomic<int> cancel_flag;     // (ref: ParallelManager::m_is_cancelled, astcenc_internal_entry.h:104)
-	int per_slice_fast_load;          // ASTCENC_AMD_OPT_PER_SLICE_FAST_LOAD: -1 not set (each entry point's default), 0, 1
-};
 
 extern "C" {
 
@@ -497,30 +457,6 @@ void astcenc_context_free(astcenc_context* ctx)
 	delete ctx;
 }
 
-static astcenc_error check_compress_args(astcenc_context* ctx, unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
-                                         const astcenc_swizzle* swizzle, size_t data_len, unsigned int thread_index, size_t& block_count)
-{
-	if (ctx->config.flags & ASTCENC_FLG_DECOMPRESS_ONLY) return ASTCENC_ERR_BAD_CONTEXT;
-	if (!swz_ok(swizzle->r, false) || !swz_ok(swizzle->g, false) || !swz_ok(swizzle->b, false) || !swz_ok(swizzle->a, false))
-	{
-		return ASTCENC_ERR_BAD_SWIZZLE;
-	}
-	if (thread_index >= ctx->thread_count) return ASTCENC_ERR_BAD_PARAM;
-
-	bool overflow = false;
-	size_t texel_count = mul_safe(mul_safe(dim_x, dim_y, overflow), dim_z, overflow);
-	if (overflow || texel_count == 0) return ASTCENC_ERR_BAD_PARAM;
-
-	size_t bx = block_count_axis(dim_x, ctx->config.block_x);
-	size_t by = block_count_axis(dim_y, ctx->config.block_y);
-	size_t bz = block_count_axis(dim_z, ctx->config.block_z);
-	overflow = false;
-	block_count = mul_safe(mul_safe(bx, by, overflow), bz, overflow);
-	mul_safe(block_count, 16, overflow);
-	if (overflow || block_count == 0) return ASTCENC_ERR_BAD_PARAM;
-	if (data_len < block_count * 16) return ASTCENC_ERR_OUT_OF_MEM;
-	return ASTCENC_SUCCESS;
-}
 
 static astcenc_error run_job(astcenc_context* ctx, CompressJob& job)
 {
@@ -629,18 +565,8 @@ astcenc_error astcenc_amd_decompress_image_device(astcenc_context* ctx, const vo
                                                   void* device_image, unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
                                                   astcenc_type data_type, const astcenc_swizzle* swizzle, void* hip_stream)
 {
-	if (!swz_ok(swizzle->r, true) || !swz_ok(swizzle->g, true) || !swz_ok(swizzle->b, true) || !swz_ok(swizzle->a, true))
-	{
-		return ASTCENC_ERR_BAD_SWIZZLE;
-	}
-	bool overflow = false;
-	size_t texel_count = mul_safe(mul_safe(dim_x, dim_y, overflow), dim_z, overflow);
-	if (overflow || texel_count == 0 || !device_blocks || !device_image) return ASTCENC_ERR_BAD_PARAM;
-	size_t block_count = mul_safe(mul_safe(block_count_axis(dim_x, ctx->config.block_x), block_count_axis(dim_y, ctx->config.block_y), overflow),
-	                              block_count_axis(dim_z, ctx->config.block_z), overflow);
-	mul_safe(block_count, 16, overflow);
-	if (overflow || block_count == 0) return ASTCENC_ERR_BAD_PARAM;
-	if (data_len < block_count * 16) return ASTCENC_ERR_OUT_OF_MEM;
+	astcenc_error status = check_decompress_device_args(ctx, device_blocks, data_len, device_image, dim_x, dim_y, dim_z, swizzle);
+	if (status != ASTCENC_SUCCESS) return status;
 
 	DecompressDeviceJob job;
 	memset(&job, 0, sizeof(job));

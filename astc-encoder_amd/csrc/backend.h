@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <atomic>
 #include "astc_tables.h"
+#include "image_set.h"
 
 namespace astcd {
 
@@ -53,6 +54,25 @@ struct DecompressDeviceJob {
 	void*    stream;
 };
 
+/* An image set on one device (astcenc_amd_compress_images_device): every entry is described by the device-resident fields
+ * of a CompressJob (device_data, device_out, dimensions, data_type, swz, a_scale_radius, fast_load_slice0); the blocks of all
+ * entries are compressed as one block range, entry after entry. */
+struct CompressSetJob {
+	const CompressJob* entries;
+	uint32_t count;            // >= 1; the blocks of all entries fit in 32 bits (checked by the caller)
+	void*    stream;
+	float*   kernel_ms;
+	const std::atomic<int>* cancel_flag;
+	void (*progress)(float);
+};
+
+/* ... and its decompression (astcenc_amd_decompress_images_device): every entry as a DecompressDeviceJob (stream unused). */
+struct DecompressSetJob {
+	const DecompressDeviceJob* entries;
+	uint32_t count;
+	void*    stream;
+};
+
 /* Squared-error sums of two images of the same size (wave_metrics.h); sums[METRIC_SUMS] on the host. */
 struct CompareJob {
 	const void* device_a; uint32_t type_a;
@@ -77,6 +97,12 @@ int backend_compress(Backend* b, const CompressJob& job);
 int backend_decompress(Backend* b, const DecompressJob& job);
 int backend_decompress_device(Backend* b, const DecompressDeviceJob& job);
 int backend_compare(Backend* b, const CompareJob& job);
+/* Image sets run on the device that owns entry 0's buffers; a buffer of another device is rc 3.  (Product library only: the
+ * entry points live in astcenc_set.cpp, which the sequential build of oracle/emu does not link.) */
+int backend_compress_set(Backend* b, const CompressSetJob& job);
+int backend_decompress_set(Backend* b, const DecompressSetJob& job);
+/* A line for the diagnostics callback (astcenc_amd_set_log_callback), printf-style. */
+void backend_log(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 const char* backend_name();
 /* Where the library's diagnostics go (null: nowhere, the default; see include/astcenc_amd.h). */
 void backend_set_log_callback(void (*callback)(const char* message));
@@ -92,6 +118,8 @@ struct KernelLaunch {
 	uint32_t first, count;
 	void* stream;                    // hipStream_t
 	unsigned long long* d_prof;      // stage timers (profiling builds) or null
+	const ImageSetTable* d_set;      // null: blocks [first, first + count) of `img` into `d_out`; else an image set's table (image_set.h):
+	                                 // the blocks of all entries back to back, `img` and `d_out` unused
 };
 
 /* Return 0 on success, a hipError_t value otherwise. `prepare` sets the dynamic-LDS attribute and
@@ -149,6 +177,12 @@ struct DecodeLaunch {
 	void* stream;
 };
 int astc_decode_launch(const DecodeLaunch& d);
+/* An image set's decode (one DecodeLaunch per entry, stream unused): astc_decode_set_build writes the table
+ * (astc_decode_set_bytes(count) bytes, image_set.h) and returns the wavefront runs of all entries; astc_decode_set_launch covers
+ * them from the table's device copy, in one launch unless they exceed the grid. */
+size_t astc_decode_set_bytes(uint32_t count);
+uint32_t astc_decode_set_build(void* out, const DecodeLaunch* entries, uint32_t count);
+int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -58,6 +58,8 @@ struct DeviceSlot {
 	uint8_t* d_out; size_t out_cap;
 	float* d_alpha; size_t alpha_cap;   // alpha averages of the a_scale_radius pre-pass
 	float* d_alpha_scratch; size_t alpha_scratch_cap;   // padded tiles of the pre-pass when they outgrow LDS (large radii)
+	uint8_t* d_set; size_t set_cap;     // the table of an image set (image_set.h), compression or decompression
+	std::vector<uint8_t> h_set;         // ... and its host copy (kept until the next set call: the upload is asynchronous)
 	unsigned long long* d_prof;   // stage timers (ASTC_PROFILE builds) / search trace (ASTC_TRACE builds)
 	size_t trace_cap;             // bytes at d_prof in ASTC_TRACE builds
 	double* d_sums;               // totals of the image comparison kernel
@@ -122,6 +124,16 @@ static void log_msg(const char* fmt, ...)
 	else fprintf(stderr, "astcenc_amd: %s\n", line);
 }
 
+void backend_log(const char* fmt, ...)
+{
+	char line[512];
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(line, sizeof(line), fmt, ap);
+	va_end(ap);
+	log_msg("%s", line);
+}
+
 #define HIP_TRY(expr, fail) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	log_msg("%s -> %s", #expr, hipGetErrorString(e_)); fail; } } while (0)
 
@@ -181,7 +193,7 @@ int kernel_launch(const Backend* b, const DeviceSlot* s, const KernelLaunch& k)
 	{
 		// the run-time build: same parameters as the library's builds (kernel_device.h), launched through the module API
 		KernelLaunch a = k;
-		void* args[] = { &a.d_tab, &a.img, &a.d_out, &a.first, &a.count, &a.d_prof };
+		void* args[] = { &a.d_tab, &a.img, &a.d_out, &a.first, &a.count, &a.d_prof, &a.d_set };
 		return (int)hipModuleLaunchKernel(s->jit_fn, k.count, 1, 1, 64, 1, 1, k.lds_bytes, static_cast<hipStream_t>(k.stream), args, nullptr);
 	}
 	return kernel_variants[b->variant].launch(k);
@@ -225,7 +237,7 @@ bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 	if (ok)
 	{
 		KernelLaunch k;
-		k.d_tab = s->d_tab; k.lds_bytes = b->lds_bytes; k.d_prof = nullptr; k.stream = s->stream;
+		k.d_tab = s->d_tab; k.lds_bytes = b->lds_bytes; k.d_prof = nullptr; k.d_set = nullptr; k.stream = s->stream;
 		k.first = 0; k.count = (uint32_t)nblocks;
 		ImageDesc& im = k.img;
 		im.data = d_img; im.dim_x = dim_x; im.dim_y = dim_y; im.data_type = 0;
@@ -237,7 +249,7 @@ bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 		k.d_out = d_out;
 		ok = ok && kernel_variants[b->variant].launch(k) == 0;
 		k.d_out = d_out + nblocks * 16;
-		void* args[] = { &k.d_tab, &k.img, &k.d_out, &k.first, &k.count, &k.d_prof };
+		void* args[] = { &k.d_tab, &k.img, &k.d_out, &k.first, &k.count, &k.d_prof, &k.d_set };
 		ok = ok && hipModuleLaunchKernel(fn, k.count, 1, 1, 64, 1, 1, k.lds_bytes, s->stream, args, nullptr) == hipSuccess;
 		ok = ok && hipMemcpyAsync(out.data(), d_out, out.size(), hipMemcpyDeviceToHost, s->stream) == hipSuccess;
 		ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
@@ -305,6 +317,7 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_out) (void)hipFree(s->d_out);
 	if (s->d_alpha) (void)hipFree(s->d_alpha);
 	if (s->d_alpha_scratch) (void)hipFree(s->d_alpha_scratch);
+	if (s->d_set) (void)hipFree(s->d_set);
 	if (s->d_sums) (void)hipFree(s->d_sums);
 	if (s->d_prof) (void)hipFree(s->d_prof);
 	for (int i = 0; i < 2; i++) { if (s->h_in[i]) (void)hipHostFree(s->h_in[i]); if (s->h_out[i]) (void)hipHostFree(s->h_out[i]); }
@@ -432,6 +445,7 @@ DeviceSlot* slot_create(Backend* b, int device, int* status)
 	s->h_in[0] = s->h_in[1] = nullptr; s->h_in_cap = 0; s->h_out[0] = s->h_out[1] = nullptr; s->h_out_cap = 0;
 	s->d_image = nullptr; s->image_cap = 0; s->d_out = nullptr; s->out_cap = 0; s->d_alpha = nullptr; s->alpha_cap = 0;
 	s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
+	s->d_set = nullptr; s->set_cap = 0;
 	s->d_prof = nullptr; s->trace_cap = 0; s->d_sums = nullptr;
 	s->worker = nullptr;
 	s->jit_module = nullptr; s->jit_fn = nullptr; s->jit_tried = false;
@@ -674,6 +688,133 @@ int backend_specialize(Backend* b)
 
 static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob& job, Progress* progress);
 
+/* The context's run-time build: adopted as soon as the compiler has delivered it; asked for (JIT_LAZY) once the context has
+ * compressed enough to be worth a compile.  Called by every compression of `nblocks` blocks on slot `s`. */
+static void jit_count_blocks(Backend* b, DeviceSlot* s, size_t nblocks)
+{
+	slot_adopt_jit(b, s);
+	if (b->jit && b->jit_mode == JIT_LAZY && b->blocks_done.fetch_add(nblocks) + nblocks >= b->jit_lazy_blocks) jit_start(b->jit);
+}
+
+/* The kernel's record of the image of `job` whose texels start at `data` (alpha_avg: null, set by the pre-pass). */
+static ImageDesc image_desc(const Backend* b, const CompressJob& job, const void* data)
+{
+	const uint32_t bsx = b->root.dim_x, bsy = b->root.dim_y, bsz = b->root.dim_z;
+	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
+	ImageDesc img;
+	img.data = data;
+	img.dim_x = job.dim_x; img.dim_y = job.dim_y;
+	img.data_type = job.data_type;
+	for (int i = 0; i < 4; i++) img.swz[i] = job.swz[i];
+	img.blocks_x = (job.dim_x + bsx - 1) / bsx; img.blocks_y = (job.dim_y + bsy - 1) / bsy;
+	img.dim_z = dim_z; img.blocks_z = (dim_z + bsz - 1) / bsz;
+	bool needs_swz = job.swz[0] != 0 || job.swz[1] != 1 || job.swz[2] != 2 || job.swz[3] != 3;
+	bool hdr = b->cfg.profile >= 2;
+	img.use_fast_load = (!needs_swz && !hdr && job.data_type == 0 && bsz == 1) ? 1 : 0;   // ref: astcenc_entry.cpp:946
+	img.fast_load_slice0 = job.fast_load_slice0;
+	img.alpha_avg = nullptr;
+	img.a_scale_radius = job.a_scale_radius;
+	return img;
+}
+
+/* The alpha-average pre-pass of one image (`rows` texel rows of dim_x, dim_z slices) into d_averages.  Returns 0 ok, 1 out of
+ * memory (or a radius whose scratch is refused), 2 launch failure.  alpha_scratch_release() once the call's pre-passes are queued. */
+static int alpha_prepass(DeviceSlot* s, hipStream_t stream, const void* d_image, float* d_averages, uint32_t dim_x, uint32_t rows,
+                         uint32_t dim_z, uint32_t data_type, uint32_t swz_a, uint32_t radius)
+{
+	AlphaLaunch a;
+	a.d_image = d_image; a.d_averages = d_averages;
+	a.dim_x = dim_x; a.dim_y = rows; a.dim_z = dim_z; a.data_type = data_type;
+	a.swz_a = swz_a; a.radius = radius; a.stream = stream;
+	a.d_scratch = nullptr; a.scratch_workgroups = 0;
+	const size_t scratch = astc_alpha_scratch_bytes(dim_x, rows, dim_z, radius, &a.scratch_workgroups);
+	if (scratch == (size_t)-1)
+	{
+		log_msg("a_scale_radius %u needs more than 1 GiB of pre-pass scratch per tile: refused", radius);
+		return 1;
+	}
+	if (scratch)
+	{
+		if (s->alpha_scratch_cap < scratch)
+		{
+			if (s->d_alpha_scratch) (void)hipFree(s->d_alpha_scratch);
+			s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
+			HIP_TRY(hipMalloc(&s->d_alpha_scratch, scratch + ALLOC_SLACK), return 1);
+			s->alpha_scratch_cap = scratch;
+		}
+		a.d_scratch = s->d_alpha_scratch;
+	}
+	int arc = astc_alpha_launch(a);
+	if (arc != 0) { log_msg("alpha pre-pass launch failed (hip error %d)", arc); return 2; }
+	return 0;
+}
+
+/* (a large scratch is not kept for the life of the context: the pre-pass runs once per call, its scratch goes back as soon as
+ *  the stream is past the kernel -- hipFree waits for that) */
+static void alpha_scratch_release(DeviceSlot* s, hipStream_t stream)
+{
+	if (s->alpha_scratch_cap > ((size_t)64 << 20))
+	{
+		(void)hipStreamSynchronize(stream);
+		(void)hipFree(s->d_alpha_scratch);
+		s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
+	}
+}
+
+/* The kernel launches of one call: blocks [0, nblocks) of `k` (one image, or an image set's table) in chunks of `chunk`.
+ * Chunks bound the time between cancel checks / progress callbacks on huge images; a chunk is still tens of thousands of
+ * workgroups, far more than the 256 CUs need to stay full.  The host stays at most two chunks ahead of the device: chunk k-1's
+ * completion event is waited for (and reported to the progress callback) after chunk k has been queued, so the device always
+ * has its next kernel waiting, a cancel takes effect within two chunks, and nothing synchronises a whole stream.  The banded
+ * host-pointer path does its own waiting in its two hooks.  After the call: `launched` blocks are queued, the last chunk
+ * (`prev_blocks` of them) is neither waited for nor reported. */
+struct ChunkLoop {
+	KernelLaunch k;                   // every field but first / count
+	size_t nblocks, chunk;
+	bool chunked;                     // wait for and report every chunk
+	bool timed;                       // ev0 / ev1 around the launches (kernel_ms)
+	const std::atomic<int>* cancel_flag;
+	Progress* progress;
+	std::function<int(size_t first, size_t n)> before_launch;                                       // banded: 0 ok
+	std::function<int(size_t first, size_t n, size_t chunk_index, size_t prev_blocks)> after_launch; // banded: 0 ok
+	size_t launched, prev_blocks;
+};
+
+static int run_chunks(const Backend* b, DeviceSlot* s, ChunkLoop& L)
+{
+	const hipStream_t stream = static_cast<hipStream_t>(L.k.stream);
+	if (L.timed) HIP_TRY(hipEventRecord(s->ev0, stream), return 2);
+	L.launched = 0; L.prev_blocks = 0;
+	size_t chunk_index = 0;
+	for (size_t first = 0; first < L.nblocks; first += L.chunk, chunk_index++)
+	{
+		if (L.cancel_flag && L.cancel_flag->load(std::memory_order_relaxed)) break;
+		size_t n = L.nblocks - first < L.chunk ? L.nblocks - first : L.chunk;
+		if (L.before_launch && L.before_launch(first, n) != 0) return 2;
+		KernelLaunch k = L.k;
+		k.first = (uint32_t)first; k.count = (uint32_t)n;
+		int lrc = kernel_launch(b, s, k);
+		if (lrc != 0) { log_msg("kernel launch failed (hip error %d)", lrc); return 2; }
+		L.launched = first + n;
+		if (L.after_launch)
+		{
+			if (L.after_launch(first, n, chunk_index, L.prev_blocks) != 0) return 2;
+		}
+		else if (L.chunked)
+		{
+			HIP_TRY(hipEventRecord(s->ev_done[chunk_index % 3], stream), return 2);
+			if (chunk_index > 0)
+			{
+				HIP_TRY(hipEventSynchronize(s->ev_done[(chunk_index - 1) % 3]), return 2);
+				if (L.progress) L.progress->add(L.prev_blocks);
+			}
+		}
+		L.prev_blocks = n;
+	}
+	if (L.timed) HIP_TRY(hipEventRecord(s->ev1, stream), return 2);
+	return 0;
+}
+
 /* The blocks of `job` on one slot.  Returns 0 ok, 1 out of memory, 2 device failure, 3 bad argument. */
 static int compress_on_slot(Backend* b, DeviceSlot* s, const CompressJob& job, Progress* progress)
 {
@@ -700,10 +841,7 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 	const uint32_t blocks_y = (job.dim_y + bsy - 1) / bsy;
 	const uint32_t blocks_z = (dim_z + bsz - 1) / bsz;
 	const size_t nblocks = (size_t)blocks_x * blocks_y * blocks_z;
-	// the context's run-time build: adopted as soon as the compiler has delivered it; asked for (JIT_LAZY) once the context
-	// has compressed enough to be worth a compile
-	slot_adopt_jit(b, s);
-	if (b->jit && b->jit_mode == JIT_LAZY && b->blocks_done.fetch_add(nblocks) + nblocks >= b->jit_lazy_blocks) jit_start(b->jit);
+	jit_count_blocks(b, s, nblocks);
 	const size_t texel_bytes = job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16;
 	// (a shard of the alpha-scale split carries halo rows around its own: they are uploaded and averaged, not compressed)
 	const uint32_t halo_above = dim_z == 1 && job.a_scale_radius != 0 ? job.halo_above : 0u;
@@ -753,19 +891,7 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 	}
 	if (!d_image || !d_out) return 2;
 
-	ImageDesc img;
-	img.data = static_cast<const uint8_t*>(d_image) + (size_t)halo_above * job.dim_x * texel_bytes;
-	img.dim_x = job.dim_x; img.dim_y = job.dim_y;
-	img.data_type = job.data_type;
-	for (int i = 0; i < 4; i++) img.swz[i] = job.swz[i];
-	img.blocks_x = blocks_x; img.blocks_y = blocks_y;
-	img.dim_z = dim_z; img.blocks_z = blocks_z;
-	bool needs_swz = job.swz[0] != 0 || job.swz[1] != 1 || job.swz[2] != 2 || job.swz[3] != 3;
-	bool hdr = b->cfg.profile >= 2;
-	img.use_fast_load = (!needs_swz && !hdr && job.data_type == 0 && bsz == 1) ? 1 : 0;   // ref: astcenc_entry.cpp:946
-	img.fast_load_slice0 = job.fast_load_slice0;
-	img.alpha_avg = nullptr;
-	img.a_scale_radius = job.a_scale_radius;
+	ImageDesc img = image_desc(b, job, static_cast<const uint8_t*>(d_image) + (size_t)halo_above * job.dim_x * texel_bytes);
 	if (job.a_scale_radius != 0)
 	{
 		const size_t need = (size_t)job.dim_x * rows_with_halo * sizeof(float);
@@ -776,43 +902,13 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 			HIP_TRY(hipMalloc(&s->d_alpha, need + ALLOC_SLACK), return 1);
 			s->alpha_cap = need;
 		}
-		AlphaLaunch a;
-		a.d_image = d_image; a.d_averages = s->d_alpha;
-		a.dim_x = job.dim_x; a.dim_y = rows_with_halo; a.dim_z = dim_z; a.data_type = job.data_type;
-		a.swz_a = job.swz[3]; a.radius = job.a_scale_radius; a.stream = stream;
-		a.d_scratch = nullptr; a.scratch_workgroups = 0;
-		const size_t scratch = astc_alpha_scratch_bytes(job.dim_x, rows_with_halo, dim_z, job.a_scale_radius, &a.scratch_workgroups);
-		if (scratch == (size_t)-1)
-		{
-			log_msg("a_scale_radius %u needs more than 1 GiB of pre-pass scratch per tile: refused", job.a_scale_radius);
-			return 1;
-		}
-		if (scratch)
-		{
-			if (s->alpha_scratch_cap < scratch)
-			{
-				if (s->d_alpha_scratch) (void)hipFree(s->d_alpha_scratch);
-				s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
-				HIP_TRY(hipMalloc(&s->d_alpha_scratch, scratch + ALLOC_SLACK), return 1);
-				s->alpha_scratch_cap = scratch;
-			}
-			a.d_scratch = s->d_alpha_scratch;
-		}
-		int arc = astc_alpha_launch(a);
-		if (arc != 0) { log_msg("alpha pre-pass launch failed (hip error %d)", arc); return 2; }
+		const int arc = alpha_prepass(s, stream, d_image, s->d_alpha, job.dim_x, rows_with_halo, dim_z, job.data_type, job.swz[3], job.a_scale_radius);
+		if (arc != 0) return arc;
 		img.alpha_avg = s->d_alpha + (size_t)halo_above * job.dim_x;
-		// (a large scratch is not kept for the life of the context: the pre-pass runs once per call, its scratch goes back
-		//  as soon as the stream is past the kernel -- hipFree waits for that)
-		if (s->alpha_scratch_cap > ((size_t)64 << 20))
-		{
-			(void)hipStreamSynchronize(stream);
-			(void)hipFree(s->d_alpha_scratch);
-			s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
-		}
+		alpha_scratch_release(s, stream);
 	}
 
-	// Chunks bound the time between cancel checks / progress callbacks on huge images; a chunk is
-	// still tens of thousands of workgroups, far more than the 256 CUs need to stay full.
+	// (chunks: run_chunks)
 	const bool chunked = (progress && progress->callback) || job.host_slices;
 	size_t chunk = chunked ? (size_t)1 << 18 : nblocks;
 	if (banded)
@@ -884,32 +980,23 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 		HIP_TRY(hipMemsetAsync(s->d_prof, 0, need, stream), return 2);
 	}
 #endif
-	if (job.kernel_ms) HIP_TRY(hipEventRecord(s->ev0, stream), return 2);
-	// The host stays at most two chunks ahead of the device: chunk k-1's completion event is waited for
-	// (and reported to the progress callback) after chunk k has been queued, so the device always has its
-	// next kernel waiting, a cancel takes effect within two chunks, and nothing synchronises a whole stream.
-	size_t launched = 0, chunk_index = 0, prev_blocks = 0;
-	for (size_t first = 0; first < nblocks; first += chunk, chunk_index++)
+	ChunkLoop L;
+	L.k.d_tab = s->d_tab; L.k.lds_bytes = b->lds_bytes; L.k.img = img; L.k.d_out = d_out;
+	L.k.stream = stream; L.k.d_prof = s->d_prof; L.k.d_set = nullptr;
+	L.nblocks = nblocks; L.chunk = chunk; L.chunked = chunked; L.timed = job.kernel_ms != nullptr;
+	L.cancel_flag = job.cancel_flag; L.progress = progress;
+	if (banded)
 	{
-		if (job.cancel_flag && job.cancel_flag->load(std::memory_order_relaxed)) break;
-		size_t n = nblocks - first < chunk ? nblocks - first : chunk;
-		if (banded)
-		{
+		L.before_launch = [&](size_t first, size_t n) -> int {
 			// band 0 first; from then on the next band is queued before this band's kernel, so that it
 			// crosses PCIe while the kernel runs (and ahead of this band's results on the copy stream)
 			if (first == 0 && upload_band(0, n) != 0) return 2;
 			const size_t next = first + n;
 			if (next < nblocks && upload_band(next, nblocks - next < chunk ? nblocks - next : chunk) != 0) return 2;
 			HIP_TRY(hipStreamWaitEvent(stream, s->ev_copy[(first / chunk) & 1], 0), return 2);
-		}
-		KernelLaunch k;
-		k.d_tab = s->d_tab; k.lds_bytes = b->lds_bytes; k.img = img; k.d_out = d_out;
-		k.first = (uint32_t)first; k.count = (uint32_t)n; k.stream = stream; k.d_prof = s->d_prof;
-		int lrc = kernel_launch(b, s, k);
-		if (lrc != 0) { log_msg("kernel launch failed (hip error %d)", lrc); return 2; }
-		launched = first + n;
-		if (banded)
-		{
+			return 0;
+		};
+		L.after_launch = [&](size_t first, size_t n, size_t chunk_index, size_t prev_blocks) -> int {
 			// this band's blocks go home on the copy stream once its kernel is done; the band before it is collected
 			// meanwhile (its transfer was queued one iteration ago, behind its own kernel)
 			HIP_TRY(hipEventRecord(s->ev_band, stream), return 2);
@@ -917,20 +1004,11 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 			HIP_TRY(hipMemcpyAsync(s->h_out[chunk_index & 1], d_out + first * 16, n * 16, hipMemcpyDeviceToHost, s->copy_stream), return 2);
 			HIP_TRY(hipEventRecord(s->ev_out[chunk_index & 1], s->copy_stream), return 2);
 			if (chunk_index > 0 && collect_band(first - prev_blocks, prev_blocks) != 0) return 2;
-			prev_blocks = n;
-		}
-		else if (chunked)
-		{
-			HIP_TRY(hipEventRecord(s->ev_done[chunk_index % 3], stream), return 2);
-			if (chunk_index > 0)
-			{
-				HIP_TRY(hipEventSynchronize(s->ev_done[(chunk_index - 1) % 3]), return 2);
-				if (progress) progress->add(prev_blocks);
-			}
-			prev_blocks = n;
-		}
+			return 0;
+		};
 	}
-	if (job.kernel_ms) HIP_TRY(hipEventRecord(s->ev1, stream), return 2);
+	if (run_chunks(b, s, L) != 0) return 2;
+	const size_t launched = L.launched, prev_blocks = L.prev_blocks;
 
 	if (job.host_out && !banded && launched)
 	{
@@ -1293,6 +1371,172 @@ int backend_compare(Backend* bk, const CompareJob& job)
 	int lrc = astc_compare_launch(c);
 	if (lrc != 0) { log_msg("compare kernel launch failed (hip error %d)", lrc); return 2; }
 	HIP_TRY(hipMemcpyAsync(job.sums, b->d_sums, METRIC_SUMS_HOST * sizeof(double), hipMemcpyDeviceToHost, stream), return 2);
+	HIP_TRY(hipStreamSynchronize(stream), return 2);
+	return 0;
+}
+
+/* Image sets.  Every buffer of the set must live on the device that owns entry 0's first buffer (or be unknown to the runtime,
+ * which the single-image path allows as well); otherwise rc 3 and nothing is launched. */
+static bool set_on_one_device(const DeviceSlot* s, const void* const* ptrs, size_t count)
+{
+	for (size_t i = 0; i < count; i++)
+	{
+		hipPointerAttribute_t attr;
+		memset(&attr, 0, sizeof(attr));
+		if (!ptrs[i] || hipPointerGetAttributes(&attr, ptrs[i]) != hipSuccess) { (void)hipGetLastError(); continue; }
+		if (attr.device != s->device)
+		{
+			log_msg("image set entry %zu: a buffer of device %d, entry 0's are on device %d", i / 2, attr.device, s->device);
+			return false;
+		}
+	}
+	return true;
+}
+
+/* Grows the slot's table buffer to `bytes` and queues the upload of the host copy (s->h_set). */
+static int set_table_upload(DeviceSlot* s, hipStream_t stream, size_t bytes)
+{
+	if (s->set_cap < bytes)
+	{
+		if (s->d_set) (void)hipFree(s->d_set);
+		s->d_set = nullptr; s->set_cap = 0;
+		HIP_TRY(hipMalloc(&s->d_set, bytes + ALLOC_SLACK), return 1);
+		s->set_cap = bytes;
+	}
+	HIP_TRY(hipMemcpyAsync(s->d_set, s->h_set.data(), bytes, hipMemcpyHostToDevice, stream), return 2);
+	return 0;
+}
+
+static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& job, Progress* progress)
+{
+	hipStream_t stream;
+	if (!pick_stream(s, job.stream, &stream)) return 3;
+	const uint32_t count = job.count;
+	const size_t rec_offset = image_set_records_offset(count);
+	const size_t table_bytes = rec_offset + (size_t)count * sizeof(ImageSetEntryDesc);
+	s->h_set.assign(table_bytes, 0);
+	uint32_t* first = reinterpret_cast<uint32_t*>(s->h_set.data() + image_set_first_offset());
+	ImageSetEntryDesc* rec = reinterpret_cast<ImageSetEntryDesc*>(s->h_set.data() + rec_offset);
+	// the entries' blocks back to back; the alpha averages of the entries that need them side by side in one buffer
+	size_t nblocks = 0, alpha_floats = 0;
+	std::vector<size_t> alpha_at(count, 0);
+	for (uint32_t e = 0; e < count; e++)
+	{
+		const CompressJob& en = job.entries[e];
+		rec[e].img = image_desc(b, en, en.device_data);
+		rec[e].out = en.device_out;
+		first[e] = (uint32_t)nblocks;
+		nblocks += (size_t)rec[e].img.blocks_x * rec[e].img.blocks_y * rec[e].img.blocks_z;
+		if (en.a_scale_radius != 0)
+		{
+			alpha_at[e] = alpha_floats;
+			alpha_floats += ((size_t)en.dim_x * en.dim_y + 63) & ~(size_t)63;
+		}
+	}
+	if (nblocks > 0xFFFFFFFFu) return 3;
+	ImageSetTable* t = reinterpret_cast<ImageSetTable*>(s->h_set.data());
+	t->count = count;
+	t->total = (uint32_t)nblocks;
+	jit_count_blocks(b, s, nblocks);
+
+	if (alpha_floats)
+	{
+		const size_t need = alpha_floats * sizeof(float);
+		if (s->alpha_cap < need)
+		{
+			if (s->d_alpha) (void)hipFree(s->d_alpha);
+			s->d_alpha = nullptr; s->alpha_cap = 0;
+			HIP_TRY(hipMalloc(&s->d_alpha, need + ALLOC_SLACK), return 1);
+			s->alpha_cap = need;
+		}
+		for (uint32_t e = 0; e < count; e++)
+		{
+			const CompressJob& en = job.entries[e];
+			if (en.a_scale_radius == 0) continue;
+			const uint32_t dim_z = en.dim_z ? en.dim_z : 1u;
+			const int arc = alpha_prepass(s, stream, en.device_data, s->d_alpha + alpha_at[e], en.dim_x, en.dim_y, dim_z, en.data_type, en.swz[3], en.a_scale_radius);
+			if (arc != 0) return arc;
+			rec[e].img.alpha_avg = s->d_alpha + alpha_at[e];
+		}
+		alpha_scratch_release(s, stream);
+	}
+	const int urc = set_table_upload(s, stream, table_bytes);
+	if (urc != 0) return urc;
+
+	ChunkLoop L;
+	L.k.d_tab = s->d_tab; L.k.lds_bytes = b->lds_bytes; L.k.img = rec[0].img; L.k.d_out = rec[0].out;
+	L.k.stream = stream; L.k.d_prof = s->d_prof; L.k.d_set = reinterpret_cast<const ImageSetTable*>(s->d_set);
+#if defined(ASTC_TRACE)
+	L.k.d_prof = nullptr;      // (the search trace is a single-image debug aid: compress_on_slot_locked sizes its buffer)
+#endif
+	L.chunked = progress && progress->callback;
+	L.nblocks = nblocks; L.chunk = L.chunked ? (size_t)1 << 18 : nblocks;
+	L.timed = job.kernel_ms != nullptr;
+	L.cancel_flag = job.cancel_flag; L.progress = progress;
+	if (run_chunks(b, s, L) != 0) return 2;
+	HIP_TRY(hipStreamSynchronize(stream), return 2);
+	if (L.chunked && L.prev_blocks && L.launched) progress->add(L.prev_blocks);
+	if (job.kernel_ms) HIP_TRY(hipEventElapsedTime(job.kernel_ms, s->ev0, s->ev1), return 2);
+	return 0;
+}
+
+int backend_compress_set(Backend* b, const CompressSetJob& job)
+{
+	DeviceGuard guard;
+	int st = 0;
+	DeviceSlot* s = slot_for_pointer(b, job.entries[0].device_data, &st);
+	if (!s) return st ? st : 2;
+	std::vector<const void*> ptrs;
+	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_data); ptrs.push_back(job.entries[e].device_out); }
+	if (!set_on_one_device(s, ptrs.data(), ptrs.size())) return 3;
+	Progress progress;
+	progress.done = 0; progress.callback = job.progress; progress.total = 0;
+	for (uint32_t e = 0; e < job.count; e++)
+	{
+		const CompressJob& en = job.entries[e];
+		const uint32_t dz = en.dim_z ? en.dim_z : 1u;
+		progress.total += (size_t)((en.dim_x + b->root.dim_x - 1) / b->root.dim_x) * ((en.dim_y + b->root.dim_y - 1) / b->root.dim_y) *
+		                  ((dz + b->root.dim_z - 1) / b->root.dim_z);
+	}
+	std::lock_guard<std::mutex> busy(s->busy);
+	HIP_TRY(hipSetDevice(s->device), return 2);
+	return compress_set_locked(b, s, job, &progress);
+}
+
+int backend_decompress_set(Backend* bk, const DecompressSetJob& job)
+{
+	DeviceGuard guard;
+	int st = 0;
+	DeviceSlot* s = slot_for_pointer(bk, job.entries[0].device_image, &st);
+	if (!s) return st ? st : 2;
+	std::vector<const void*> ptrs;
+	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_image); ptrs.push_back(job.entries[e].device_blocks); }
+	if (!set_on_one_device(s, ptrs.data(), ptrs.size())) return 3;
+	std::lock_guard<std::mutex> busy(s->busy);
+	HIP_TRY(hipSetDevice(s->device), return 2);
+	hipStream_t stream;
+	if (!pick_stream(s, job.stream, &stream)) return 3;
+	std::vector<DecodeLaunch> d(job.count);
+	for (uint32_t e = 0; e < job.count; e++)
+	{
+		const DecompressDeviceJob& en = job.entries[e];
+		DecodeLaunch& x = d[e];
+		x.d_blocks = en.device_blocks;
+		x.d_image = en.device_image;
+		x.d_tables = s->d_dectab;
+		x.dim_x = en.dim_x; x.dim_y = en.dim_y; x.dim_z = en.dim_z ? en.dim_z : 1u; x.data_type = en.data_type;
+		for (int i = 0; i < 4; i++) x.swz[i] = en.swz[i];
+		x.block_x = bk->root.dim_x; x.block_y = bk->root.dim_y; x.block_z = bk->root.dim_z;
+		x.profile = bk->cfg.profile;
+		x.stream = nullptr;
+	}
+	const size_t bytes = astc_decode_set_bytes(job.count);
+	s->h_set.assign(bytes, 0);
+	const uint32_t runs = astc_decode_set_build(s->h_set.data(), d.data(), job.count);
+	const int urc = set_table_upload(s, stream, bytes);
+	if (urc != 0) return urc;
+	int lrc = astc_decode_set_launch(s->d_set, runs, stream);
+	if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
 	HIP_TRY(hipStreamSynchronize(stream), return 2);
 	return 0;
 }

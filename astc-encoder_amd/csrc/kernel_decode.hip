@@ -7,6 +7,7 @@
 #include "wave_decode.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstring>
 
 namespace astcd {
 
@@ -23,6 +24,37 @@ astc_decompress_blocks(const uint8_t* __restrict__ blocks, DecodeImage img, uint
 	decode_row_batch(img, blocks, bx0, row0 + blockIdx.y, layer0 + blockIdx.z, (int)(left < (uint32_t)DECODE_BATCH ? left : (uint32_t)DECODE_BATCH), batch);
 }
 
+/* An image set (astcenc_amd_compress_images_device's counterpart): the runs of every entry back to back on a 1D grid, the
+ * entry of a run found in the table (image_set.h), its place in the entry -- run, block row, layer -- split off with scalar
+ * arithmetic.  `run0`: the launch covers runs [run0, run0 + gridDim.x) of the set (astc_decode_set_launch). */
+struct DecodeSetEntry {
+	DecodeImage img;
+	const uint8_t* blocks;
+	uint32_t runs_x;          // runs per block row: ceil(blocks_x / DECODE_BATCH)
+	uint32_t runs_xy;         // ... per layer of blocks
+};
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
+astc_decompress_set(const ImageSetTable* __restrict__ set, uint32_t run0)
+{
+	__shared__ DecodeBatch batch;
+	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
+	const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
+	const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
+	const __attribute__((address_space(4))) uint32_t* first = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
+	const uint32_t r = run0 + blockIdx.x;
+	const uint32_t e = image_set_find(first, count, r);
+	const DecodeSetEntry rec = image_set_record<DecodeSetEntry>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
+		t + image_set_records_offset(count) + (size_t)e * sizeof(DecodeSetEntry)));
+	const uint32_t local = r - first[e];
+	const uint32_t bz = local / rec.runs_xy;
+	const uint32_t in_layer = local - bz * rec.runs_xy;
+	const uint32_t by = in_layer / rec.runs_x;
+	const uint32_t bx0 = (in_layer - by * rec.runs_x) * (uint32_t)DECODE_BATCH;
+	const uint32_t left = rec.img.blocks_x - bx0;
+	decode_row_batch(rec.img, rec.blocks, bx0, by, bz, (int)(left < (uint32_t)DECODE_BATCH ? left : (uint32_t)DECODE_BATCH), batch);
+}
+
 size_t astc_decode_tables_bytes() { return sizeof(DecodeTables); }
 
 void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uint32_t block_z)
@@ -30,7 +62,7 @@ void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uin
 	decode_tables_build(*static_cast<DecodeTables*>(out), (int)block_x, (int)block_y, (int)block_z);
 }
 
-int astc_decode_launch(const DecodeLaunch& d)
+static DecodeImage decode_image(const DecodeLaunch& d)
 {
 	DecodeImage img;
 	img.data = d.d_image;
@@ -44,15 +76,24 @@ int astc_decode_launch(const DecodeLaunch& d)
 	img.blocks_z = (d.dim_z + d.block_z - 1) / d.block_z;
 	img.profile = d.profile;
 	decode_image_prepare(img);
+	return img;
+}
+
+// (ASTCENC_AMD_DECODE_GRID_LIMIT: a smaller limit for tests/test_decode.py, which cannot allocate a 262 144-row image)
+static uint32_t decode_grid_limit_from_env()
+{
+	const char* e = getenv("ASTCENC_AMD_DECODE_GRID_LIMIT");
+	const long v = e ? strtol(e, nullptr, 10) : 0;
+	return (uint32_t)(v >= 1 && v < 65535 ? v : 0);
+}
+
+int astc_decode_launch(const DecodeLaunch& d)
+{
+	const DecodeImage img = decode_image(d);
 	// Grid y / z hold block rows / layers of blocks, at most 65535 each: a taller stream (more than 262 140 texel rows at the
 	// smallest footprint, or as many slices) is covered by several launches, each told where its rows and layers start.  The
 	// image record stays the whole image's, so every address is formed from the real dimensions.
-	// (ASTCENC_AMD_DECODE_GRID_LIMIT: a smaller limit for tests/test_decode.py, which cannot allocate a 262 144-row image)
-	static const uint32_t limit = []() {
-		const char* e = getenv("ASTCENC_AMD_DECODE_GRID_LIMIT");
-		const long v = e ? strtol(e, nullptr, 10) : 0;
-		return (uint32_t)(v >= 1 && v < 65535 ? v : 65535);
-	}();
+	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 65535u; }();
 	const uint32_t runs = (img.blocks_x + (uint32_t)DECODE_BATCH - 1u) / (uint32_t)DECODE_BATCH;
 	for (uint32_t layer0 = 0; layer0 < img.blocks_z; layer0 += limit)
 	{
@@ -62,6 +103,46 @@ int astc_decode_launch(const DecodeLaunch& d)
 			const uint32_t rows = img.blocks_y - row0 < limit ? img.blocks_y - row0 : limit;
 			hipLaunchKernelGGL(astc_decompress_blocks, dim3(runs, rows, layers), dim3(64), 0, static_cast<hipStream_t>(d.stream), d.d_blocks, img, row0, layer0);
 		}
+	}
+	return (int)hipGetLastError();
+}
+
+size_t astc_decode_set_bytes(uint32_t count)
+{
+	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeSetEntry);
+}
+
+uint32_t astc_decode_set_build(void* out, const DecodeLaunch* entries, uint32_t count)
+{
+	uint8_t* t = static_cast<uint8_t*>(out);
+	memset(t, 0, astc_decode_set_bytes(count));
+	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
+	DecodeSetEntry* rec = reinterpret_cast<DecodeSetEntry*>(t + image_set_records_offset(count));
+	uint32_t runs = 0;
+	for (uint32_t e = 0; e < count; e++)
+	{
+		rec[e].img = decode_image(entries[e]);
+		rec[e].blocks = entries[e].d_blocks;
+		rec[e].runs_x = (rec[e].img.blocks_x + (uint32_t)DECODE_BATCH - 1u) / (uint32_t)DECODE_BATCH;
+		rec[e].runs_xy = rec[e].runs_x * rec[e].img.blocks_y;
+		first[e] = runs;
+		runs += rec[e].runs_xy * rec[e].img.blocks_z;
+	}
+	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
+	h->count = count;
+	h->total = runs;
+	return runs;
+}
+
+int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream)
+{
+	// grid x: at most 2^32 - 1 work-items in all, i.e. 2^26 - 1 wavefronts of 64 (or the test limit above)
+	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 0xFFFFFFFFu / 64u; }();
+	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);
+	for (uint32_t run0 = 0; run0 < runs; run0 += limit)
+	{
+		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
+		hipLaunchKernelGGL(astc_decompress_set, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
 	}
 	return (int)hipGetLastError();
 }

@@ -8,6 +8,7 @@
 //   ASTC_KERNEL_NAME
 #pragma once
 #include "wave_block.h"
+#include "image_set.h"
 
 #ifndef ASTC_KERNEL_LINKAGE
 #define ASTC_KERNEL_LINKAGE
@@ -30,15 +31,49 @@ __device__ inline uint32_t xcd_block_remap(uint32_t b, uint32_t n)
 	return (b % 8u) * per + (b / 8u);
 }
 
+/* ... the same for the launches of an image set, in runs of XCD_SET_RUN blocks dealt round-robin: a set mixes images whose
+ * blocks cost differently (the levels of a mip chain, textures of several kinds), and with one contiguous eighth per XCD the
+ * XCDs that drew the costly entries would run on alone at the end.  A run still keeps raster neighbours together. */
+constexpr uint32_t XCD_SET_RUN = 1024;
+__device__ inline uint32_t xcd_block_remap_runs(uint32_t b, uint32_t n)
+{
+	const uint32_t group = XCD_SET_RUN * 8u;
+	const uint32_t even = n / group * group;
+	if (b >= even) return b;               // ragged tail keeps identity order
+	const uint32_t g = b / group, r = b - g * group;
+	return g * group + (r % 8u) * XCD_SET_RUN + r / 8u;
+}
+
 // (the occupancy bound twice: __launch_bounds__ is a macro of the HIP headers, and the run-time compiler of ROCm 7.0 drops its
 //  second argument -- 160 VGPRs, three waves per SIMD -- where hipcc and the ROCm 7.2 run-time compiler honour it)
 ASTC_KERNEL_LINKAGE __global__ void __launch_bounds__(64, ASTC_WAVES_PER_EU) __attribute__((amdgpu_waves_per_eu(ASTC_WAVES_PER_EU)))
 ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
-                 uint8_t* __restrict__ out, uint32_t first_block, uint32_t num_blocks, unsigned long long* prof)
+                 uint8_t* __restrict__ out, uint32_t first_block, uint32_t num_blocks, unsigned long long* prof,
+                 const ImageSetTable* __restrict__ set)
 {
 	uint8_t* lds = lds_base();
 
-	uint32_t b = xcd_block_remap(blockIdx.x, num_blocks) + first_block;
+	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
+	uint32_t b = (set ? xcd_block_remap_runs(blockIdx.x, num_blocks) : xcd_block_remap(blockIdx.x, num_blocks)) + first_block;
+#if defined(ASTC_TRACE)
+	const uint32_t trace_slot = b;
+#endif
+	// An image set (astcenc_amd_compress_images_device): `b` counts the blocks of all entries back to back.  The entry that
+	// holds it is found in the table (image_set.h); its image record and output replace the by-value ones, and `b` becomes
+	// the block's index within the entry.  Scalar loads through a constant pointer, as for `tab` below.
+	if (set)
+	{
+		const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
+		const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
+		const __attribute__((address_space(4))) uint32_t* first =
+			reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
+		const uint32_t e = image_set_find(first, count, b);
+		const ImageSetEntryDesc rec = image_set_record<ImageSetEntryDesc>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
+			t + image_set_records_offset(count) + (size_t)e * sizeof(ImageSetEntryDesc)));
+		img = rec.img;
+		out = rec.out;
+		b -= first[e];
+	}
 	// raster block order: x fastest, then y, then z (ref: astcenc_entry.cpp:961-966)
 	uint32_t row = b / img.blocks_x;
 	uint32_t bx = b - row * img.blocks_x;
@@ -49,7 +84,6 @@ ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
 	// it (fields of `tab - CTX_LAYOUT_BACK` written as such cost a 64-bit subtraction per field)
 	// (through an integer the optimiser cannot see through, and back as a pointer to constant memory -- a generic pointer
 	//  would make every table read a flat load)
-	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
 	uintptr_t base_bits = reinterpret_cast<uintptr_t>(tab) - CTX_LAYOUT_BACK;
 	asm volatile("" : "+s"(base_bits));
 	const uint8_t* const base = (const uint8_t*)(constant_bytes)base_bits;
@@ -81,7 +115,7 @@ ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
 	c.Ts = lds_row_stride(c.Tp);
 #if defined(ASTC_TRACE)
 	// trace builds: `prof` is the search trace buffer, one slice per block of the image (wave_ctx.h: TRACE_PUT)
-	if (prof) prof = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint32_t*>(prof) + (size_t)b * TRACE_WORDS_PER_BLOCK);
+	if (prof) prof = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint32_t*>(prof) + (size_t)trace_slot * TRACE_WORDS_PER_BLOCK);
 #endif
 	c.prof = prof;
 

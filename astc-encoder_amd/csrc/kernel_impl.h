@@ -42,11 +42,11 @@ int ASTC_LAUNCH_NAME(const KernelLaunch& k)
 	static const unsigned pad = getenv("ASTC_LDS_PAD") ? (unsigned)atoi(getenv("ASTC_LDS_PAD")) : 0u;
 	if (pad) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ASTC_KERNEL_NAME), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(k.lds_bytes + pad));
 	hipLaunchKernelGGL(ASTC_KERNEL_NAME, dim3(k.count), dim3(64), k.lds_bytes + pad, static_cast<hipStream_t>(k.stream),
-	                   k.d_tab, k.img, k.d_out, k.first, k.count, k.d_prof);
+	                   k.d_tab, k.img, k.d_out, k.first, k.count, k.d_prof, k.d_set);
 	return (int)hipGetLastError();
 #endif
 	hipLaunchKernelGGL(ASTC_KERNEL_NAME, dim3(k.count), dim3(64), k.lds_bytes, static_cast<hipStream_t>(k.stream),
-	                   k.d_tab, k.img, k.d_out, k.first, k.count, k.d_prof);
+	                   k.d_tab, k.img, k.d_out, k.first, k.count, k.d_prof, k.d_set);
 	return (int)hipGetLastError();
 }
 

@@ -47,6 +47,7 @@ ASTC_EMBED(astc_src_wave_refine, "wave_refine.h")
 ASTC_EMBED(astc_src_wave_batch, "wave_batch.h")
 ASTC_EMBED(astc_src_wave_partition, "wave_partition.h")
 ASTC_EMBED(astc_src_wave_pack, "wave_pack.h")
+ASTC_EMBED(astc_src_image_set, "image_set.h")
 
 extern char** environ;
 
@@ -63,6 +64,7 @@ const EmbeddedHeader kHeaders[] = {
 	{ "wave_color.h", astc_src_wave_color, astc_src_wave_color_end }, { "wave_color_hdr.h", astc_src_wave_color_hdr, astc_src_wave_color_hdr_end },
 	{ "wave_refine.h", astc_src_wave_refine, astc_src_wave_refine_end }, { "wave_batch.h", astc_src_wave_batch, astc_src_wave_batch_end },
 	{ "wave_partition.h", astc_src_wave_partition, astc_src_wave_partition_end }, { "wave_pack.h", astc_src_wave_pack, astc_src_wave_pack_end },
+	{ "image_set.h", astc_src_image_set, astc_src_image_set_end },
 };
 constexpr int kHeaderCount = (int)(sizeof(kHeaders) / sizeof(kHeaders[0]));
 constexpr long JIT_MAX_SCRATCH_BYTES = 32;

@@ -91,8 +91,27 @@ EXPORTS = ["astcenc_config_init", "astcenc_context_alloc", "astcenc_compress_ima
 EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume_device", "astcenc_amd_decompress_image_device",
                "astcenc_amd_compare_images_device", "astcenc_amd_backend_name", "astcenc_amd_context_device_count",
                "astcenc_amd_context_set_option", "astcenc_amd_compare_images_hdr_device", "astcenc_amd_context_kernel_name",
-               "astcenc_amd_set_log_callback", "astcenc_amd_context_specialize"]
+               "astcenc_amd_set_log_callback", "astcenc_amd_context_specialize", "astcenc_amd_compress_images_device",
+               "astcenc_amd_decompress_images_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
+
+
+class ImageSetEntry(C.Structure):
+    """struct astcenc_amd_image_set_entry (include/astcenc_amd.h)."""
+    _fields_ = [("image", C.c_void_p), ("blocks", C.c_void_p), ("blocks_len", C.c_size_t),
+                ("dim_x", C.c_uint), ("dim_y", C.c_uint), ("dim_z", C.c_uint), ("data_type", C.c_int), ("swizzle", Swizzle)]
+
+
+def image_set_entry(image, blocks, swizzle=SWZ_RGBA, blocks_len=None):
+    """ImageSetEntry of two device tensors: `image` [H, W, 4] or [D, H, W, 4] of uint8 / float16 / float32 (contiguous) and
+    `blocks`, uint8 (blocks_len: its size in bytes unless given)."""
+    import torch
+    types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
+    assert image.is_contiguous() and blocks.is_contiguous() and image.dim() in (3, 4) and image.shape[-1] == 4
+    d = image.shape[0] if image.dim() == 4 else 1
+    h, w = image.shape[-3], image.shape[-2]
+    return ImageSetEntry(image.data_ptr(), blocks.data_ptr(), blocks.numel() * blocks.element_size() if blocks_len is None else blocks_len,
+                         w, h, d, types[image.dtype], Swizzle(*swizzle))
 
 
 class ErrorSums(C.Structure):
@@ -193,6 +212,12 @@ class Library:
                                                              C.POINTER(C.c_float)]
             L.astcenc_amd_compress_volume_device.restype = C.c_int
 
+        if hasattr(L, "astcenc_amd_compress_images_device"):
+            L.astcenc_amd_compress_images_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p, C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_images_device.restype = C.c_int
+            L.astcenc_amd_decompress_images_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p]
+            L.astcenc_amd_decompress_images_device.restype = C.c_int
+
     # -- thin wrappers returning error codes, as the C API does --
     def config_init(self, profile, bx, by, bz, quality, flags):
         cfg = Config()
@@ -264,6 +289,31 @@ class Library:
             return out
         finally:
             self.context_free(ctx)
+
+    @staticmethod
+    def _set_args(entries, stream):
+        """ctypes array of the entries (ImageSetEntry, or (image, blocks[, swizzle]) tuples of torch tensors) and the stream:
+        a torch stream, a raw hipStream_t, or None for torch's current stream."""
+        entries = [e if isinstance(e, ImageSetEntry) else image_set_entry(*e) for e in entries]
+        arr = (ImageSetEntry * len(entries))(*entries) if entries else None
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream()
+        return arr, len(entries), getattr(stream, "cuda_stream", stream)
+
+    def compress_images_device(self, ctx, entries, stream=None):
+        """astcenc_amd_compress_images_device over `entries` (see _set_args); returns the astcenc_error, the kernel time of the
+        call (ms) in self.last_kernel_ms."""
+        arr, n, s = self._set_args(entries, stream)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_images_device(ctx, arr, n, s, C.byref(ms))
+        self.last_kernel_ms = ms.value
+        return err
+
+    def decompress_images_device(self, ctx, entries, stream=None):
+        """astcenc_amd_decompress_images_device over `entries` (see _set_args): every entry's blocks into its image."""
+        arr, n, s = self._set_args(entries, stream)
+        return self.lib.astcenc_amd_decompress_images_device(ctx, arr, n, s)
 
     def decompress(self, data, width, height, block=(6, 6), profile=PRF_LDR, out_type=np.uint8, depth=None):
         """Decode blocks back to [H, W, 4] ([D, H, W, 4] when depth is given) through

@@ -65,6 +65,45 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_image_device(
 	const struct astcenc_swizzle* swizzle,
 	void* hip_stream);
 
+/* Image sets: many device-resident images -- a mip chain, the textures of a scene, a batch of a dataset -- compressed or
+ * decompressed in one call with one context.  One entry per image.  Compression reads `image` and writes `blocks`;
+ * decompression reads `blocks` and writes `image`, so one array can describe both directions. */
+struct astcenc_amd_image_set_entry {
+	void* image;                   /* device pointer: dim_z slices of dim_x * dim_y texels, tightly packed RGBA rows */
+	void* blocks;                  /* device pointer: 16 bytes per block, raster block order */
+	size_t blocks_len;             /* bytes available at / readable from `blocks` */
+	unsigned int dim_x, dim_y, dim_z;
+	enum astcenc_type data_type;
+	struct astcenc_swizzle swizzle;
+};
+
+/* Compress every entry of entries[0 .. entry_count).  Every entry's blocks are exactly those astcenc_amd_compress_volume_device
+ * writes for that entry alone -- its per-slice loading default and ASTCENC_AMD_OPT_PER_SLICE_FAST_LOAD, the alpha-scale pre-pass
+ * (run per entry, 2D footprints), the entry's own data type and swizzle -- but the blocks of all entries run in the same chain
+ * of kernel launches, so that a set of small images fills the device as one large image does.
+ *
+ *   - Every entry is checked with the checks and error codes of astcenc_amd_compress_volume_device (a null `image` or `blocks`:
+ *     ASTCENC_ERR_BAD_CONTEXT, as there), all of them before anything is launched: a bad entry makes the call return its error
+ *     with nothing written, and the log callback (astcenc_amd_set_log_callback) names the entry's index.
+ *   - entry_count == 0 returns ASTCENC_SUCCESS and does nothing; a null `entries` with a non-zero count, a null context, or a
+ *     set of more than 2^32 - 1 blocks in all return ASTCENC_ERR_BAD_PARAM.
+ *   - The call runs on the device that owns entry 0's image; a buffer of any entry on another device returns
+ *     ASTCENC_ERR_BAD_PARAM.  Outputs must not overlap each other or any input (not checked).
+ *   - Cancel, progress and timing as in astcenc_amd_compress_volume_device: the same cancel rules; the progress callback sees a
+ *     monotonic percentage of the whole set's blocks; kernel_ms covers every launch of the call; the call returns once the
+ *     work on hip_stream has completed. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_images_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	void* hip_stream, float* kernel_ms);
+
+/* Decompress every entry: each entry's image is exactly what astcenc_amd_decompress_image_device writes for that entry alone
+ * (same checks and error codes, all before anything is launched), one launch for the whole set.  Same argument rules as above. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_images_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	void* hip_stream);
+
 /* Error sums of two device-resident images of the same size, the quantities the reference CLI's quality
  * report is made of (ref: compute_error_metrics, Source/astcenccli_error_metrics.cpp:110-300):
  *   PSNR (LDR-RGBA)     = 10 log10(4 texels / (squared_error[0] + .. + [3]))
