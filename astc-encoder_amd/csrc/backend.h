@@ -9,6 +9,7 @@
 #include <atomic>
 #include "astc_tables.h"
 #include "image_set.h"
+#include "mip_filter.h"
 
 namespace astcd {
 
@@ -64,6 +65,18 @@ struct CompressSetJob {
 	float*   kernel_ms;
 	const std::atomic<int>* cancel_flag;
 	void (*progress)(float);
+	const struct MipChainJob* generate;   // non-null: generate this mip chain first, on the same stream (the entries are its levels)
+};
+
+/* Levels 1 .. level_count - 1 of a 2D device image (astcenc_amd_generate_mip_chain_device, mip_filter.h): level i at
+ * device_levels + texels_offset[i]; runs on the device that owns device_image, every buffer must be there (else rc 3). */
+struct MipChainJob {
+	const void* device_image;
+	uint32_t dim_x, dim_y, data_type, level_count;
+	uint32_t srgb;             // U8 channels 0-2 are sRGB-encoded (an ASTCENC_PRF_LDR_SRGB context)
+	uint8_t* device_levels;
+	size_t texels_offset[MIP_MAX_LEVELS];
+	void* stream;
 };
 
 /* ... and its decompression (astcenc_amd_decompress_images_device): every entry as a DecompressDeviceJob (stream unused). */
@@ -101,6 +114,7 @@ int backend_compare(Backend* b, const CompareJob& job);
  * entry points live in astcenc_set.cpp, which the sequential build of oracle/emu does not link.) */
 int backend_compress_set(Backend* b, const CompressSetJob& job);
 int backend_decompress_set(Backend* b, const DecompressSetJob& job);
+int backend_generate_mips(Backend* b, const MipChainJob& job);
 /* A line for the diagnostics callback (astcenc_amd_set_log_callback), printf-style. */
 void backend_log(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 const char* backend_name();
@@ -187,6 +201,19 @@ int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream);
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();
 void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uint32_t block_z);
+
+/* Mip chain generation (kernel_mips.hip): levels 1 .. levels - 1 of level[0] (dim_x x dim_y texels of data_type), level[i]
+ * made from level[i - 1].  d_srgb: the tables of astc_mip_srgb_tables_build in device memory (astc_mip_srgb_table_bytes()),
+ * used for RGBA8 when srgb != 0. */
+struct MipLaunch {
+	void* level[MIP_MAX_LEVELS];      // (level 0 is only read)
+	uint32_t dim_x, dim_y, data_type, levels, srgb;
+	const void* d_srgb;
+	void* stream;
+};
+int astc_mip_launch(const MipLaunch& m);
+size_t astc_mip_srgb_table_bytes();
+void astc_mip_srgb_tables_build(void* out);
 
 /* Image comparison launch (kernel_metrics.hip); d_sums = astc_compare_scratch_doubles() doubles of device memory,
  * the totals arrive in the first ten. */

@@ -47,9 +47,11 @@ struct DeviceSlot {
 	uint8_t* d_base;              // device allocation: context records, then the table blob
 	uint8_t* d_tab;               // the blob inside it
 	uint8_t* d_dectab;            // the decoder's per-footprint tables inside it (after the blob)
+	const double* d_srgb;         // the sRGB tables of mip chain generation inside it (after the decoder's)
 	hipStream_t stream;
 	hipStream_t copy_stream;      // PCIe traffic of the banded host-pointer path
 	hipEvent_t ev0, ev1, ev_copy[2], ev_band, ev_done[3], ev_out[2];
+	hipEvent_t ev_gen;            // start of a mip chain's generation: its compression's kernel_ms counts from here
 	// pinned staging of the banded host-pointer path: two bands of input in flight, the blocks of two bands on their way back
 	uint8_t* h_in[2]; size_t h_in_cap;
 	uint8_t* h_out[2]; size_t h_out_cap;
@@ -79,6 +81,7 @@ struct Backend {
 	std::mutex slots_mu;              // guards `extra`
 	std::vector<uint8_t> full;        // host copy of [LdsLayout][DeviceConfig][table blob][decoder tables], uploaded to every slot
 	size_t dectab_offset;             // of the decoder tables in it
+	size_t srgb_offset;               // of the sRGB tables of mip chain generation in it
 	DeviceConfig cfg;
 	uint32_t lds_bytes;
 	bool hdr;
@@ -321,7 +324,7 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_sums) (void)hipFree(s->d_sums);
 	if (s->d_prof) (void)hipFree(s->d_prof);
 	for (int i = 0; i < 2; i++) { if (s->h_in[i]) (void)hipHostFree(s->h_in[i]); if (s->h_out[i]) (void)hipHostFree(s->h_out[i]); }
-	for (hipEvent_t e : { s->ev_copy[0], s->ev_copy[1], s->ev_band, s->ev_done[0], s->ev_done[1], s->ev_done[2], s->ev_out[0], s->ev_out[1], s->ev0, s->ev1 })
+	for (hipEvent_t e : { s->ev_copy[0], s->ev_copy[1], s->ev_band, s->ev_done[0], s->ev_done[1], s->ev_done[2], s->ev_out[0], s->ev_out[1], s->ev0, s->ev1, s->ev_gen })
 		if (e) (void)hipEventDestroy(e);
 	if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -442,6 +445,7 @@ DeviceSlot* slot_create(Backend* b, int device, int* status)
 	s->ev0 = s->ev1 = s->ev_copy[0] = s->ev_copy[1] = s->ev_band = nullptr;
 	s->ev_done[0] = s->ev_done[1] = s->ev_done[2] = nullptr;
 	s->ev_out[0] = s->ev_out[1] = nullptr;
+	s->ev_gen = nullptr;
 	s->h_in[0] = s->h_in[1] = nullptr; s->h_in_cap = 0; s->h_out[0] = s->h_out[1] = nullptr; s->h_out_cap = 0;
 	s->d_image = nullptr; s->image_cap = 0; s->d_out = nullptr; s->out_cap = 0; s->d_alpha = nullptr; s->alpha_cap = 0;
 	s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
@@ -464,6 +468,7 @@ DeviceSlot* slot_create(Backend* b, int device, int* status)
 	SLOT_TRY(hipMemcpy(s->d_base, b->full.data(), b->full.size(), hipMemcpyHostToDevice), 2);
 	s->d_tab = s->d_base + CTX_LAYOUT_BACK;
 	s->d_dectab = s->d_base + b->dectab_offset;
+	s->d_srgb = reinterpret_cast<const double*>(s->d_base + b->srgb_offset);
 	SLOT_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), 2);
 	SLOT_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking), 2);
 	SLOT_TRY(hipEventCreateWithFlags(&s->ev_copy[0], hipEventDisableTiming), 2);
@@ -473,6 +478,7 @@ DeviceSlot* slot_create(Backend* b, int device, int* status)
 	for (int i = 0; i < 2; i++) SLOT_TRY(hipEventCreateWithFlags(&s->ev_out[i], hipEventDisableTiming), 2);
 	SLOT_TRY(hipEventCreate(&s->ev0), 2);
 	SLOT_TRY(hipEventCreate(&s->ev1), 2);
+	SLOT_TRY(hipEventCreate(&s->ev_gen), 2);
 #if defined(ASTC_PROFILE)
 	enum { PS_COUNT = 40 };
 	SLOT_TRY(hipMalloc(&s->d_prof, 2 * PS_COUNT * sizeof(unsigned long long)), 1);
@@ -612,10 +618,13 @@ Backend* backend_create(const uint8_t* blob, size_t blob_bytes, const DeviceConf
 		delete b; *status = 2; return nullptr;
 	}
 
-	// device allocation = [LdsLayout, 256 B][DeviceConfig, 256 B][table blob][decoder tables]; kernels get the blob pointer
+	// device allocation = [LdsLayout, 256 B][DeviceConfig, 256 B][table blob][decoder tables][sRGB tables of mip generation];
+	// kernels get the blob pointer
 	b->dectab_offset = (CTX_LAYOUT_BACK + blob_bytes + 255) & ~(size_t)255;
-	b->full.assign(b->dectab_offset + astc_decode_tables_bytes(), 0);
+	b->srgb_offset = (b->dectab_offset + astc_decode_tables_bytes() + 255) & ~(size_t)255;
+	b->full.assign(b->srgb_offset + astc_mip_srgb_table_bytes(), 0);
 	astc_decode_tables_build(b->full.data() + b->dectab_offset, b->root.dim_x, b->root.dim_y, b->root.dim_z);
+	astc_mip_srgb_tables_build(b->full.data() + b->srgb_offset);
 	memcpy(b->full.data(), layout, layout_bytes);
 	static_assert(sizeof(DeviceConfig) <= 256, "DeviceConfig outgrew its slot");
 	memcpy(b->full.data() + (CTX_LAYOUT_BACK - CTX_CONFIG_BACK), &b->cfg, sizeof(DeviceConfig));
@@ -1407,10 +1416,32 @@ static int set_table_upload(DeviceSlot* s, hipStream_t stream, size_t bytes)
 	return 0;
 }
 
+/* Queues the generation of a mip chain on `stream` (the slot's lock held). */
+static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChainJob& job)
+{
+	MipLaunch m;
+	memset(&m, 0, sizeof(m));
+	m.level[0] = const_cast<void*>(job.device_image);
+	for (uint32_t i = 1; i < job.level_count; i++) m.level[i] = job.device_levels + job.texels_offset[i];
+	m.dim_x = job.dim_x; m.dim_y = job.dim_y; m.data_type = job.data_type; m.levels = job.level_count;
+	m.srgb = job.srgb; m.d_srgb = s->d_srgb;
+	m.stream = stream;
+	const int lrc = astc_mip_launch(m);
+	if (lrc != 0) { log_msg("mip generation kernel launch failed (hip error %d)", lrc); return 2; }
+	return 0;
+}
+
 static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& job, Progress* progress)
 {
 	hipStream_t stream;
 	if (!pick_stream(s, job.stream, &stream)) return 3;
+	if (job.generate)
+	{
+		// the levels first (kernel_ms counts from here), then everything below reads them in stream order
+		if (job.kernel_ms) HIP_TRY(hipEventRecord(s->ev_gen, stream), return 2);
+		const int grc = generate_mips_locked(s, stream, *job.generate);
+		if (grc != 0) return grc;
+	}
 	const uint32_t count = job.count;
 	const size_t rec_offset = image_set_records_offset(count);
 	const size_t table_bytes = rec_offset + (size_t)count * sizeof(ImageSetEntryDesc);
@@ -1476,7 +1507,7 @@ static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& 
 	if (run_chunks(b, s, L) != 0) return 2;
 	HIP_TRY(hipStreamSynchronize(stream), return 2);
 	if (L.chunked && L.prev_blocks && L.launched) progress->add(L.prev_blocks);
-	if (job.kernel_ms) HIP_TRY(hipEventElapsedTime(job.kernel_ms, s->ev0, s->ev1), return 2);
+	if (job.kernel_ms) HIP_TRY(hipEventElapsedTime(job.kernel_ms, job.generate ? s->ev_gen : s->ev0, s->ev1), return 2);
 	return 0;
 }
 
@@ -1489,6 +1520,7 @@ int backend_compress_set(Backend* b, const CompressSetJob& job)
 	std::vector<const void*> ptrs;
 	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_data); ptrs.push_back(job.entries[e].device_out); }
 	if (!set_on_one_device(s, ptrs.data(), ptrs.size())) return 3;
+	if (job.generate && job.generate->device_image != job.entries[0].device_data) return 3;
 	Progress progress;
 	progress.done = 0; progress.callback = job.progress; progress.total = 0;
 	for (uint32_t e = 0; e < job.count; e++)
@@ -1537,6 +1569,25 @@ int backend_decompress_set(Backend* bk, const DecompressSetJob& job)
 	if (urc != 0) return urc;
 	int lrc = astc_decode_set_launch(s->d_set, runs, stream);
 	if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
+	HIP_TRY(hipStreamSynchronize(stream), return 2);
+	return 0;
+}
+
+int backend_generate_mips(Backend* b, const MipChainJob& job)
+{
+	DeviceGuard guard;
+	int st = 0;
+	DeviceSlot* s = slot_for_pointer(b, job.device_image, &st);
+	if (!s) return st ? st : 2;
+	// (the device check of a set: the image and the levels buffer -- the one allocation every generated level lies in)
+	const void* ptrs[2] = { job.device_image, job.level_count > 1 ? job.device_levels : nullptr };
+	if (!set_on_one_device(s, ptrs, 2)) return 3;
+	std::lock_guard<std::mutex> busy(s->busy);
+	HIP_TRY(hipSetDevice(s->device), return 2);
+	hipStream_t stream;
+	if (!pick_stream(s, job.stream, &stream)) return 3;
+	const int grc = generate_mips_locked(s, stream, job);
+	if (grc != 0) return grc;
 	HIP_TRY(hipStreamSynchronize(stream), return 2);
 	return 0;
 }

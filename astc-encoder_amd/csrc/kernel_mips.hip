@@ -1,0 +1,279 @@
+// SPDX-License-Identifier: Apache-2.0
+// Mip chain generation (astcenc_amd_generate_mip_chain_device): every level made from the one above it with the filter of
+// mip_filter.h.  Memory-bound, so the launches are shaped by their traffic:
+//   - a large level is one launch; a lane makes 16 bytes of output (4 RGBA8, 2 F16 or 1 F32 texels) and stores them at once.
+//     When both source axes are even and a source row is a whole number of 32-byte pieces, the lane reads its 2 x 2 footprints
+//     with four 16-byte loads (astc_downsample_even); any other level takes the tap loop of the header (astc_downsample_level);
+//   - once a source level has at most MIP_TAIL_TEXELS texels, one workgroup makes every remaining level in one launch
+//     (astc_downsample_tail): each level lives in LDS, where the next one reads it, and is written out once.
+// Linear RGBA8 is integer arithmetic only; float64 is used for sRGB channels and float data, as the filter demands.
+#include "backend.h"
+#include "mip_filter.h"
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+
+namespace astcd {
+
+// the kinds of data a level holds: which arithmetic of mip_filter.h runs
+enum MipKind { MIP_U8 = 0, MIP_U8_SRGB = 1, MIP_F16 = 2, MIP_F32 = 3 };
+constexpr uint32_t MIP_TAIL_TEXELS = 4096;      // a source level this small: the rest of the chain in one workgroup
+constexpr uint32_t MIP_TAIL_DST_TEXELS = 2048;  // ... whose destinations have at most half as many texels (LDS buffer size)
+constexpr uint32_t MIP_TAIL_THREADS = 1024;
+constexpr uint32_t MIP_THREADS = 256;
+constexpr uint32_t MIP_MAX_GROUPS = 1u << 20;
+
+template <int K> struct MipTexel;                           // a texel as it is stored
+template <> struct MipTexel<MIP_U8> { typedef uint32_t T; };
+template <> struct MipTexel<MIP_U8_SRGB> { typedef uint32_t T; };
+template <> struct MipTexel<MIP_F16> { typedef uint2 T; };
+template <> struct MipTexel<MIP_F32> { typedef float4 T; };
+
+/* Unit u of a level (units_x per row) -> its row and the unit within the row; 32-bit division while the index fits. */
+__device__ inline void mip_unit_xy(size_t u, uint32_t units_x, uint32_t& ux, size_t& y)
+{
+	if (u <= 0xFFFFFFFFull)
+	{
+		const uint32_t q = (uint32_t)u / units_x;
+		y = q; ux = (uint32_t)u - q * units_x;
+	}
+	else
+	{
+		y = u / units_x; ux = (uint32_t)(u - y * units_x);
+	}
+}
+
+/* The float channels of a stored texel, and back. */
+template <int K> __device__ inline void mip_unpack(const typename MipTexel<K>::T& t, float v[4]);
+template <> __device__ inline void mip_unpack<MIP_F16>(const uint2& t, float v[4])
+{
+	v[0] = mip_float_from_half((unsigned short)(t.x & 0xFFFFu)); v[1] = mip_float_from_half((unsigned short)(t.x >> 16));
+	v[2] = mip_float_from_half((unsigned short)(t.y & 0xFFFFu)); v[3] = mip_float_from_half((unsigned short)(t.y >> 16));
+}
+template <> __device__ inline void mip_unpack<MIP_F32>(const float4& t, float v[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+__device__ inline uint2 mip_pack_f16(const float v[4])
+{
+	return make_uint2((uint32_t)mip_half_from_float(v[0]) | ((uint32_t)mip_half_from_float(v[1]) << 16),
+	                  (uint32_t)mip_half_from_float(v[2]) | ((uint32_t)mip_half_from_float(v[3]) << 16));
+}
+
+/* A source texel from global memory with the loads the compressor uses on a caller's image (wave_load.h): one dword for RGBA8,
+ * component loads otherwise, so a source needs only the alignment of its components. */
+template <int K> __device__ inline typename MipTexel<K>::T mip_load_global(const void* src, size_t i);
+template <> __device__ inline uint32_t mip_load_global<MIP_U8>(const void* src, size_t i) { return static_cast<const uint32_t*>(src)[i]; }
+template <> __device__ inline uint32_t mip_load_global<MIP_U8_SRGB>(const void* src, size_t i) { return static_cast<const uint32_t*>(src)[i]; }
+template <> __device__ inline uint2 mip_load_global<MIP_F16>(const void* src, size_t i)
+{
+	const uint16_t* p = static_cast<const uint16_t*>(src) + 4 * i;
+	return make_uint2((uint32_t)p[0] | ((uint32_t)p[1] << 16), (uint32_t)p[2] | ((uint32_t)p[3] << 16));
+}
+template <> __device__ inline float4 mip_load_global<MIP_F32>(const void* src, size_t i)
+{
+	const float* p = static_cast<const float*>(src) + 4 * i;
+	return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+/* One destination texel with the taps (tx, ty), its source texels read by load(x, y) -> stored texel. */
+template <int K, typename Load>
+__device__ inline typename MipTexel<K>::T mip_texel(const MipTaps& tx, const MipTaps& ty, Load load, const double* srgb)
+{
+	if constexpr (K == MIP_U8 || K == MIP_U8_SRGB)
+	{
+		return mip_texel_u8(tx, ty, load, K == MIP_U8_SRGB ? srgb : nullptr, K == MIP_U8_SRGB ? srgb + 256 : nullptr);
+	}
+	else
+	{
+		float out[4];
+		mip_texel_float(tx, ty, [&](unsigned int x, unsigned int y, float v[4]) { mip_unpack<K>(load(x, y), v); }, out);
+		if constexpr (K == MIP_F16) return mip_pack_f16(out);
+		else return make_float4(out[0], out[1], out[2], out[3]);
+	}
+}
+
+/* Even source axes: a lane's 16 bytes of output from two source rows of 32 bytes each (four 16-byte loads).  Launched only when
+ * the source is 16-byte aligned and its row pitch a multiple of 32 bytes, so every load is aligned and units_x = sx_bytes / 32. */
+template <int K>
+__global__ void __launch_bounds__(MIP_THREADS)
+astc_downsample_even(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, size_t dst_pitch, uint32_t units_x,
+                     size_t units, const double* __restrict__ srgb)
+{
+	const size_t stride = (size_t)gridDim.x * MIP_THREADS;
+	for (size_t u = (size_t)blockIdx.x * MIP_THREADS + threadIdx.x; u < units; u += stride)
+	{
+		uint32_t ux; size_t y;
+		mip_unit_xy(u, units_x, ux, y);
+		const uint4* r0 = reinterpret_cast<const uint4*>(src + 2 * y * src_pitch + (size_t)ux * 32);
+		const uint4* r1 = reinterpret_cast<const uint4*>(src + (2 * y + 1) * src_pitch + (size_t)ux * 32);
+		const uint4 a0 = r0[0], a1 = r0[1], b0 = r1[0], b1 = r1[1];
+		uint4 out;
+		if constexpr (K == MIP_U8)
+		{
+			// four texels, each the rounded mean (s + 2) >> 2 of its 2 x 2 footprint: the channels in two 16-bit SIMD halves
+			const uint32_t ra[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+			const uint32_t rb[8] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w };
+			uint32_t o[4];
+			#pragma unroll
+			for (int k = 0; k < 4; k++)
+			{
+				const uint32_t p0 = ra[2 * k], p1 = ra[2 * k + 1], p2 = rb[2 * k], p3 = rb[2 * k + 1];
+				const uint32_t lo = (p0 & 0x00FF00FFu) + (p1 & 0x00FF00FFu) + (p2 & 0x00FF00FFu) + (p3 & 0x00FF00FFu) + 0x00020002u;
+				const uint32_t hi = ((p0 >> 8) & 0x00FF00FFu) + ((p1 >> 8) & 0x00FF00FFu) + ((p2 >> 8) & 0x00FF00FFu) + ((p3 >> 8) & 0x00FF00FFu) + 0x00020002u;
+				o[k] = ((lo >> 2) & 0x00FF00FFu) | (((hi >> 2) & 0x00FF00FFu) << 8);
+			}
+			out = make_uint4(o[0], o[1], o[2], o[3]);
+		}
+		else
+		{
+			// the tap loop of the header over the loaded texels (taps of an even axis, in the lane's own coordinates)
+			typedef typename MipTexel<K>::T T;
+			constexpr int PER = 32 / (int)sizeof(T);            // source texels per 32-byte row piece
+			T row0[PER], row1[PER];
+			__builtin_memcpy(&row0[0], &a0, 16); __builtin_memcpy(reinterpret_cast<uint8_t*>(row0) + 16, &a1, 16);
+			__builtin_memcpy(&row1[0], &b0, 16); __builtin_memcpy(reinterpret_cast<uint8_t*>(row1) + 16, &b1, 16);
+			T res[PER / 2];
+			#pragma unroll
+			for (int k = 0; k < PER / 2; k++)
+			{
+				const MipTaps t = mip_axis_taps(2, 0);
+				res[k] = mip_texel<K>(t, t, [&](unsigned int x, unsigned int yy) { return yy ? row1[2 * k + x] : row0[2 * k + x]; }, srgb);
+			}
+			__builtin_memcpy(&out, res, 16);
+		}
+		*reinterpret_cast<uint4*>(dst + y * dst_pitch + (size_t)ux * 16) = out;
+	}
+}
+
+/* Any level: a lane makes the 16 / sizeof(T) destination texels from x = ux * that on, through the tap loop of the header;
+ * one 16-byte store when they are all there and the address allows it, texel stores otherwise. */
+template <int K>
+__global__ void __launch_bounds__(MIP_THREADS)
+astc_downsample_level(const void* __restrict__ src, uint32_t sx, uint32_t sy, uint8_t* __restrict__ dst, uint32_t dx, uint32_t units_x,
+                      size_t units, const double* __restrict__ srgb)
+{
+	typedef typename MipTexel<K>::T T;
+	constexpr uint32_t TPL = 16 / (uint32_t)sizeof(T);
+	const size_t stride = (size_t)gridDim.x * MIP_THREADS;
+	for (size_t u = (size_t)blockIdx.x * MIP_THREADS + threadIdx.x; u < units; u += stride)
+	{
+		uint32_t ux; size_t y;
+		mip_unit_xy(u, units_x, ux, y);
+		const MipTaps ty = mip_axis_taps(sy, (uint32_t)y);
+		const uint32_t x0 = ux * TPL;
+		T res[TPL];
+		#pragma unroll
+		for (uint32_t k = 0; k < TPL; k++)
+		{
+			if (x0 + k >= dx) break;
+			const MipTaps tx = mip_axis_taps(sx, x0 + k);
+			res[k] = mip_texel<K>(tx, ty, [&](unsigned int x, unsigned int yy) { return mip_load_global<K>(src, (size_t)yy * sx + x); }, srgb);
+		}
+		const size_t at = y * dx + x0;
+		T* out = reinterpret_cast<T*>(dst) + at;
+		if (x0 + TPL <= dx && ((at * sizeof(T)) & 15u) == 0)
+		{
+			uint4 v;
+			__builtin_memcpy(&v, res, 16);
+			*reinterpret_cast<uint4*>(out) = v;
+		}
+		else
+		{
+			for (uint32_t k = 0; k < TPL && x0 + k < dx; k++) out[k] = res[k];
+		}
+	}
+}
+
+/* The rest of the chain in one workgroup: level k + 1 is made from level k (k = 0: `src` in global memory, then the LDS copy of
+ * the level before), kept in LDS for the next one and written to dst[k]. */
+struct MipTailArgs {
+	const void* src;
+	uint32_t sx, sy, levels;
+	uint8_t* dst[MIP_MAX_LEVELS];
+};
+
+template <int K>
+__global__ void __launch_bounds__(MIP_TAIL_THREADS)
+astc_downsample_tail(MipTailArgs a, const double* __restrict__ srgb)
+{
+	typedef typename MipTexel<K>::T T;
+	__shared__ T buf[2][MIP_TAIL_DST_TEXELS];
+	uint32_t sx = a.sx, sy = a.sy;
+	for (uint32_t k = 0; k < a.levels; k++)
+	{
+		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
+		T* out = buf[k & 1];
+		const T* in = buf[(k & 1) ^ 1];
+		T* g = reinterpret_cast<T*>(a.dst[k]);
+		for (uint32_t t = threadIdx.x; t < dx * dy; t += MIP_TAIL_THREADS)
+		{
+			const uint32_t y = t / dx, x = t - y * dx;
+			const MipTaps tx = mip_axis_taps(sx, x), ty = mip_axis_taps(sy, y);
+			T v;
+			if (k == 0)
+				v = mip_texel<K>(tx, ty, [&](unsigned int xx, unsigned int yy) { return mip_load_global<K>(a.src, (size_t)yy * sx + xx); }, srgb);
+			else
+				v = mip_texel<K>(tx, ty, [&](unsigned int xx, unsigned int yy) { return in[yy * sx + xx]; }, srgb);
+			out[t] = v;
+			g[t] = v;
+		}
+		__syncthreads();
+		sx = dx; sy = dy;
+	}
+}
+
+template <int K>
+static int mip_launch_kind(const MipLaunch& m)
+{
+	typedef typename MipTexel<K>::T T;
+	const hipStream_t stream = static_cast<hipStream_t>(m.stream);
+	const double* srgb = static_cast<const double*>(m.d_srgb);
+	uint32_t sx = m.dim_x, sy = m.dim_y;
+	for (uint32_t level = 1; level < m.levels; level++)
+	{
+		const void* src = m.level[level - 1];
+		if ((size_t)sx * sy <= MIP_TAIL_TEXELS)
+		{
+			MipTailArgs a;
+			memset(&a, 0, sizeof(a));
+			a.src = src; a.sx = sx; a.sy = sy; a.levels = m.levels - level;
+			for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = static_cast<uint8_t*>(m.level[level + k]);
+			hipLaunchKernelGGL(astc_downsample_tail<K>, dim3(1), dim3(MIP_TAIL_THREADS), 0, stream, a, srgb);
+			break;
+		}
+		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
+		uint8_t* dst = static_cast<uint8_t*>(m.level[level]);
+		const size_t src_pitch = (size_t)sx * sizeof(T);
+		const bool even = (sx & 1u) == 0 && (sy & 1u) == 0 && (src_pitch & 31u) == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+		const uint32_t units_x = even ? (uint32_t)(src_pitch / 32) : (uint32_t)((dx + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+		const size_t units = (size_t)units_x * dy;
+		size_t groups = (units + MIP_THREADS - 1) / MIP_THREADS;
+		if (groups > MIP_MAX_GROUPS) groups = MIP_MAX_GROUPS;
+		if (even)
+			hipLaunchKernelGGL(astc_downsample_even<K>, dim3((uint32_t)groups), dim3(MIP_THREADS), 0, stream,
+			                   static_cast<const uint8_t*>(src), src_pitch, dst, (size_t)dx * sizeof(T), units_x, units, srgb);
+		else
+			hipLaunchKernelGGL(astc_downsample_level<K>, dim3((uint32_t)groups), dim3(MIP_THREADS), 0, stream,
+			                   src, sx, sy, dst, dx, units_x, units, srgb);
+		sx = dx; sy = dy;
+	}
+	return (int)hipGetLastError();
+}
+
+int astc_mip_launch(const MipLaunch& m)
+{
+	if (m.levels < 2) return 0;
+	switch (m.data_type)
+	{
+	case 0: return m.d_srgb && m.srgb ? mip_launch_kind<MIP_U8_SRGB>(m) : mip_launch_kind<MIP_U8>(m);
+	case 1: return mip_launch_kind<MIP_F16>(m);
+	default: return mip_launch_kind<MIP_F32>(m);
+	}
+}
+
+size_t astc_mip_srgb_table_bytes() { return MIP_SRGB_TABLE_DOUBLES * sizeof(double); }
+
+void astc_mip_srgb_tables_build(void* out)
+{
+	mip_srgb_tables_build(static_cast<double*>(out), [](double x, double y) { return ::pow(x, y); });
+}
+
+} // namespace astcd

@@ -92,8 +92,17 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compare_images_device", "astcenc_amd_backend_name", "astcenc_amd_context_device_count",
                "astcenc_amd_context_set_option", "astcenc_amd_compare_images_hdr_device", "astcenc_amd_context_kernel_name",
                "astcenc_amd_set_log_callback", "astcenc_amd_context_specialize", "astcenc_amd_compress_images_device",
-               "astcenc_amd_decompress_images_device"]
+               "astcenc_amd_decompress_images_device", "astcenc_amd_mip_chain_layout", "astcenc_amd_generate_mip_chain_device",
+               "astcenc_amd_compress_mip_chain_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
+MAX_MIP_LEVELS = 32
+
+
+class MipChainLayout(C.Structure):
+    """struct astcenc_amd_mip_chain_layout (include/astcenc_amd.h)."""
+    _fields_ = [("level_count", C.c_uint), ("dim_x", C.c_uint * MAX_MIP_LEVELS), ("dim_y", C.c_uint * MAX_MIP_LEVELS),
+                ("texels_offset", C.c_size_t * MAX_MIP_LEVELS), ("blocks_offset", C.c_size_t * MAX_MIP_LEVELS),
+                ("texels_len", C.c_size_t), ("blocks_len", C.c_size_t)]
 
 
 class ImageSetEntry(C.Structure):
@@ -217,6 +226,16 @@ class Library:
             L.astcenc_amd_compress_images_device.restype = C.c_int
             L.astcenc_amd_decompress_images_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p]
             L.astcenc_amd_decompress_images_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_mip_chain_layout"):
+            L.astcenc_amd_mip_chain_layout.argtypes = [C.POINTER(Config), C.c_uint, C.c_uint, C.c_int, C.c_uint, C.POINTER(MipChainLayout)]
+            L.astcenc_amd_mip_chain_layout.restype = C.c_int
+            L.astcenc_amd_generate_mip_chain_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_void_p,
+                                                                C.c_size_t, C.c_void_p]
+            L.astcenc_amd_generate_mip_chain_device.restype = C.c_int
+            L.astcenc_amd_compress_mip_chain_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.POINTER(Swizzle),
+                                                                C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_mip_chain_device.restype = C.c_int
 
     # -- thin wrappers returning error codes, as the C API does --
     def config_init(self, profile, bx, by, bz, quality, flags):
@@ -315,6 +334,67 @@ class Library:
         arr, n, s = self._set_args(entries, stream)
         return self.lib.astcenc_amd_decompress_images_device(ctx, arr, n, s)
 
+    def mip_chain_layout(self, cfg, w, h, dtype, levels=0):
+        """astcenc_amd_mip_chain_layout for the footprint of `cfg` (a Config); dtype: TYPE_*.  Returns (error, MipChainLayout)."""
+        layout = MipChainLayout()
+        err = self.lib.astcenc_amd_mip_chain_layout(C.byref(cfg), w, h, dtype, levels, C.byref(layout))
+        return err, layout
+
+    def _mip_chain_buffers(self, ctx, image, levels, blocks):
+        """(w, h, dtype code, layout, device_levels tensor, level tensors [level 0 = image], blocks tensor or None) of a chain;
+        the context's config gives the footprint."""
+        import torch
+        types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
+        assert image.is_contiguous() and image.dim() == 3 and image.shape[-1] == 4, "a contiguous [H, W, 4] device tensor"
+        h, w = image.shape[0], image.shape[1]
+        cfg = Config()
+        cfg.block_x, cfg.block_y, cfg.block_z = self._ctx_block(ctx)
+        err, layout = self.mip_chain_layout(cfg, w, h, types[image.dtype], levels)
+        if err:
+            raise AstcError(err, "astcenc_amd_mip_chain_layout")
+        n = layout.level_count
+        store = torch.empty(max(layout.texels_len, 1), dtype=torch.uint8, device=image.device)
+        tensors = [image]
+        for i in range(1, n):
+            size = layout.dim_x[i] * layout.dim_y[i] * 4 * image.element_size()
+            tensors.append(store[layout.texels_offset[i]:layout.texels_offset[i] + size].view(image.dtype)
+                           .view(layout.dim_y[i], layout.dim_x[i], 4))
+        out = torch.empty(layout.blocks_len, dtype=torch.uint8, device=image.device) if blocks else None
+        return w, h, types[image.dtype], layout, store, tensors, out
+
+    def _ctx_block(self, ctx):
+        """The footprint of a context (astcenc_get_block_info on a zero block: it reports the context's block size)."""
+        info = BlockInfo()
+        self.lib.astcenc_get_block_info(ctx, (C.c_uint8 * 16)(), C.byref(info))
+        return info.block_x, info.block_y, info.block_z
+
+    def generate_mip_chain_device(self, ctx, image, levels=0, stream=None):
+        """Levels of the [H, W, 4] device tensor `image` (astcenc_amd_generate_mip_chain_device): a list of torch views, one per
+        level, level 0 being `image` itself and the others views of one buffer."""
+        w, h, dtype, layout, store, tensors, _ = self._mip_chain_buffers(ctx, image, levels, False)
+        s = torch_stream(stream)
+        err = self.lib.astcenc_amd_generate_mip_chain_device(ctx, image.data_ptr(), w, h, dtype, layout.level_count,
+                                                             store.data_ptr(), layout.texels_len, s)
+        if err:
+            raise AstcError(err, "astcenc_amd_generate_mip_chain_device")
+        return tensors
+
+    def compress_mip_chain_device(self, ctx, image, levels=0, swizzle=SWZ_RGBA, stream=None):
+        """astcenc_amd_compress_mip_chain_device: returns (level tensors, per-level block tensors); the kernel time of the call
+        (ms, generation included) in self.last_kernel_ms."""
+        w, h, dtype, layout, store, tensors, out = self._mip_chain_buffers(ctx, image, levels, True)
+        s = torch_stream(stream)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_mip_chain_device(ctx, image.data_ptr(), w, h, dtype, C.byref(Swizzle(*swizzle)),
+                                                             layout.level_count, store.data_ptr(), layout.texels_len,
+                                                             out.data_ptr(), layout.blocks_len, s, C.byref(ms))
+        self.last_kernel_ms = ms.value
+        if err:
+            raise AstcError(err, "astcenc_amd_compress_mip_chain_device")
+        n = layout.level_count
+        ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
+        return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+
     def decompress(self, data, width, height, block=(6, 6), profile=PRF_LDR, out_type=np.uint8, depth=None):
         """Decode blocks back to [H, W, 4] ([D, H, W, 4] when depth is given) through
         astcenc_decompress_image of whichever library this is."""
@@ -340,6 +420,14 @@ class Library:
             return out
         finally:
             self.context_free(ctx)
+
+
+def torch_stream(stream):
+    """A raw hipStream_t of a torch stream, a raw handle, or torch's current stream for None."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream()
+    return getattr(stream, "cuda_stream", stream)
 
 
 def synthetic_image(width, height, seed=0x9E3779B1):
@@ -519,3 +607,42 @@ def read_ktx(path):
         raise ValueError("truncated KTX file")
     block = (blk[0], blk[1], blk[2] if len(blk) > 2 else 1)
     return np.frombuffer(raw, dtype=np.uint8, count=n, offset=at + 4).copy(), w, h, d if d else 1, block, srgb
+
+
+def write_ktx_mips(path, level_blocks, width, height, block, srgb=False):
+    """Write the blocks of a mip chain (level_blocks[i]: level i, max(1, width >> i) x max(1, height >> i) texels) as one KTX 1.1
+    file: numberOfMipmapLevels = len(level_blocks), each level preceded by its imageSize (ASTC levels are whole 16-byte blocks,
+    so no mip padding)."""
+    import struct
+    if len(block) > 2 and block[2] > 1:
+        raise ValueError("mip chains are 2D: a 2D footprint")
+    header = KTX_MAGIC + struct.pack("<13I", 0x04030201, 0, 1, 0, ktx_gl_format(block, srgb), GL_RGBA,
+                                     width, height, 0, 0, 1, len(level_blocks), 0)
+    with open(path, "wb") as f:
+        f.write(header)
+        for blocks in level_blocks:
+            data = np.ascontiguousarray(blocks if isinstance(blocks, np.ndarray) else blocks.cpu().numpy(), dtype=np.uint8).tobytes()
+            f.write(struct.pack("<I", len(data)) + data)
+
+
+def read_ktx_mips(path):
+    """-> ([blocks uint8[] per level], width, height, (bx, by, bz), is_srgb) of a 2D KTX 1.1 file with any number of mip levels
+    (either byte order); the level sizes are checked against the footprint."""
+    import struct
+    raw = open(path, "rb").read()
+    _, w, h, d, block, srgb = read_ktx(path)
+    if d != 1:
+        raise ValueError("not a 2D KTX file")
+    e = "<" if struct.unpack_from("<I", raw, 12)[0] == 0x04030201 else ">"
+    mips, kv = struct.unpack_from(e + "2I", raw, 56)
+    at, levels = 64 + kv, []
+    for i in range(max(mips, 1)):
+        if len(raw) < at + 4:
+            raise ValueError("truncated KTX file")
+        n = struct.unpack_from(e + "I", raw, at)[0]
+        lw, lh = max(1, w >> i), max(1, h >> i)
+        if n != -(-lw // block[0]) * -(-lh // block[1]) * 16 or len(raw) < at + 4 + n:
+            raise ValueError("bad KTX mip level %d" % i)
+        levels.append(np.frombuffer(raw, dtype=np.uint8, count=n, offset=at + 4).copy())
+        at += 4 + n + (-n % 4)
+    return levels, w, h, block, srgb

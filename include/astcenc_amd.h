@@ -104,6 +104,85 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_images_device(
 	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
 	void* hip_stream);
 
+/* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
+ *
+ * Level i is max(1, dim_x >> i) x max(1, dim_y >> i) (the GL / Vulkan / KTX rule); level_count == 0 means the full chain down
+ * to 1 x 1, floor(log2(max(dim_x, dim_y))) + 1 levels, and a level_count above that is ASTCENC_ERR_BAD_PARAM.  Level 0 is the
+ * caller's image; levels 1 .. level_count - 1 are tightly packed RGBA rows of data_type in one caller buffer, each starting on a
+ * 256-byte boundary.  Compressed levels lie back to back in another buffer, 16 bytes per block in raster order (ready for a KTX
+ * file).
+ *
+ * The filter, exactly (a numpy model reproduces it bit for bit):
+ *   - every level is made from the one above it; along each axis a source of S texels makes D = max(1, S >> 1), destination
+ *     texel j taking: S == 1: source texel 0, weight 1, denominator 1; S even: texels 2j, 2j+1, weights (1, 1), denominator 2;
+ *     S = 2n+1 > 1: texels 2j, 2j+1, 2j+2, weights (n-j, n, j+1), denominator 2n+1 (the exact area each covers).  A texel's
+ *     weight is the product of its two axis weights, its denominator den = den_x * den_y;
+ *   - U8, linear: sum(w * v) / den as an exact rational, rounded to nearest, ties up;
+ *   - U8 in an ASTCENC_PRF_LDR_SRGB context, channels 0-2: codes decoded with the sRGB EOTF (float64, on the host), averaged in
+ *     float64 as below, encoded as the number of codes c in 1..255 with mean >= EOTF((c - 0.5) / 255).  Channel 3 is linear;
+ *     U8 in every other profile is linear;
+ *   - F16 / F32: per y tap in increasing row, row = sum over the x taps (increasing x) of w_x * v, acc = sum over the y taps of
+ *     w_y * row (each sum starting at its first product), all float64; then acc / den in float64, rounded to float32, then
+ *     to F16 for F16 levels (round to nearest even both times);
+ *   - channels are independent (no premultiplication, no renormalisation); the swizzle does not touch the levels, it applies
+ *     when they are compressed. */
+#define ASTCENC_AMD_MAX_MIP_LEVELS 32
+
+struct astcenc_amd_mip_chain_layout {
+	unsigned int level_count;                          /* the levels of the chain (level_count resolved) */
+	unsigned int dim_x[ASTCENC_AMD_MAX_MIP_LEVELS], dim_y[ASTCENC_AMD_MAX_MIP_LEVELS];
+	size_t texels_offset[ASTCENC_AMD_MAX_MIP_LEVELS];  /* byte offset of level i >= 1 in device_levels; [0] = 0 (level 0 is the caller's image) */
+	size_t blocks_offset[ASTCENC_AMD_MAX_MIP_LEVELS];  /* byte offset of level i's blocks in device_blocks, levels back to back */
+	size_t texels_len;                                 /* bytes device_levels must hold (levels 1 .. level_count-1; 0 for one level) */
+	size_t blocks_len;                                 /* bytes device_blocks must hold (all levels) */
+};
+
+/* The layout of a chain for the footprint of `config` (a 3D footprint makes one layer of blocks per 2D level).  Pure host
+ * arithmetic, no device and no context: usable before any allocation.  A null config or layout, a zero dimension or an unknown
+ * data_type: ASTCENC_ERR_BAD_PARAM. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_mip_chain_layout(
+	const struct astcenc_config* config,
+	unsigned int dim_x, unsigned int dim_y,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	struct astcenc_amd_mip_chain_layout* layout);
+
+/* Levels 1 .. level_count - 1 of the 2D device image into device_levels (levels_len bytes, at least the layout's texels_len;
+ * may be null when the chain has one level).  Runs on the device that owns device_image and returns once the work on
+ * hip_stream (NULL = the context's own stream) has completed.  Everything is checked before anything is launched, and an error
+ * writes nothing: a null context, a bad dimension, type or level_count: ASTCENC_ERR_BAD_PARAM; a null device_image or
+ * device_levels: ASTCENC_ERR_BAD_CONTEXT (as astcenc_amd_compress_image_device returns for a null buffer); levels_len too
+ * short: ASTCENC_ERR_OUT_OF_MEM; a buffer or stream of another device: ASTCENC_ERR_BAD_PARAM.  The log callback
+ * (astcenc_amd_set_log_callback) names the argument.  device_image needs the alignment of its components (4 bytes for U8
+ * texels); device_levels must not overlap it (not checked). */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_generate_mip_chain_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	void* device_levels, size_t levels_len,
+	void* hip_stream);
+
+/* The same generation, then every level (level 0 = device_image) compressed into device_blocks (blocks_len bytes, at least the
+ * layout's blocks_len) in the same chain of launches: an image set of one entry per level (astcenc_amd_compress_images_device),
+ * so every level's blocks are exactly what astcenc_amd_compress_image_device writes for that level's texels, and the set's
+ * rules hold -- its entry checks (before anything is launched, generation included), the alpha-scale pre-pass per level,
+ * cancel, the progress callback over the whole chain's blocks.  kernel_ms covers every launch of the call, generation
+ * included.  A null device_blocks: ASTCENC_ERR_BAD_CONTEXT; blocks_len too short: ASTCENC_ERR_OUT_OF_MEM; otherwise the
+ * errors of generation.  The buffers must not overlap (not checked). */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	unsigned int level_count,
+	void* device_levels, size_t levels_len,
+	void* device_blocks, size_t blocks_len,
+	void* hip_stream,
+	float* kernel_ms);
+
 /* Error sums of two device-resident images of the same size, the quantities the reference CLI's quality
  * report is made of (ref: compute_error_metrics, Source/astcenccli_error_metrics.cpp:110-300):
  *   PSNR (LDR-RGBA)     = 10 log10(4 texels / (squared_error[0] + .. + [3]))
