@@ -190,7 +190,8 @@ static astcenc_error check_mip_args(const char* fn, astcenc_context* ctx, const 
 	}
 	memset(&gen, 0, sizeof(gen));
 	gen.device_image = device_image;
-	gen.dim_x = dim_x; gen.dim_y = dim_y; gen.data_type = (uint32_t)data_type; gen.level_count = layout.level_count;
+	gen.dim_x = dim_x; gen.dim_y = dim_y; gen.dim_z = 1; gen.kind = ASTCENC_AMD_MIP_ARRAY;
+	gen.data_type = (uint32_t)data_type; gen.level_count = layout.level_count;
 	gen.srgb = ctx->config.profile == ASTCENC_PRF_LDR_SRGB ? 1u : 0u;
 	gen.device_levels = static_cast<uint8_t*>(device_levels);
 	for (unsigned int i = 0; i < layout.level_count; i++) gen.texels_offset[i] = layout.texels_offset[i];
@@ -240,6 +241,146 @@ astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const 
 		e.blocks = static_cast<uint8_t*>(device_blocks) + layout.blocks_offset[i];
 		e.blocks_len = (i + 1 < layout.level_count ? layout.blocks_offset[i + 1] : layout.blocks_len) - layout.blocks_offset[i];
 		e.dim_x = layout.dim_x[i]; e.dim_y = layout.dim_y[i]; e.dim_z = 1;
+		e.data_type = data_type;
+		e.swizzle = *swizzle;
+	}
+	status = compress_set(ctx, entries.data(), layout.level_count, hip_stream, kernel_ms, layout.level_count > 1 ? &gen : nullptr);
+	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream on another device than device_image, or more than 2^32 - 1 blocks", fn);
+	return status;
+}
+
+/* Mip chains of arrays and volumes: the 2D chain's checks with a third dimension (include/astcenc_amd.h). */
+astcenc_error astcenc_amd_mip_chain_volume_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+                                                  astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
+                                                  struct astcenc_amd_mip_chain_volume_layout* layout)
+{
+	if (!config || !layout) return ASTCENC_ERR_BAD_PARAM;
+	memset(layout, 0, sizeof(*layout));
+	if (dim_x == 0 || dim_y == 0 || dim_z == 0 || config->block_x == 0 || config->block_y == 0 || config->block_z == 0) return ASTCENC_ERR_BAD_PARAM;
+	if ((int)data_type < ASTCENC_TYPE_U8 || (int)data_type > ASTCENC_TYPE_F32) return ASTCENC_ERR_BAD_PARAM;
+	if (kind != ASTCENC_AMD_MIP_ARRAY && kind != ASTCENC_AMD_MIP_VOLUME) return ASTCENC_ERR_BAD_PARAM;
+	// (an array's blocks must not span layers)
+	if (kind == ASTCENC_AMD_MIP_ARRAY && config->block_z > 1) return ASTCENC_ERR_BAD_PARAM;
+	const bool volume = kind == ASTCENC_AMD_MIP_VOLUME;
+	const unsigned int full = volume ? mip_full_levels_3d(dim_x, dim_y, dim_z) : mip_full_levels(dim_x, dim_y);
+	if (level_count > full) return ASTCENC_ERR_BAD_PARAM;
+	const unsigned int n = level_count == 0 ? full : level_count;
+	const size_t texel_bytes = data_type == ASTCENC_TYPE_U8 ? 4 : data_type == ASTCENC_TYPE_F16 ? 8 : 16;
+	size_t texels = 0, blocks = 0;
+	bool overflow = false;
+	for (unsigned int i = 0; i < n; i++)
+	{
+		const unsigned int dx = mip_level_dim(dim_x, i), dy = mip_level_dim(dim_y, i), dz = volume ? mip_level_dim(dim_z, i) : dim_z;
+		layout->dim_x[i] = dx;
+		layout->dim_y[i] = dy;
+		layout->dim_z[i] = dz;
+		layout->blocks_offset[i] = blocks;
+		const size_t level_blocks = mul_safe(mul_safe(block_count_axis(dx, config->block_x), block_count_axis(dy, config->block_y), overflow),
+		                                     block_count_axis(dz, config->block_z), overflow);
+		const size_t level_block_bytes = mul_safe(level_blocks, 16, overflow);
+		overflow = overflow || blocks + level_block_bytes < blocks;
+		blocks += level_block_bytes;
+		// (level 0 is the caller's: its bytes must exist, but it takes no room in device_levels)
+		const size_t level_bytes = mul_safe(mul_safe(mul_safe(dx, dy, overflow), dz, overflow), texel_bytes, overflow);
+		if (i == 0) continue;
+		const size_t at = (texels + MIP_LEVEL_ALIGN - 1) & ~(size_t)(MIP_LEVEL_ALIGN - 1);
+		overflow = overflow || at < texels || at + level_bytes < at;
+		layout->texels_offset[i] = at;
+		texels = at + level_bytes;
+	}
+	if (overflow)
+	{
+		memset(layout, 0, sizeof(*layout));
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	layout->level_count = n;
+	layout->texels_len = texels;
+	layout->blocks_len = blocks;
+	return ASTCENC_SUCCESS;
+}
+
+static astcenc_error check_mip_volume_args(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
+                                           void* device_levels, size_t levels_len, void* hip_stream,
+                                           struct astcenc_amd_mip_chain_volume_layout& layout, MipChainJob& gen)
+{
+	astcenc_error status = astcenc_amd_mip_chain_volume_layout(&ctx->config, dim_x, dim_y, dim_z, kind, data_type, level_count, &layout);
+	if (status != ASTCENC_SUCCESS)
+	{
+		const char* why = "bad image";
+		if (kind != ASTCENC_AMD_MIP_ARRAY && kind != ASTCENC_AMD_MIP_VOLUME) why = "kind is neither ASTCENC_AMD_MIP_ARRAY nor ASTCENC_AMD_MIP_VOLUME";
+		else if (kind == ASTCENC_AMD_MIP_ARRAY && ctx->config.block_z > 1) why = "kind ASTCENC_AMD_MIP_ARRAY with a 3D footprint";
+		else if (dim_x && dim_y && dim_z &&
+		         level_count > (kind == ASTCENC_AMD_MIP_VOLUME ? mip_full_levels_3d(dim_x, dim_y, dim_z) : mip_full_levels(dim_x, dim_y)))
+			why = "level_count exceeds the full chain";
+		else if (dim_x && dim_y && dim_z && (int)data_type >= ASTCENC_TYPE_U8 && (int)data_type <= ASTCENC_TYPE_F32)
+			why = "the chain's bytes overflow size_t";
+		backend_log("%s: dim_x %u, dim_y %u, dim_z %u, kind %d, data_type %d, level_count %u: %s", fn, dim_x, dim_y, dim_z, (int)kind,
+		            (int)data_type, level_count, why);
+		return status;
+	}
+	if (!device_image) { backend_log("%s: device_image is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
+	if (layout.level_count > 1 && !device_levels) { backend_log("%s: device_levels is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
+	if (levels_len < layout.texels_len)
+	{
+		backend_log("%s: levels_len %zu, the chain needs %zu", fn, levels_len, layout.texels_len);
+		return ASTCENC_ERR_OUT_OF_MEM;
+	}
+	memset(&gen, 0, sizeof(gen));
+	gen.device_image = device_image;
+	gen.dim_x = dim_x; gen.dim_y = dim_y; gen.dim_z = dim_z; gen.kind = (uint32_t)kind;
+	gen.data_type = (uint32_t)data_type; gen.level_count = layout.level_count;
+	gen.srgb = ctx->config.profile == ASTCENC_PRF_LDR_SRGB ? 1u : 0u;
+	gen.device_levels = static_cast<uint8_t*>(device_levels);
+	for (unsigned int i = 0; i < layout.level_count; i++) gen.texels_offset[i] = layout.texels_offset[i];
+	gen.stream = hip_stream;
+	return ASTCENC_SUCCESS;
+}
+
+astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                                           unsigned int level_count, void* device_levels, size_t levels_len, void* hip_stream)
+{
+	static const char* fn = "astcenc_amd_generate_mip_chain_volume_device";
+	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
+	struct astcenc_amd_mip_chain_volume_layout layout;
+	MipChainJob gen;
+	astcenc_error status = check_mip_volume_args(fn, ctx, device_image, dim_x, dim_y, dim_z, kind, data_type, level_count, device_levels, levels_len,
+	                                             hip_stream, layout, gen);
+	if (status != ASTCENC_SUCCESS) return status;
+	if (layout.level_count == 1) return ASTCENC_SUCCESS;
+	status = rc_to_error(backend_generate_mips(ctx->backend, gen));
+	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: device_levels or hip_stream is not on the device of device_image", fn);
+	return status;
+}
+
+astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                                           const astcenc_swizzle* swizzle, unsigned int level_count, void* device_levels,
+                                                           size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
+                                                           float* kernel_ms)
+{
+	static const char* fn = "astcenc_amd_compress_mip_chain_volume_device";
+	if (!ctx || !swizzle) return ASTCENC_ERR_BAD_PARAM;
+	struct astcenc_amd_mip_chain_volume_layout layout;
+	MipChainJob gen;
+	astcenc_error status = check_mip_volume_args(fn, ctx, device_image, dim_x, dim_y, dim_z, kind, data_type, level_count, device_levels, levels_len,
+	                                             hip_stream, layout, gen);
+	if (status != ASTCENC_SUCCESS) return status;
+	if (!device_blocks) { backend_log("%s: device_blocks is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
+	if (blocks_len < layout.blocks_len)
+	{
+		backend_log("%s: blocks_len %zu, the chain needs %zu", fn, blocks_len, layout.blocks_len);
+		return ASTCENC_ERR_OUT_OF_MEM;
+	}
+	std::vector<astcenc_amd_image_set_entry> entries(layout.level_count);
+	for (unsigned int i = 0; i < layout.level_count; i++)
+	{
+		astcenc_amd_image_set_entry& e = entries[i];
+		e.image = i == 0 ? const_cast<void*>(device_image) : static_cast<uint8_t*>(device_levels) + layout.texels_offset[i];
+		e.blocks = static_cast<uint8_t*>(device_blocks) + layout.blocks_offset[i];
+		e.blocks_len = (i + 1 < layout.level_count ? layout.blocks_offset[i + 1] : layout.blocks_len) - layout.blocks_offset[i];
+		e.dim_x = layout.dim_x[i]; e.dim_y = layout.dim_y[i]; e.dim_z = layout.dim_z[i];
 		e.data_type = data_type;
 		e.swizzle = *swizzle;
 	}

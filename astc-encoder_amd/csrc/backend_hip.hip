@@ -1424,6 +1424,7 @@ static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChai
 	m.level[0] = const_cast<void*>(job.device_image);
 	for (uint32_t i = 1; i < job.level_count; i++) m.level[i] = job.device_levels + job.texels_offset[i];
 	m.dim_x = job.dim_x; m.dim_y = job.dim_y; m.data_type = job.data_type; m.levels = job.level_count;
+	m.dim_z = job.dim_z; m.kind = job.kind;
 	m.srgb = job.srgb; m.d_srgb = s->d_srgb;
 	m.stream = stream;
 	const int lrc = astc_mip_launch(m);

@@ -6,6 +6,11 @@
 //     with four 16-byte loads (astc_downsample_even); any other level takes the tap loop of the header (astc_downsample_level);
 //   - once a source level has at most MIP_TAIL_TEXELS texels, one workgroup makes every remaining level in one launch
 //     (astc_downsample_tail): each level lives in LDS, where the next one reads it, and is written out once.
+// Texture arrays and cube maps (ASTCENC_AMD_MIP_ARRAY) run the same launches over all layers: a layer's rows follow the
+// previous layer's, so the even path is unchanged, the tap loop finds the layer from its row, and the tail runs one
+// workgroup per layer.  A 2D image is the array of one layer.  Volumes (ASTCENC_AMD_MIP_VOLUME) whose source level has more
+// than one slice take the 3D kernels astc_mip3d_even / _level / _tail, the same shapes with a z axis; a level whose source
+// depth is 1 takes the 2D kernels, which the 3D filter then equals.
 // Linear RGBA8 is integer arithmetic only; float64 is used for sRGB channels and float data, as the filter demands.
 #include "backend.h"
 #include "mip_filter.h"
@@ -74,6 +79,20 @@ template <> __device__ inline float4 mip_load_global<MIP_F32>(const void* src, s
 }
 
 /* One destination texel with the taps (tx, ty), its source texels read by load(x, y) -> stored texel. */
+/* Row r of a layered level (rows_per_layer rows per layer) -> its layer and its row within the layer. */
+__device__ inline void mip_row_layer(size_t r, uint32_t rows_per_layer, size_t& layer, uint32_t& y)
+{
+	if (r <= 0xFFFFFFFFull)
+	{
+		const uint32_t q = (uint32_t)r / rows_per_layer;
+		layer = q; y = (uint32_t)r - q * rows_per_layer;
+	}
+	else
+	{
+		layer = r / rows_per_layer; y = (uint32_t)(r - layer * rows_per_layer);
+	}
+}
+
 template <int K, typename Load>
 __device__ inline typename MipTexel<K>::T mip_texel(const MipTaps& tx, const MipTaps& ty, Load load, const double* srgb)
 {
@@ -85,6 +104,23 @@ __device__ inline typename MipTexel<K>::T mip_texel(const MipTaps& tx, const Mip
 	{
 		float out[4];
 		mip_texel_float(tx, ty, [&](unsigned int x, unsigned int y, float v[4]) { mip_unpack<K>(load(x, y), v); }, out);
+		if constexpr (K == MIP_F16) return mip_pack_f16(out);
+		else return make_float4(out[0], out[1], out[2], out[3]);
+	}
+}
+
+/* ... and in a volume: load(x, y, z). */
+template <int K, typename Load>
+__device__ inline typename MipTexel<K>::T mip_texel_3d(const MipTaps& tx, const MipTaps& ty, const MipTaps& tz, Load load, const double* srgb)
+{
+	if constexpr (K == MIP_U8 || K == MIP_U8_SRGB)
+	{
+		return mip_texel_u8_3d(tx, ty, tz, load, K == MIP_U8_SRGB ? srgb : nullptr, K == MIP_U8_SRGB ? srgb + 256 : nullptr);
+	}
+	else
+	{
+		float out[4];
+		mip_texel_float_3d(tx, ty, tz, [&](unsigned int x, unsigned int y, unsigned int z, float v[4]) { mip_unpack<K>(load(x, y, z), v); }, out);
 		if constexpr (K == MIP_F16) return mip_pack_f16(out);
 		else return make_float4(out[0], out[1], out[2], out[3]);
 	}
@@ -144,20 +180,24 @@ astc_downsample_even(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t*
 }
 
 /* Any level: a lane makes the 16 / sizeof(T) destination texels from x = ux * that on, through the tap loop of the header;
- * one 16-byte store when they are all there and the address allows it, texel stores otherwise. */
+ * one 16-byte store when they are all there and the address allows it, texel stores otherwise.  The rows of all layers in
+ * one range: row r is row r mod dy of layer r / dy. */
 template <int K>
 __global__ void __launch_bounds__(MIP_THREADS)
-astc_downsample_level(const void* __restrict__ src, uint32_t sx, uint32_t sy, uint8_t* __restrict__ dst, uint32_t dx, uint32_t units_x,
-                      size_t units, const double* __restrict__ srgb)
+astc_downsample_level(const void* __restrict__ src, uint32_t sx, uint32_t sy, uint8_t* __restrict__ dst, uint32_t dx, uint32_t dy,
+                      uint32_t units_x, size_t units, const double* __restrict__ srgb)
 {
 	typedef typename MipTexel<K>::T T;
 	constexpr uint32_t TPL = 16 / (uint32_t)sizeof(T);
 	const size_t stride = (size_t)gridDim.x * MIP_THREADS;
 	for (size_t u = (size_t)blockIdx.x * MIP_THREADS + threadIdx.x; u < units; u += stride)
 	{
-		uint32_t ux; size_t y;
-		mip_unit_xy(u, units_x, ux, y);
-		const MipTaps ty = mip_axis_taps(sy, (uint32_t)y);
+		uint32_t ux; size_t r;
+		mip_unit_xy(u, units_x, ux, r);
+		size_t layer; uint32_t y;
+		mip_row_layer(r, dy, layer, y);
+		const size_t base = layer * sx * sy;
+		const MipTaps ty = mip_axis_taps(sy, y);
 		const uint32_t x0 = ux * TPL;
 		T res[TPL];
 		#pragma unroll
@@ -165,9 +205,9 @@ astc_downsample_level(const void* __restrict__ src, uint32_t sx, uint32_t sy, ui
 		{
 			if (x0 + k >= dx) break;
 			const MipTaps tx = mip_axis_taps(sx, x0 + k);
-			res[k] = mip_texel<K>(tx, ty, [&](unsigned int x, unsigned int yy) { return mip_load_global<K>(src, (size_t)yy * sx + x); }, srgb);
+			res[k] = mip_texel<K>(tx, ty, [&](unsigned int x, unsigned int yy) { return mip_load_global<K>(src, base + (size_t)yy * sx + x); }, srgb);
 		}
-		const size_t at = y * dx + x0;
+		const size_t at = r * dx + x0;
 		T* out = reinterpret_cast<T*>(dst) + at;
 		if (x0 + TPL <= dx && ((at * sizeof(T)) & 15u) == 0)
 		{
@@ -182,8 +222,9 @@ astc_downsample_level(const void* __restrict__ src, uint32_t sx, uint32_t sy, ui
 	}
 }
 
-/* The rest of the chain in one workgroup: level k + 1 is made from level k (k = 0: `src` in global memory, then the LDS copy of
- * the level before), kept in LDS for the next one and written to dst[k]. */
+/* The rest of the chain in one workgroup per layer: level k + 1 is made from level k (k = 0: `src` in global memory, then the
+ * LDS copy of the level before), kept in LDS for the next one and written to dst[k].  Layer l's levels follow the l levels
+ * of the layers before it; a workgroup takes layers blockIdx.x, + gridDim.x, ... */
 struct MipTailArgs {
 	const void* src;
 	uint32_t sx, sy, levels;
@@ -192,31 +233,184 @@ struct MipTailArgs {
 
 template <int K>
 __global__ void __launch_bounds__(MIP_TAIL_THREADS)
-astc_downsample_tail(MipTailArgs a, const double* __restrict__ srgb)
+astc_downsample_tail(MipTailArgs a, uint32_t layers, const double* __restrict__ srgb)
 {
 	typedef typename MipTexel<K>::T T;
 	__shared__ T buf[2][MIP_TAIL_DST_TEXELS];
-	uint32_t sx = a.sx, sy = a.sy;
+	for (uint32_t layer = blockIdx.x; layer < layers; layer += gridDim.x)
+	{
+		uint32_t sx = a.sx, sy = a.sy;
+		const T* src = reinterpret_cast<const T*>(a.src) + (size_t)layer * sx * sy;
+		for (uint32_t k = 0; k < a.levels; k++)
+		{
+			const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
+			T* out = buf[k & 1];
+			const T* in = buf[(k & 1) ^ 1];
+			T* g = reinterpret_cast<T*>(a.dst[k]) + (size_t)layer * dx * dy;
+			for (uint32_t t = threadIdx.x; t < dx * dy; t += MIP_TAIL_THREADS)
+			{
+				const uint32_t y = t / dx, x = t - y * dx;
+				const MipTaps tx = mip_axis_taps(sx, x), ty = mip_axis_taps(sy, y);
+				T v;
+				if (k == 0)
+					v = mip_texel<K>(tx, ty, [&](unsigned int xx, unsigned int yy) { return mip_load_global<K>(src, (size_t)yy * sx + xx); }, srgb);
+				else
+					v = mip_texel<K>(tx, ty, [&](unsigned int xx, unsigned int yy) { return in[yy * sx + xx]; }, srgb);
+				out[t] = v;
+				g[t] = v;
+			}
+			__syncthreads();
+			sx = dx; sy = dy;
+		}
+	}
+}
+
+/* Volumes, all three source axes even: a lane's 16 bytes of output from two slices x two rows of 32 bytes each (eight 16-byte
+ * loads).  As astc_downsample_even: launched only when the source is 16-byte aligned and its row pitch a multiple of 32 bytes.
+ * The destination rows of all slices in one range: row r is row r mod dy of slice r / dy. */
+template <int K>
+__global__ void __launch_bounds__(MIP_THREADS)
+astc_mip3d_even(const uint8_t* __restrict__ src, size_t src_pitch, uint32_t sy, uint8_t* __restrict__ dst, size_t dst_pitch, uint32_t dy,
+                uint32_t units_x, size_t units, const double* __restrict__ srgb)
+{
+	const size_t stride = (size_t)gridDim.x * MIP_THREADS;
+	const size_t slice_pitch = (size_t)sy * src_pitch;
+	for (size_t u = (size_t)blockIdx.x * MIP_THREADS + threadIdx.x; u < units; u += stride)
+	{
+		uint32_t ux; size_t r;
+		mip_unit_xy(u, units_x, ux, r);
+		size_t z; uint32_t y;
+		mip_row_layer(r, dy, z, y);
+		const uint8_t* p = src + 2 * z * slice_pitch + (size_t)(2 * y) * src_pitch + (size_t)ux * 32;
+		const uint4* r00 = reinterpret_cast<const uint4*>(p);
+		const uint4* r01 = reinterpret_cast<const uint4*>(p + src_pitch);
+		const uint4* r10 = reinterpret_cast<const uint4*>(p + slice_pitch);
+		const uint4* r11 = reinterpret_cast<const uint4*>(p + slice_pitch + src_pitch);
+		const uint4 a0 = r00[0], a1 = r00[1], b0 = r01[0], b1 = r01[1], c0 = r10[0], c1 = r10[1], d0 = r11[0], d1 = r11[1];
+		uint4 out;
+		if constexpr (K == MIP_U8)
+		{
+			// four texels, each the rounded mean (s + 4) >> 3 of its 2 x 2 x 2 footprint: the channels in two 16-bit SIMD
+			// halves (8 * 255 + 4 fits in 16 bits)
+			const uint32_t ra[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+			const uint32_t rb[8] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w };
+			const uint32_t rc[8] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
+			const uint32_t rd[8] = { d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w };
+			uint32_t o[4];
+			#pragma unroll
+			for (int k = 0; k < 4; k++)
+			{
+				const uint32_t q[8] = { ra[2 * k], ra[2 * k + 1], rb[2 * k], rb[2 * k + 1], rc[2 * k], rc[2 * k + 1], rd[2 * k], rd[2 * k + 1] };
+				uint32_t lo = 0x00040004u, hi = 0x00040004u;
+				#pragma unroll
+				for (int i = 0; i < 8; i++)
+				{
+					lo += q[i] & 0x00FF00FFu;
+					hi += (q[i] >> 8) & 0x00FF00FFu;
+				}
+				o[k] = ((lo >> 3) & 0x00FF00FFu) | (((hi >> 3) & 0x00FF00FFu) << 8);
+			}
+			out = make_uint4(o[0], o[1], o[2], o[3]);
+		}
+		else
+		{
+			typedef typename MipTexel<K>::T T;
+			constexpr int PER = 32 / (int)sizeof(T);
+			T row[4][PER];                                       // [slice * 2 + row]
+			__builtin_memcpy(&row[0][0], &a0, 16); __builtin_memcpy(reinterpret_cast<uint8_t*>(row[0]) + 16, &a1, 16);
+			__builtin_memcpy(&row[1][0], &b0, 16); __builtin_memcpy(reinterpret_cast<uint8_t*>(row[1]) + 16, &b1, 16);
+			__builtin_memcpy(&row[2][0], &c0, 16); __builtin_memcpy(reinterpret_cast<uint8_t*>(row[2]) + 16, &c1, 16);
+			__builtin_memcpy(&row[3][0], &d0, 16); __builtin_memcpy(reinterpret_cast<uint8_t*>(row[3]) + 16, &d1, 16);
+			T res[PER / 2];
+			#pragma unroll
+			for (int k = 0; k < PER / 2; k++)
+			{
+				const MipTaps t = mip_axis_taps(2, 0);
+				res[k] = mip_texel_3d<K>(t, t, t, [&](unsigned int x, unsigned int yy, unsigned int zz) { return row[zz * 2 + yy][2 * k + x]; }, srgb);
+			}
+			__builtin_memcpy(&out, res, 16);
+		}
+		*reinterpret_cast<uint4*>(dst + r * dst_pitch + (size_t)ux * 16) = out;
+	}
+}
+
+/* Volumes, any shape: astc_downsample_level with a z axis (3 x 3 x 3 taps at most). */
+template <int K>
+__global__ void __launch_bounds__(MIP_THREADS)
+astc_mip3d_level(const void* __restrict__ src, uint32_t sx, uint32_t sy, uint32_t sz, uint8_t* __restrict__ dst, uint32_t dx, uint32_t dy,
+                 uint32_t units_x, size_t units, const double* __restrict__ srgb)
+{
+	typedef typename MipTexel<K>::T T;
+	constexpr uint32_t TPL = 16 / (uint32_t)sizeof(T);
+	const size_t stride = (size_t)gridDim.x * MIP_THREADS;
+	for (size_t u = (size_t)blockIdx.x * MIP_THREADS + threadIdx.x; u < units; u += stride)
+	{
+		uint32_t ux; size_t r;
+		mip_unit_xy(u, units_x, ux, r);
+		size_t z; uint32_t y;
+		mip_row_layer(r, dy, z, y);
+		const MipTaps ty = mip_axis_taps(sy, y), tz = mip_axis_taps(sz, (uint32_t)z);
+		const uint32_t x0 = ux * TPL;
+		T res[TPL];
+		#pragma unroll
+		for (uint32_t k = 0; k < TPL; k++)
+		{
+			if (x0 + k >= dx) break;
+			const MipTaps tx = mip_axis_taps(sx, x0 + k);
+			res[k] = mip_texel_3d<K>(tx, ty, tz, [&](unsigned int x, unsigned int yy, unsigned int zz) {
+				return mip_load_global<K>(src, ((size_t)zz * sy + yy) * sx + x); }, srgb);
+		}
+		const size_t at = r * dx + x0;
+		T* out = reinterpret_cast<T*>(dst) + at;
+		if (x0 + TPL <= dx && ((at * sizeof(T)) & 15u) == 0)
+		{
+			uint4 v;
+			__builtin_memcpy(&v, res, 16);
+			*reinterpret_cast<uint4*>(out) = v;
+		}
+		else
+		{
+			for (uint32_t k = 0; k < TPL && x0 + k < dx; k++) out[k] = res[k];
+		}
+	}
+}
+
+/* Volumes: the rest of the chain in one workgroup once a source level has at most MIP_TAIL_TEXELS texels (a destination has
+ * at most half its source's texels, so the 2D tail's buffers hold every level). */
+struct Mip3dTailArgs {
+	const void* src;
+	uint32_t sx, sy, sz, levels;
+	uint8_t* dst[MIP_MAX_LEVELS];
+};
+
+template <int K>
+__global__ void __launch_bounds__(MIP_TAIL_THREADS)
+astc_mip3d_tail(Mip3dTailArgs a, const double* __restrict__ srgb)
+{
+	typedef typename MipTexel<K>::T T;
+	__shared__ T buf[2][MIP_TAIL_DST_TEXELS];
+	uint32_t sx = a.sx, sy = a.sy, sz = a.sz;
 	for (uint32_t k = 0; k < a.levels; k++)
 	{
-		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
+		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u, dz = sz > 1 ? sz >> 1 : 1u;
 		T* out = buf[k & 1];
 		const T* in = buf[(k & 1) ^ 1];
 		T* g = reinterpret_cast<T*>(a.dst[k]);
-		for (uint32_t t = threadIdx.x; t < dx * dy; t += MIP_TAIL_THREADS)
+		for (uint32_t t = threadIdx.x; t < dx * dy * dz; t += MIP_TAIL_THREADS)
 		{
-			const uint32_t y = t / dx, x = t - y * dx;
-			const MipTaps tx = mip_axis_taps(sx, x), ty = mip_axis_taps(sy, y);
+			const uint32_t zy = t / dx, x = t - zy * dx, z = zy / dy, y = zy - z * dy;
+			const MipTaps tx = mip_axis_taps(sx, x), ty = mip_axis_taps(sy, y), tz = mip_axis_taps(sz, z);
 			T v;
 			if (k == 0)
-				v = mip_texel<K>(tx, ty, [&](unsigned int xx, unsigned int yy) { return mip_load_global<K>(a.src, (size_t)yy * sx + xx); }, srgb);
+				v = mip_texel_3d<K>(tx, ty, tz, [&](unsigned int xx, unsigned int yy, unsigned int zz) {
+					return mip_load_global<K>(a.src, ((size_t)zz * sy + yy) * sx + xx); }, srgb);
 			else
-				v = mip_texel<K>(tx, ty, [&](unsigned int xx, unsigned int yy) { return in[yy * sx + xx]; }, srgb);
+				v = mip_texel_3d<K>(tx, ty, tz, [&](unsigned int xx, unsigned int yy, unsigned int zz) { return in[(zz * sy + yy) * sx + xx]; }, srgb);
 			out[t] = v;
 			g[t] = v;
 		}
 		__syncthreads();
-		sx = dx; sy = dy;
+		sx = dx; sy = dy; sz = dz;
 	}
 }
 
@@ -226,25 +420,57 @@ static int mip_launch_kind(const MipLaunch& m)
 	typedef typename MipTexel<K>::T T;
 	const hipStream_t stream = static_cast<hipStream_t>(m.stream);
 	const double* srgb = static_cast<const double*>(m.d_srgb);
-	uint32_t sx = m.dim_x, sy = m.dim_y;
+	const bool volume = m.kind == 1;
+	uint32_t sx = m.dim_x, sy = m.dim_y, sz = m.dim_z ? m.dim_z : 1u;
 	for (uint32_t level = 1; level < m.levels; level++)
 	{
 		const void* src = m.level[level - 1];
+		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
+		uint8_t* dst = static_cast<uint8_t*>(m.level[level]);
+		const size_t src_pitch = (size_t)sx * sizeof(T);
+		const bool aligned = (src_pitch & 31u) == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+		if (volume && sz > 1)
+		{
+			const uint32_t dz = sz >> 1;
+			if ((size_t)sx * sy * sz <= MIP_TAIL_TEXELS)
+			{
+				Mip3dTailArgs a;
+				memset(&a, 0, sizeof(a));
+				a.src = src; a.sx = sx; a.sy = sy; a.sz = sz; a.levels = m.levels - level;
+				for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = static_cast<uint8_t*>(m.level[level + k]);
+				hipLaunchKernelGGL(astc_mip3d_tail<K>, dim3(1), dim3(MIP_TAIL_THREADS), 0, stream, a, srgb);
+				break;
+			}
+			const bool even = (sx & 1u) == 0 && (sy & 1u) == 0 && (sz & 1u) == 0 && aligned;
+			const uint32_t units_x = even ? (uint32_t)(src_pitch / 32) : (uint32_t)((dx + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+			const size_t units = (size_t)units_x * dy * dz;
+			size_t groups = (units + MIP_THREADS - 1) / MIP_THREADS;
+			if (groups > MIP_MAX_GROUPS) groups = MIP_MAX_GROUPS;
+			if (even)
+				hipLaunchKernelGGL(astc_mip3d_even<K>, dim3((uint32_t)groups), dim3(MIP_THREADS), 0, stream,
+				                   static_cast<const uint8_t*>(src), src_pitch, sy, dst, (size_t)dx * sizeof(T), dy, units_x, units, srgb);
+			else
+				hipLaunchKernelGGL(astc_mip3d_level<K>, dim3((uint32_t)groups), dim3(MIP_THREADS), 0, stream,
+				                   src, sx, sy, sz, dst, dx, dy, units_x, units, srgb);
+			sx = dx; sy = dy; sz = dz;
+			continue;
+		}
+		// 2D layers: the layers of an array, or one (a 2D image, a volume level of depth 1)
+		const uint32_t layers = volume ? 1u : sz;
 		if ((size_t)sx * sy <= MIP_TAIL_TEXELS)
 		{
 			MipTailArgs a;
 			memset(&a, 0, sizeof(a));
 			a.src = src; a.sx = sx; a.sy = sy; a.levels = m.levels - level;
 			for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = static_cast<uint8_t*>(m.level[level + k]);
-			hipLaunchKernelGGL(astc_downsample_tail<K>, dim3(1), dim3(MIP_TAIL_THREADS), 0, stream, a, srgb);
+			const uint32_t groups = layers < MIP_MAX_GROUPS ? layers : MIP_MAX_GROUPS;
+			hipLaunchKernelGGL(astc_downsample_tail<K>, dim3(groups), dim3(MIP_TAIL_THREADS), 0, stream, a, layers, srgb);
 			break;
 		}
-		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
-		uint8_t* dst = static_cast<uint8_t*>(m.level[level]);
-		const size_t src_pitch = (size_t)sx * sizeof(T);
-		const bool even = (sx & 1u) == 0 && (sy & 1u) == 0 && (src_pitch & 31u) == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+		// (even sizes: a layer is an even number of rows, so the rows of all layers pair up as those of one tall image)
+		const bool even = (sx & 1u) == 0 && (sy & 1u) == 0 && aligned;
 		const uint32_t units_x = even ? (uint32_t)(src_pitch / 32) : (uint32_t)((dx + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
-		const size_t units = (size_t)units_x * dy;
+		const size_t units = (size_t)units_x * dy * layers;
 		size_t groups = (units + MIP_THREADS - 1) / MIP_THREADS;
 		if (groups > MIP_MAX_GROUPS) groups = MIP_MAX_GROUPS;
 		if (even)
@@ -252,7 +478,7 @@ static int mip_launch_kind(const MipLaunch& m)
 			                   static_cast<const uint8_t*>(src), src_pitch, dst, (size_t)dx * sizeof(T), units_x, units, srgb);
 		else
 			hipLaunchKernelGGL(astc_downsample_level<K>, dim3((uint32_t)groups), dim3(MIP_THREADS), 0, stream,
-			                   src, sx, sy, dst, dx, units_x, units, srgb);
+			                   src, sx, sy, dst, dx, dy, units_x, units, srgb);
 		sx = dx; sy = dy;
 	}
 	return (int)hipGetLastError();

@@ -3,6 +3,8 @@
 // texel along one axis, the per-texel arithmetic of every data type, and the chain's level dimensions.  Everything here is
 // exactly reproducible -- integer arithmetic for linear U8, float64 in a fixed order for sRGB and float data, explicit
 // round-to-nearest-even conversions -- so that a numpy model (tests/mip_model.py) matches it bit for bit.
+// The chains of volumes (astcenc_amd_generate_mip_chain_volume_device) add a z axis with the same taps: mip_texel_u8_3d and
+// mip_texel_float_3d below (numpy model: tests/mip_model_3d.py).  A volume of depth 1 gives exactly the 2D arithmetic.
 //
 // No includes and no HIP types: kernel_mips.hip builds its kernels on these functions and tests/test_mip_chain_cpu.py
 // compiles the header with g++.
@@ -27,6 +29,12 @@ ASTC_MIP_FN unsigned int mip_full_levels(unsigned int dim_x, unsigned int dim_y)
 	unsigned int m = dim_x > dim_y ? dim_x : dim_y, n = 1;
 	while (m > 1) { m >>= 1; n++; }
 	return n;
+}
+
+/* ... of a dim_x x dim_y x dim_z volume (every axis halves): floor(log2(max(dim_x, dim_y, dim_z))) + 1. */
+ASTC_MIP_FN unsigned int mip_full_levels_3d(unsigned int dim_x, unsigned int dim_y, unsigned int dim_z)
+{
+	return mip_full_levels(dim_x > dim_y ? dim_x : dim_y, dim_z);
 }
 
 /* A level's size along one axis: max(1, dim >> level). */
@@ -212,6 +220,112 @@ ASTC_MIP_FN unsigned int mip_texel_u8(const MipTaps& tx, const MipTaps& ty, Load
 	{
 		const double dden = (double)tx.den * (double)ty.den;
 		for (int c = 0; c < 3; c++) out |= mip_srgb_encode(acc[c] / dden, thr) << (8 * c);
+	}
+	else
+		for (int c = 0; c < 3; c++) out |= mip_round_mean(sum[c], den) << (8 * c);
+	return out;
+}
+
+/* One destination texel of float data in a volume: for each z tap in increasing slice, the 2D acc of that slice exactly as
+ * mip_texel_float computes it (before its division), then vol = w_z0 * acc0 + w_z1 * acc1 (+ ...) in float64 (starting at its
+ * first product), then vol / ((den_x * den_y) * den_z) in float64, rounded to float32.  load(x, y, z, float v[4]).  With one z
+ * tap (a source of depth 1: weight 1, denominator 1) every step is exact and the result is mip_texel_float's. */
+template <typename Load>
+ASTC_MIP_FN void mip_texel_float_3d(const MipTaps& tx, const MipTaps& ty, const MipTaps& tz, Load load, float out[4])
+{
+	double vol[4] = { 0.0, 0.0, 0.0, 0.0 };
+	ASTC_MIP_UNROLL
+	for (unsigned int kz = 0; kz < 3; kz++)
+	{
+		if (kz >= tz.count) break;
+		double acc[4] = { 0.0, 0.0, 0.0, 0.0 };
+		ASTC_MIP_UNROLL
+		for (unsigned int ky = 0; ky < 3; ky++)
+		{
+			if (ky >= ty.count) break;
+			double row[4] = { 0.0, 0.0, 0.0, 0.0 };
+			ASTC_MIP_UNROLL
+			for (unsigned int kx = 0; kx < 3; kx++)
+			{
+				if (kx >= tx.count) break;
+				float v[4];
+				load(tx.first + kx, ty.first + ky, tz.first + kz, v);
+				for (int c = 0; c < 4; c++)
+				{
+					const double p = (double)tx.w[kx] * (double)v[c];
+					row[c] = kx == 0 ? p : row[c] + p;
+				}
+			}
+			for (int c = 0; c < 4; c++)
+			{
+				const double q = (double)ty.w[ky] * row[c];
+				acc[c] = ky == 0 ? q : acc[c] + q;
+			}
+		}
+		for (int c = 0; c < 4; c++)
+		{
+			const double r = (double)tz.w[kz] * acc[c];
+			vol[c] = kz == 0 ? r : vol[c] + r;
+		}
+	}
+	const double den = ((double)tx.den * (double)ty.den) * (double)tz.den;
+	for (int c = 0; c < 4; c++) out[c] = (float)(vol[c] / den);
+}
+
+/* One destination texel of RGBA8 data in a volume, load(x, y, z) -> packed texel.  Linear channels: weight w_x * w_y * w_z,
+ * denominator den_x * den_y * den_z (at most the source level's texel count), the exact rational mean rounded to nearest,
+ * ties up.  sRGB channels 0-2 (lin != null): the decoded values averaged as mip_texel_float_3d averages, encoded with
+ * mip_srgb_encode(thr); channel 3 linear. */
+template <typename Load>
+ASTC_MIP_FN unsigned int mip_texel_u8_3d(const MipTaps& tx, const MipTaps& ty, const MipTaps& tz, Load load, const double* lin,
+                                         const double* thr)
+{
+	unsigned long long sum[4] = { 0, 0, 0, 0 };
+	double vol[3] = { 0.0, 0.0, 0.0 };
+	ASTC_MIP_UNROLL
+	for (unsigned int kz = 0; kz < 3; kz++)
+	{
+		if (kz >= tz.count) break;
+		double acc[3] = { 0.0, 0.0, 0.0 };
+		ASTC_MIP_UNROLL
+		for (unsigned int ky = 0; ky < 3; ky++)
+		{
+			if (ky >= ty.count) break;
+			double row[3] = { 0.0, 0.0, 0.0 };
+			ASTC_MIP_UNROLL
+			for (unsigned int kx = 0; kx < 3; kx++)
+			{
+				if (kx >= tx.count) break;
+				const unsigned int p = load(tx.first + kx, ty.first + ky, tz.first + kz);
+				const unsigned long long w = (unsigned long long)tx.w[kx] * ty.w[ky] * tz.w[kz];
+				for (int c = 0; c < 4; c++) sum[c] += w * ((p >> (8 * c)) & 0xFFu);
+				if (lin)
+					for (int c = 0; c < 3; c++)
+					{
+						const double v = (double)tx.w[kx] * lin[(p >> (8 * c)) & 0xFFu];
+						row[c] = kx == 0 ? v : row[c] + v;
+					}
+			}
+			if (lin)
+				for (int c = 0; c < 3; c++)
+				{
+					const double q = (double)ty.w[ky] * row[c];
+					acc[c] = ky == 0 ? q : acc[c] + q;
+				}
+		}
+		if (lin)
+			for (int c = 0; c < 3; c++)
+			{
+				const double r = (double)tz.w[kz] * acc[c];
+				vol[c] = kz == 0 ? r : vol[c] + r;
+			}
+	}
+	const unsigned long long den = (unsigned long long)tx.den * ty.den * tz.den;
+	unsigned int out = mip_round_mean(sum[3], den) << 24;
+	if (lin)
+	{
+		const double dden = ((double)tx.den * (double)ty.den) * (double)tz.den;
+		for (int c = 0; c < 3; c++) out |= mip_srgb_encode(vol[c] / dden, thr) << (8 * c);
 	}
 	else
 		for (int c = 0; c < 3; c++) out |= mip_round_mean(sum[c], den) << (8 * c);

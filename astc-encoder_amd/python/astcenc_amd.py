@@ -93,9 +93,11 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_context_set_option", "astcenc_amd_compare_images_hdr_device", "astcenc_amd_context_kernel_name",
                "astcenc_amd_set_log_callback", "astcenc_amd_context_specialize", "astcenc_amd_compress_images_device",
                "astcenc_amd_decompress_images_device", "astcenc_amd_mip_chain_layout", "astcenc_amd_generate_mip_chain_device",
-               "astcenc_amd_compress_mip_chain_device"]
+               "astcenc_amd_compress_mip_chain_device", "astcenc_amd_mip_chain_volume_layout",
+               "astcenc_amd_generate_mip_chain_volume_device", "astcenc_amd_compress_mip_chain_volume_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
+MIP_ARRAY, MIP_VOLUME = 0, 1
 
 
 class MipChainLayout(C.Structure):
@@ -103,6 +105,13 @@ class MipChainLayout(C.Structure):
     _fields_ = [("level_count", C.c_uint), ("dim_x", C.c_uint * MAX_MIP_LEVELS), ("dim_y", C.c_uint * MAX_MIP_LEVELS),
                 ("texels_offset", C.c_size_t * MAX_MIP_LEVELS), ("blocks_offset", C.c_size_t * MAX_MIP_LEVELS),
                 ("texels_len", C.c_size_t), ("blocks_len", C.c_size_t)]
+
+
+class MipChainVolumeLayout(C.Structure):
+    """struct astcenc_amd_mip_chain_volume_layout (include/astcenc_amd.h)."""
+    _fields_ = [("level_count", C.c_uint), ("dim_x", C.c_uint * MAX_MIP_LEVELS), ("dim_y", C.c_uint * MAX_MIP_LEVELS),
+                ("dim_z", C.c_uint * MAX_MIP_LEVELS), ("texels_offset", C.c_size_t * MAX_MIP_LEVELS),
+                ("blocks_offset", C.c_size_t * MAX_MIP_LEVELS), ("texels_len", C.c_size_t), ("blocks_len", C.c_size_t)]
 
 
 class ImageSetEntry(C.Structure):
@@ -236,6 +245,17 @@ class Library:
                                                                 C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                                                 C.POINTER(C.c_float)]
             L.astcenc_amd_compress_mip_chain_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_mip_chain_volume_layout"):
+            L.astcenc_amd_mip_chain_volume_layout.argtypes = [C.POINTER(Config), C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_uint,
+                                                              C.POINTER(MipChainVolumeLayout)]
+            L.astcenc_amd_mip_chain_volume_layout.restype = C.c_int
+            L.astcenc_amd_generate_mip_chain_volume_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                                       C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.astcenc_amd_generate_mip_chain_volume_device.restype = C.c_int
+            L.astcenc_amd_compress_mip_chain_volume_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                                       C.POINTER(Swizzle), C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                       C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_mip_chain_volume_device.restype = C.c_int
 
     # -- thin wrappers returning error codes, as the C API does --
     def config_init(self, profile, bx, by, bz, quality, flags):
@@ -391,6 +411,57 @@ class Library:
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_compress_mip_chain_device")
+        n = layout.level_count
+        ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
+        return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+
+    def mip_chain_volume_layout(self, cfg, w, h, d, kind, dtype, levels=0):
+        """astcenc_amd_mip_chain_volume_layout; kind: MIP_ARRAY / MIP_VOLUME.  Returns (error, MipChainVolumeLayout)."""
+        layout = MipChainVolumeLayout()
+        err = self.lib.astcenc_amd_mip_chain_volume_layout(C.byref(cfg), w, h, d, kind, dtype, levels, C.byref(layout))
+        return err, layout
+
+    def _mip_chain_volume_buffers(self, ctx, image, kind, levels, blocks):
+        """As _mip_chain_buffers for a [Z, H, W, 4] device tensor (Z: layers or depth): level tensors are [Z_i, H_i, W_i, 4]."""
+        import torch
+        types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
+        assert image.is_contiguous() and image.dim() == 4 and image.shape[-1] == 4, "a contiguous [Z, H, W, 4] device tensor"
+        d, h, w = image.shape[0], image.shape[1], image.shape[2]
+        cfg = Config()
+        cfg.block_x, cfg.block_y, cfg.block_z = self._ctx_block(ctx)
+        err, layout = self.mip_chain_volume_layout(cfg, w, h, d, kind, types[image.dtype], levels)
+        if err:
+            raise AstcError(err, "astcenc_amd_mip_chain_volume_layout")
+        store = torch.empty(max(layout.texels_len, 1), dtype=torch.uint8, device=image.device)
+        tensors = [image]
+        for i in range(1, layout.level_count):
+            size = layout.dim_x[i] * layout.dim_y[i] * layout.dim_z[i] * 4 * image.element_size()
+            tensors.append(store[layout.texels_offset[i]:layout.texels_offset[i] + size].view(image.dtype)
+                           .view(layout.dim_z[i], layout.dim_y[i], layout.dim_x[i], 4))
+        out = torch.empty(layout.blocks_len, dtype=torch.uint8, device=image.device) if blocks else None
+        return (w, h, d), types[image.dtype], layout, store, tensors, out
+
+    def generate_mip_chain_volume_device(self, ctx, image, kind=MIP_VOLUME, levels=0, stream=None):
+        """Levels of the [Z, H, W, 4] device tensor `image` (astcenc_amd_generate_mip_chain_volume_device): a list of [Z_i, H_i,
+        W_i, 4] torch views, level 0 being `image` itself."""
+        (w, h, d), dtype, layout, store, tensors, _ = self._mip_chain_volume_buffers(ctx, image, kind, levels, False)
+        err = self.lib.astcenc_amd_generate_mip_chain_volume_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
+                                                                    store.data_ptr(), layout.texels_len, torch_stream(stream))
+        if err:
+            raise AstcError(err, "astcenc_amd_generate_mip_chain_volume_device")
+        return tensors
+
+    def compress_mip_chain_volume_device(self, ctx, image, kind=MIP_VOLUME, levels=0, swizzle=SWZ_RGBA, stream=None):
+        """astcenc_amd_compress_mip_chain_volume_device: returns (level tensors, per-level block tensors); the kernel time of
+        the call (ms, generation included) in self.last_kernel_ms."""
+        (w, h, d), dtype, layout, store, tensors, out = self._mip_chain_volume_buffers(ctx, image, kind, levels, True)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_mip_chain_volume_device(ctx, image.data_ptr(), w, h, d, kind, dtype, C.byref(Swizzle(*swizzle)),
+                                                                    layout.level_count, store.data_ptr(), layout.texels_len,
+                                                                    out.data_ptr(), layout.blocks_len, torch_stream(stream), C.byref(ms))
+        self.last_kernel_ms = ms.value
+        if err:
+            raise AstcError(err, "astcenc_amd_compress_mip_chain_volume_device")
         n = layout.level_count
         ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
         return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
@@ -646,3 +717,63 @@ def read_ktx_mips(path):
         levels.append(np.frombuffer(raw, dtype=np.uint8, count=n, offset=at + 4).copy())
         at += 4 + n + (-n % 4)
     return levels, w, h, block, srgb
+
+
+def _ktx_chain_level_bytes(w, h, depth, layers, faces, block, i):
+    """Bytes of level i of a KTX chain: every array element, face and z slice of it (a 3D footprint: its block layers)."""
+    bz = block[2] if len(block) > 2 else 1
+    lw, lh, ld = max(1, w >> i), max(1, h >> i), max(1, depth >> i)
+    return -(-lw // block[0]) * -(-lh // block[1]) * -(-ld // bz) * 16 * max(layers, 1) * faces
+
+
+def write_ktx_chain(path, level_blocks, w, h, block, depth=1, layers=0, faces=1, srgb=False):
+    """Write the blocks of a mip chain of an array, a cube map (faces=6), a cube-map array or a volume (depth > 1, a 3D
+    footprint) as one KTX 1.1 file.  level_blocks[i] holds level i in KTX order: array elements, then faces, then z slices --
+    the order of the layers of an ASTCENC_AMD_MIP_ARRAY chain (a cube map's layers face-major within each element).
+    imageSize is the whole level, except for a cube map that is not an array, where it is one face.  ASTC data is whole
+    16-byte blocks, so there is no cube or mip padding."""
+    import struct
+    bz = block[2] if len(block) > 2 else 1
+    if faces not in (1, 6):
+        raise ValueError("faces must be 1 or 6")
+    if depth > 1 and bz <= 1:
+        raise ValueError("a volume needs a 3D footprint: KTX has no 2D-ASTC volume format")
+    if faces == 6 and (w != h or depth > 1):
+        raise ValueError("cube map faces must be square and 2D")
+    if depth > 1 and layers:
+        raise ValueError("arrays of volumes are not supported")
+    header = KTX_MAGIC + struct.pack("<13I", 0x04030201, 0, 1, 0, ktx_gl_format(block, srgb), GL_RGBA,
+                                     w, h, 0 if depth <= 1 else depth, layers, faces, len(level_blocks), 0)
+    with open(path, "wb") as f:
+        f.write(header)
+        for i, blocks in enumerate(level_blocks):
+            data = np.ascontiguousarray(blocks if isinstance(blocks, np.ndarray) else blocks.cpu().numpy(), dtype=np.uint8).tobytes()
+            if len(data) != _ktx_chain_level_bytes(w, h, depth, layers, faces, block, i):
+                raise ValueError("level %d holds %d bytes, its size is %d" % (i, len(data), _ktx_chain_level_bytes(w, h, depth, layers, faces, block, i)))
+            cube = faces == 6 and layers == 0
+            f.write(struct.pack("<I", len(data) // 6 if cube else len(data)) + data)
+
+
+def read_ktx_chain(path):
+    """-> {"levels": [blocks uint8[] per level, KTX order], "w", "h", "depth", "layers", "faces", "block": (bx, by, bz), "srgb"}
+    of a KTX 1.1 file with any number of mip levels, array elements and faces (either byte order); every imageSize is checked
+    against the level's size."""
+    import struct
+    raw = open(path, "rb").read()
+    _, w, h, depth, block, srgb = read_ktx(path)
+    e = "<" if struct.unpack_from("<I", raw, 12)[0] == 0x04030201 else ">"
+    layers, faces, mips, kv = struct.unpack_from(e + "4I", raw, 48)
+    if faces not in (1, 6):
+        raise ValueError("bad KTX face count")
+    at, levels = 64 + kv, []
+    cube = faces == 6 and layers == 0
+    for i in range(max(mips, 1)):
+        size = _ktx_chain_level_bytes(w, h, depth, layers, faces, block, i)
+        if len(raw) < at + 4:
+            raise ValueError("truncated KTX file")
+        n = struct.unpack_from(e + "I", raw, at)[0]
+        if n != (size // 6 if cube else size) or len(raw) < at + 4 + size:
+            raise ValueError("bad KTX mip level %d" % i)
+        levels.append(np.frombuffer(raw, dtype=np.uint8, count=size, offset=at + 4).copy())
+        at += 4 + size
+    return {"levels": levels, "w": w, "h": h, "depth": depth, "layers": layers, "faces": faces, "block": block, "srgb": srgb}

@@ -183,6 +183,78 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_device(
 	void* hip_stream,
 	float* kernel_ms);
 
+/* Mip chains of texture arrays, cube maps and volumes: the 2D chain above with a third dimension.
+ *
+ *   - ASTCENC_AMD_MIP_ARRAY: dim_z independent 2D layers (array layers; a cube map is an array of 6 * n layers, face-major
+ *     within each array element, the KTX order).  x and y halve, the layer count stays; the full chain is counted from x and y
+ *     alone.  Layer l of level i is byte for byte what astcenc_amd_generate_mip_chain_device makes from layer l alone (faces
+ *     are filtered independently: no seamless cube filtering).  A 3D footprint (block_z > 1) is ASTCENC_ERR_BAD_PARAM: its
+ *     blocks would mix layers.
+ *   - ASTCENC_AMD_MIP_VOLUME: one 3D image.  Level i is max(1, d >> i) on all three axes; the full chain has
+ *     floor(log2(max(dim_x, dim_y, dim_z))) + 1 levels.  The filter gains a z axis with the taps of x and y: linear U8 texels
+ *     weigh w_x * w_y * w_z over den_x * den_y * den_z (the exact rational mean, ties up); sRGB channels and F16 / F32 data
+ *     take, per z tap in increasing slice, the 2D acc of that slice exactly as above, sum w_z * acc in float64 (starting at
+ *     its first product) and divide by ((den_x * den_y) * den_z) in float64, then round as in 2D.  A volume of depth 1 makes
+ *     exactly the 2D chain.
+ *
+ * A level is dim_z[i] slices back to back of tightly packed RGBA rows (the layout of astcenc_amd_compress_volume_device and of
+ * a set entry).  Level i's blocks are exactly what astcenc_amd_compress_volume_device writes for its texels: one layer of
+ * blocks per slice for a 2D footprint, ceil(dim_z[i] / block_z) layers for a 3D one.  Everything else -- level_count, the
+ * 256-byte aligned texel offsets, the argument checks and their error codes, logging, stream order, cancel, progress and
+ * kernel_ms -- is the 2D chain's.  A chain whose texel or block bytes overflow size_t is ASTCENC_ERR_BAD_PARAM, and so is a
+ * compressed chain of more than 2^32 - 1 blocks in all (the image set's limit). */
+enum astcenc_amd_mip_kind {
+	ASTCENC_AMD_MIP_ARRAY = 0,
+	ASTCENC_AMD_MIP_VOLUME = 1
+};
+
+struct astcenc_amd_mip_chain_volume_layout {
+	unsigned int level_count;
+	unsigned int dim_x[ASTCENC_AMD_MAX_MIP_LEVELS], dim_y[ASTCENC_AMD_MAX_MIP_LEVELS];
+	unsigned int dim_z[ASTCENC_AMD_MAX_MIP_LEVELS];    /* layers (ARRAY) or depth (VOLUME) of level i */
+	size_t texels_offset[ASTCENC_AMD_MAX_MIP_LEVELS];  /* byte offset of level i >= 1 in device_levels, 256-byte aligned; [0] = 0 */
+	size_t blocks_offset[ASTCENC_AMD_MAX_MIP_LEVELS];  /* byte offset of level i's blocks in device_blocks, levels back to back */
+	size_t texels_len;
+	size_t blocks_len;
+};
+
+/* Host arithmetic, as astcenc_amd_mip_chain_layout; also ASTCENC_ERR_BAD_PARAM for an unknown kind, dim_z == 0, an ARRAY with
+ * a 3D footprint, or a byte count beyond size_t.  A VOLUME with dim_z == 1 has the 2D layout. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_mip_chain_volume_layout(
+	const struct astcenc_config* config,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	struct astcenc_amd_mip_chain_volume_layout* layout);
+
+/* Levels 1 .. level_count - 1 of device_image (dim_z slices) into device_levels: astcenc_amd_generate_mip_chain_device's
+ * contract with the layout above. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_generate_mip_chain_volume_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	void* device_levels, size_t levels_len,
+	void* hip_stream);
+
+/* The same generation, then every level compressed in the same chain of launches (an image set of one entry per level):
+ * astcenc_amd_compress_mip_chain_device's contract with the layout above. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_volume_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	unsigned int level_count,
+	void* device_levels, size_t levels_len,
+	void* device_blocks, size_t blocks_len,
+	void* hip_stream,
+	float* kernel_ms);
+
 /* Error sums of two device-resident images of the same size, the quantities the reference CLI's quality
  * report is made of (ref: compute_error_metrics, Source/astcenccli_error_metrics.cpp:110-300):
  *   PSNR (LDR-RGBA)     = 10 log10(4 texels / (squared_error[0] + .. + [3]))
