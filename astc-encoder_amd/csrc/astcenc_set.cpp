@@ -136,120 +136,9 @@ astcenc_error astcenc_amd_decompress_images_device(astcenc_context* ctx, const a
 	return rc_to_error(backend_decompress_set(ctx->backend, set));
 }
 
-/* Mip chains (include/astcenc_amd.h): the layout is host arithmetic; generation and compression check everything first. */
-astcenc_error astcenc_amd_mip_chain_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, astcenc_type data_type,
-                                           unsigned int level_count, struct astcenc_amd_mip_chain_layout* layout)
-{
-	if (!config || !layout) return ASTCENC_ERR_BAD_PARAM;
-	memset(layout, 0, sizeof(*layout));
-	if (dim_x == 0 || dim_y == 0 || config->block_x == 0 || config->block_y == 0 || config->block_z == 0) return ASTCENC_ERR_BAD_PARAM;
-	if ((int)data_type < ASTCENC_TYPE_U8 || (int)data_type > ASTCENC_TYPE_F32) return ASTCENC_ERR_BAD_PARAM;
-	const unsigned int full = mip_full_levels(dim_x, dim_y);
-	if (level_count > full) return ASTCENC_ERR_BAD_PARAM;
-	const unsigned int n = level_count == 0 ? full : level_count;
-	const size_t texel_bytes = data_type == ASTCENC_TYPE_U8 ? 4 : data_type == ASTCENC_TYPE_F16 ? 8 : 16;
-	size_t texels = 0, blocks = 0;
-	for (unsigned int i = 0; i < n; i++)
-	{
-		const unsigned int dx = mip_level_dim(dim_x, i), dy = mip_level_dim(dim_y, i);
-		layout->dim_x[i] = dx;
-		layout->dim_y[i] = dy;
-		layout->blocks_offset[i] = blocks;
-		// (a 2D level is one layer of blocks whatever the footprint's depth)
-		blocks += block_count_axis(dx, config->block_x) * block_count_axis(dy, config->block_y) * 16;
-		if (i == 0) continue;
-		texels = (texels + MIP_LEVEL_ALIGN - 1) & ~(size_t)(MIP_LEVEL_ALIGN - 1);
-		layout->texels_offset[i] = texels;
-		texels += (size_t)dx * dy * texel_bytes;
-	}
-	layout->level_count = n;
-	layout->texels_len = texels;
-	layout->blocks_len = blocks;
-	return ASTCENC_SUCCESS;
-}
-
-/* The checks shared by generation and compression; fills `gen` and `layout`. */
-static astcenc_error check_mip_args(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
-                                    astcenc_type data_type, unsigned int level_count, void* device_levels, size_t levels_len,
-                                    void* hip_stream, struct astcenc_amd_mip_chain_layout& layout, MipChainJob& gen)
-{
-	astcenc_error status = astcenc_amd_mip_chain_layout(&ctx->config, dim_x, dim_y, data_type, level_count, &layout);
-	if (status != ASTCENC_SUCCESS)
-	{
-		backend_log("%s: dim_x %u, dim_y %u, data_type %d, level_count %u: %s", fn, dim_x, dim_y, (int)data_type, level_count,
-		            level_count > mip_full_levels(dim_x ? dim_x : 1, dim_y ? dim_y : 1) ? "level_count exceeds the full chain" : "bad image");
-		return status;
-	}
-	// (a null buffer: what astcenc_amd_compress_image_device returns for one)
-	if (!device_image) { backend_log("%s: device_image is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
-	if (layout.level_count > 1 && !device_levels) { backend_log("%s: device_levels is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
-	if (levels_len < layout.texels_len)
-	{
-		backend_log("%s: levels_len %zu, the chain needs %zu", fn, levels_len, layout.texels_len);
-		return ASTCENC_ERR_OUT_OF_MEM;
-	}
-	memset(&gen, 0, sizeof(gen));
-	gen.device_image = device_image;
-	gen.dim_x = dim_x; gen.dim_y = dim_y; gen.dim_z = 1; gen.kind = ASTCENC_AMD_MIP_ARRAY;
-	gen.data_type = (uint32_t)data_type; gen.level_count = layout.level_count;
-	gen.srgb = ctx->config.profile == ASTCENC_PRF_LDR_SRGB ? 1u : 0u;
-	gen.device_levels = static_cast<uint8_t*>(device_levels);
-	for (unsigned int i = 0; i < layout.level_count; i++) gen.texels_offset[i] = layout.texels_offset[i];
-	gen.stream = hip_stream;
-	return ASTCENC_SUCCESS;
-}
-
-astcenc_error astcenc_amd_generate_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
-                                                    astcenc_type data_type, unsigned int level_count, void* device_levels, size_t levels_len,
-                                                    void* hip_stream)
-{
-	static const char* fn = "astcenc_amd_generate_mip_chain_device";
-	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
-	struct astcenc_amd_mip_chain_layout layout;
-	MipChainJob gen;
-	astcenc_error status = check_mip_args(fn, ctx, device_image, dim_x, dim_y, data_type, level_count, device_levels, levels_len, hip_stream, layout, gen);
-	if (status != ASTCENC_SUCCESS) return status;
-	if (layout.level_count == 1) return ASTCENC_SUCCESS;
-	status = rc_to_error(backend_generate_mips(ctx->backend, gen));
-	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: device_levels or hip_stream is not on the device of device_image", fn);
-	return status;
-}
-
-astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
-                                                    astcenc_type data_type, const astcenc_swizzle* swizzle, unsigned int level_count,
-                                                    void* device_levels, size_t levels_len, void* device_blocks, size_t blocks_len,
-                                                    void* hip_stream, float* kernel_ms)
-{
-	static const char* fn = "astcenc_amd_compress_mip_chain_device";
-	if (!ctx || !swizzle) return ASTCENC_ERR_BAD_PARAM;
-	struct astcenc_amd_mip_chain_layout layout;
-	MipChainJob gen;
-	astcenc_error status = check_mip_args(fn, ctx, device_image, dim_x, dim_y, data_type, level_count, device_levels, levels_len, hip_stream, layout, gen);
-	if (status != ASTCENC_SUCCESS) return status;
-	if (!device_blocks) { backend_log("%s: device_blocks is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
-	if (blocks_len < layout.blocks_len)
-	{
-		backend_log("%s: blocks_len %zu, the chain needs %zu", fn, blocks_len, layout.blocks_len);
-		return ASTCENC_ERR_OUT_OF_MEM;
-	}
-	// one set entry per level: level 0 is the caller's image, level i >= 1 lies in device_levels
-	std::vector<astcenc_amd_image_set_entry> entries(layout.level_count);
-	for (unsigned int i = 0; i < layout.level_count; i++)
-	{
-		astcenc_amd_image_set_entry& e = entries[i];
-		e.image = i == 0 ? const_cast<void*>(device_image) : static_cast<uint8_t*>(device_levels) + layout.texels_offset[i];
-		e.blocks = static_cast<uint8_t*>(device_blocks) + layout.blocks_offset[i];
-		e.blocks_len = (i + 1 < layout.level_count ? layout.blocks_offset[i + 1] : layout.blocks_len) - layout.blocks_offset[i];
-		e.dim_x = layout.dim_x[i]; e.dim_y = layout.dim_y[i]; e.dim_z = 1;
-		e.data_type = data_type;
-		e.swizzle = *swizzle;
-	}
-	status = compress_set(ctx, entries.data(), layout.level_count, hip_stream, kernel_ms, layout.level_count > 1 ? &gen : nullptr);
-	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream on another device than device_image, or more than 2^32 - 1 blocks", fn);
-	return status;
-}
-
-/* Mip chains of arrays and volumes: the 2D chain's checks with a third dimension (include/astcenc_amd.h). */
+/* Mip chains (include/astcenc_amd.h): the layout is host arithmetic; generation and compression check everything first.  A 2D
+ * chain is the VOLUME of depth 1: that kind takes the 3D footprints the 2D calls take, and at depth 1 it has the 2D layout and
+ * makes its levels with the 2D kernels (kernel_mips.hip). */
 astcenc_error astcenc_amd_mip_chain_volume_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
                                                   astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
                                                   struct astcenc_amd_mip_chain_volume_layout* layout)
@@ -319,6 +208,7 @@ static astcenc_error check_mip_volume_args(const char* fn, astcenc_context* ctx,
 		            (int)data_type, level_count, why);
 		return status;
 	}
+	// (a null buffer: what astcenc_amd_compress_image_device returns for one)
 	if (!device_image) { backend_log("%s: device_image is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
 	if (layout.level_count > 1 && !device_levels) { backend_log("%s: device_levels is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
 	if (levels_len < layout.texels_len)
@@ -337,11 +227,11 @@ static astcenc_error check_mip_volume_args(const char* fn, astcenc_context* ctx,
 	return ASTCENC_SUCCESS;
 }
 
-astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
-                                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
-                                                           unsigned int level_count, void* device_levels, size_t levels_len, void* hip_stream)
+/* The generation and compression entry points; fn: the name of the one called, for the log. */
+static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                        unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
+                                        void* device_levels, size_t levels_len, void* hip_stream)
 {
-	static const char* fn = "astcenc_amd_generate_mip_chain_volume_device";
 	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
 	MipChainJob gen;
@@ -354,13 +244,11 @@ astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx,
 	return status;
 }
 
-astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
-                                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
-                                                           const astcenc_swizzle* swizzle, unsigned int level_count, void* device_levels,
-                                                           size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
-                                                           float* kernel_ms)
+static astcenc_error compress_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                        unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, const astcenc_swizzle* swizzle,
+                                        unsigned int level_count, void* device_levels, size_t levels_len, void* device_blocks,
+                                        size_t blocks_len, void* hip_stream, float* kernel_ms)
 {
-	static const char* fn = "astcenc_amd_compress_mip_chain_volume_device";
 	if (!ctx || !swizzle) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
 	MipChainJob gen;
@@ -373,6 +261,7 @@ astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx,
 		backend_log("%s: blocks_len %zu, the chain needs %zu", fn, blocks_len, layout.blocks_len);
 		return ASTCENC_ERR_OUT_OF_MEM;
 	}
+	// one set entry per level: level 0 is the caller's image, level i >= 1 lies in device_levels
 	std::vector<astcenc_amd_image_set_entry> entries(layout.level_count);
 	for (unsigned int i = 0; i < layout.level_count; i++)
 	{
@@ -387,6 +276,58 @@ astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx,
 	status = compress_set(ctx, entries.data(), layout.level_count, hip_stream, kernel_ms, layout.level_count > 1 ? &gen : nullptr);
 	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream on another device than device_image, or more than 2^32 - 1 blocks", fn);
 	return status;
+}
+
+astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                                           unsigned int level_count, void* device_levels, size_t levels_len, void* hip_stream)
+{
+	return generate_mip_chain("astcenc_amd_generate_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          level_count, device_levels, levels_len, hip_stream);
+}
+
+astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                           unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                                           const astcenc_swizzle* swizzle, unsigned int level_count, void* device_levels,
+                                                           size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
+                                                           float* kernel_ms)
+{
+	return compress_mip_chain("astcenc_amd_compress_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          swizzle, level_count, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+}
+
+astcenc_error astcenc_amd_mip_chain_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, astcenc_type data_type,
+                                           unsigned int level_count, struct astcenc_amd_mip_chain_layout* layout)
+{
+	if (!config || !layout) return ASTCENC_ERR_BAD_PARAM;
+	struct astcenc_amd_mip_chain_volume_layout vol;       // (all zero unless it succeeds)
+	const astcenc_error status = astcenc_amd_mip_chain_volume_layout(config, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type, level_count, &vol);
+	memset(layout, 0, sizeof(*layout));
+	layout->level_count = vol.level_count;
+	memcpy(layout->dim_x, vol.dim_x, sizeof(vol.dim_x));
+	memcpy(layout->dim_y, vol.dim_y, sizeof(vol.dim_y));
+	memcpy(layout->texels_offset, vol.texels_offset, sizeof(vol.texels_offset));
+	memcpy(layout->blocks_offset, vol.blocks_offset, sizeof(vol.blocks_offset));
+	layout->texels_len = vol.texels_len;
+	layout->blocks_len = vol.blocks_len;
+	return status;
+}
+
+astcenc_error astcenc_amd_generate_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                    astcenc_type data_type, unsigned int level_count, void* device_levels, size_t levels_len,
+                                                    void* hip_stream)
+{
+	return generate_mip_chain("astcenc_amd_generate_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
+	                          level_count, device_levels, levels_len, hip_stream);
+}
+
+astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                    astcenc_type data_type, const astcenc_swizzle* swizzle, unsigned int level_count,
+                                                    void* device_levels, size_t levels_len, void* device_blocks, size_t blocks_len,
+                                                    void* hip_stream, float* kernel_ms)
+{
+	return compress_mip_chain("astcenc_amd_compress_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
+	                          swizzle, level_count, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 } // extern "C"

@@ -70,7 +70,8 @@ struct CompressSetJob {
 
 /* Levels 1 .. level_count - 1 of a device image (astcenc_amd_generate_mip_chain_device and its _volume_ form, mip_filter.h):
  * level i at device_levels + texels_offset[i]; runs on the device that owns device_image, every buffer must be there (else
- * rc 3).  kind 0 (ASTCENC_AMD_MIP_ARRAY): dim_z independent 2D layers, a 2D image being one; kind 1 (VOLUME): z halves too. */
+ * rc 3).  kind 0 (ASTCENC_AMD_MIP_ARRAY): dim_z independent 2D layers; kind 1 (VOLUME): z halves too, a 2D image being the
+ * volume of depth 1. */
 struct MipChainJob {
 	const void* device_image;
 	uint32_t dim_x, dim_y, dim_z, kind, data_type, level_count;
@@ -203,17 +204,10 @@ int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream);
 size_t astc_decode_tables_bytes();
 void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uint32_t block_z);
 
-/* Mip chain generation (kernel_mips.hip): levels 1 .. levels - 1 of level[0] (dim_x x dim_y x dim_z texels of data_type), level[i]
- * made from level[i - 1].  d_srgb: the tables of astc_mip_srgb_tables_build in device memory (astc_mip_srgb_table_bytes()),
- * used for RGBA8 when srgb != 0. */
-struct MipLaunch {
-	void* level[MIP_MAX_LEVELS];      // (level 0 is only read)
-	uint32_t dim_x, dim_y, data_type, levels, srgb;
-	uint32_t dim_z, kind;             // layers (kind 0, array) or depth (kind 1, volume) of level 0; dim_z == 1: a 2D image
-	const void* d_srgb;
-	void* stream;
-};
-int astc_mip_launch(const MipLaunch& m);
+/* Mip chain generation (kernel_mips.hip): queues the launches of `job` on `stream` (job.stream unused), level i made from level
+ * i - 1.  d_srgb: the tables of astc_mip_srgb_tables_build in device memory (astc_mip_srgb_table_bytes()), used for RGBA8 when
+ * job.srgb != 0. */
+int astc_mip_launch(const MipChainJob& job, const void* d_srgb, void* stream);
 size_t astc_mip_srgb_table_bytes();
 void astc_mip_srgb_tables_build(void* out);
 

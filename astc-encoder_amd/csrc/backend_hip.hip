@@ -1419,15 +1419,7 @@ static int set_table_upload(DeviceSlot* s, hipStream_t stream, size_t bytes)
 /* Queues the generation of a mip chain on `stream` (the slot's lock held). */
 static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChainJob& job)
 {
-	MipLaunch m;
-	memset(&m, 0, sizeof(m));
-	m.level[0] = const_cast<void*>(job.device_image);
-	for (uint32_t i = 1; i < job.level_count; i++) m.level[i] = job.device_levels + job.texels_offset[i];
-	m.dim_x = job.dim_x; m.dim_y = job.dim_y; m.data_type = job.data_type; m.levels = job.level_count;
-	m.dim_z = job.dim_z; m.kind = job.kind;
-	m.srgb = job.srgb; m.d_srgb = s->d_srgb;
-	m.stream = stream;
-	const int lrc = astc_mip_launch(m);
+	const int lrc = astc_mip_launch(job, s->d_srgb, stream);
 	if (lrc != 0) { log_msg("mip generation kernel launch failed (hip error %d)", lrc); return 2; }
 	return 0;
 }

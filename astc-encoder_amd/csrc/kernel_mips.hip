@@ -8,9 +8,9 @@
 //     (astc_downsample_tail): each level lives in LDS, where the next one reads it, and is written out once.
 // Texture arrays and cube maps (ASTCENC_AMD_MIP_ARRAY) run the same launches over all layers: a layer's rows follow the
 // previous layer's, so the even path is unchanged, the tap loop finds the layer from its row, and the tail runs one
-// workgroup per layer.  A 2D image is the array of one layer.  Volumes (ASTCENC_AMD_MIP_VOLUME) whose source level has more
-// than one slice take the 3D kernels astc_mip3d_even / _level / _tail, the same shapes with a z axis; a level whose source
-// depth is 1 takes the 2D kernels, which the 3D filter then equals.
+// workgroup per layer.  Volumes (ASTCENC_AMD_MIP_VOLUME) whose source level has more than one slice take the 3D kernels
+// astc_mip3d_even / _level / _tail, the same shapes with a z axis; a level whose source depth is 1 takes the 2D kernels with
+// one layer, their texels being the 3D filter's of depth 1.  A 2D image is the volume of depth 1, so every level of it does.
 // Linear RGBA8 is integer arithmetic only; float64 is used for sRGB channels and float data, as the filter demands.
 #include "backend.h"
 #include "mip_filter.h"
@@ -78,7 +78,6 @@ template <> __device__ inline float4 mip_load_global<MIP_F32>(const void* src, s
 	return make_float4(p[0], p[1], p[2], p[3]);
 }
 
-/* One destination texel with the taps (tx, ty), its source texels read by load(x, y) -> stored texel. */
 /* Row r of a layered level (rows_per_layer rows per layer) -> its layer and its row within the layer. */
 __device__ inline void mip_row_layer(size_t r, uint32_t rows_per_layer, size_t& layer, uint32_t& y)
 {
@@ -93,6 +92,7 @@ __device__ inline void mip_row_layer(size_t r, uint32_t rows_per_layer, size_t& 
 	}
 }
 
+/* One destination texel with the taps (tx, ty), its source texels read by load(x, y) -> stored texel. */
 template <int K, typename Load>
 __device__ inline typename MipTexel<K>::T mip_texel(const MipTaps& tx, const MipTaps& ty, Load load, const double* srgb)
 {
@@ -415,18 +415,19 @@ astc_mip3d_tail(Mip3dTailArgs a, const double* __restrict__ srgb)
 }
 
 template <int K>
-static int mip_launch_kind(const MipLaunch& m)
+static int mip_launch_kind(const MipChainJob& job, const double* srgb, hipStream_t stream)
 {
 	typedef typename MipTexel<K>::T T;
-	const hipStream_t stream = static_cast<hipStream_t>(m.stream);
-	const double* srgb = static_cast<const double*>(m.d_srgb);
-	const bool volume = m.kind == 1;
-	uint32_t sx = m.dim_x, sy = m.dim_y, sz = m.dim_z ? m.dim_z : 1u;
-	for (uint32_t level = 1; level < m.levels; level++)
+	uint8_t* level_at[MIP_MAX_LEVELS];      // (level 0 is only read)
+	level_at[0] = static_cast<uint8_t*>(const_cast<void*>(job.device_image));
+	for (uint32_t i = 1; i < job.level_count; i++) level_at[i] = job.device_levels + job.texels_offset[i];
+	const bool volume = job.kind == 1;
+	uint32_t sx = job.dim_x, sy = job.dim_y, sz = job.dim_z;
+	for (uint32_t level = 1; level < job.level_count; level++)
 	{
-		const void* src = m.level[level - 1];
+		const void* src = level_at[level - 1];
 		const uint32_t dx = sx > 1 ? sx >> 1 : 1u, dy = sy > 1 ? sy >> 1 : 1u;
-		uint8_t* dst = static_cast<uint8_t*>(m.level[level]);
+		uint8_t* dst = level_at[level];
 		const size_t src_pitch = (size_t)sx * sizeof(T);
 		const bool aligned = (src_pitch & 31u) == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
 		if (volume && sz > 1)
@@ -436,8 +437,8 @@ static int mip_launch_kind(const MipLaunch& m)
 			{
 				Mip3dTailArgs a;
 				memset(&a, 0, sizeof(a));
-				a.src = src; a.sx = sx; a.sy = sy; a.sz = sz; a.levels = m.levels - level;
-				for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = static_cast<uint8_t*>(m.level[level + k]);
+				a.src = src; a.sx = sx; a.sy = sy; a.sz = sz; a.levels = job.level_count - level;
+				for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = level_at[level + k];
 				hipLaunchKernelGGL(astc_mip3d_tail<K>, dim3(1), dim3(MIP_TAIL_THREADS), 0, stream, a, srgb);
 				break;
 			}
@@ -461,8 +462,8 @@ static int mip_launch_kind(const MipLaunch& m)
 		{
 			MipTailArgs a;
 			memset(&a, 0, sizeof(a));
-			a.src = src; a.sx = sx; a.sy = sy; a.levels = m.levels - level;
-			for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = static_cast<uint8_t*>(m.level[level + k]);
+			a.src = src; a.sx = sx; a.sy = sy; a.levels = job.level_count - level;
+			for (uint32_t k = 0; k < a.levels; k++) a.dst[k] = level_at[level + k];
 			const uint32_t groups = layers < MIP_MAX_GROUPS ? layers : MIP_MAX_GROUPS;
 			hipLaunchKernelGGL(astc_downsample_tail<K>, dim3(groups), dim3(MIP_TAIL_THREADS), 0, stream, a, layers, srgb);
 			break;
@@ -484,14 +485,16 @@ static int mip_launch_kind(const MipLaunch& m)
 	return (int)hipGetLastError();
 }
 
-int astc_mip_launch(const MipLaunch& m)
+int astc_mip_launch(const MipChainJob& job, const void* d_srgb, void* stream)
 {
-	if (m.levels < 2) return 0;
-	switch (m.data_type)
+	if (job.level_count < 2) return 0;
+	const double* srgb = static_cast<const double*>(d_srgb);
+	const hipStream_t s = static_cast<hipStream_t>(stream);
+	switch (job.data_type)
 	{
-	case 0: return m.d_srgb && m.srgb ? mip_launch_kind<MIP_U8_SRGB>(m) : mip_launch_kind<MIP_U8>(m);
-	case 1: return mip_launch_kind<MIP_F16>(m);
-	default: return mip_launch_kind<MIP_F32>(m);
+	case 0: return srgb && job.srgb ? mip_launch_kind<MIP_U8_SRGB>(job, srgb, s) : mip_launch_kind<MIP_U8>(job, srgb, s);
+	case 1: return mip_launch_kind<MIP_F16>(job, srgb, s);
+	default: return mip_launch_kind<MIP_F32>(job, srgb, s);
 	}
 }
 

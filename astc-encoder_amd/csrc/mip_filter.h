@@ -2,9 +2,11 @@
 // The filter of mip chain generation (astcenc_amd_generate_mip_chain_device, include/astcenc_amd.h): the taps of a destination
 // texel along one axis, the per-texel arithmetic of every data type, and the chain's level dimensions.  Everything here is
 // exactly reproducible -- integer arithmetic for linear U8, float64 in a fixed order for sRGB and float data, explicit
-// round-to-nearest-even conversions -- so that a numpy model (tests/mip_model.py) matches it bit for bit.
-// The chains of volumes (astcenc_amd_generate_mip_chain_volume_device) add a z axis with the same taps: mip_texel_u8_3d and
-// mip_texel_float_3d below (numpy model: tests/mip_model_3d.py).  A volume of depth 1 gives exactly the 2D arithmetic.
+// round-to-nearest-even conversions -- so that the numpy models (tests/mip_model.py, tests/mip_model_3d.py) match it bit for
+// bit.  The arithmetic is written once, over three axes (mip_texel_u8_3d, mip_texel_float_3d): a volume's z axis
+// (astcenc_amd_generate_mip_chain_volume_device) has the taps of x and y.  A 2D texel (mip_texel_u8, mip_texel_float) is a
+// texel of depth 1, whose z taps mip_axis_taps(1, 0) -- one tap of weight 1 over a denominator of 1 -- make every step of the
+// z axis exact, so that the result is the 2D arithmetic of include/astcenc_amd.h.
 //
 // No includes and no HIP types: kernel_mips.hip builds its kernels on these functions and tests/test_mip_chain_cpu.py
 // compiles the header with g++.
@@ -74,7 +76,7 @@ ASTC_MIP_FN MipTaps mip_axis_taps(unsigned int s, unsigned int j)
 }
 
 /* The mean of integer texels: sum / den rounded to the nearest integer, ties up.  (sum <= 255 * den; den = the product of the
- * two axis denominators, at most the level's texel count, so 2 * sum + den stays far below 2^64.) */
+ * axis denominators, at most the level's texel count, so 2 * sum + den stays far below 2^64.) */
 ASTC_MIP_FN unsigned int mip_round_mean(unsigned long long sum, unsigned long long den)
 {
 	return (unsigned int)((2ull * sum + den) / (2ull * den));
@@ -146,90 +148,11 @@ ASTC_MIP_FN float mip_float_from_half(unsigned short h)
 /* (The tap loops run a fixed three trips with an early exit: the weights are then indexed by constants, which keeps them in
  * registers on the device.)
  *
- * One destination texel of float data (F16 / F32 sources, stored as float channels): for each y tap in increasing source row,
- * row = w_x0 * v0 + w_x1 * v1 (+ w_x2 * v2), then acc = w_y0 * row0 + w_y1 * row1 (+ ...), all in float64 (each sum starts at
- * its first product), then acc / (den_x * den_y) in float64, rounded to float32.  load(x, y, float v[4]) reads a source texel. */
-template <typename Load>
-ASTC_MIP_FN void mip_texel_float(const MipTaps& tx, const MipTaps& ty, Load load, float out[4])
-{
-	double acc[4] = { 0.0, 0.0, 0.0, 0.0 };
-	ASTC_MIP_UNROLL
-	for (unsigned int ky = 0; ky < 3; ky++)
-	{
-		if (ky >= ty.count) break;
-		double row[4] = { 0.0, 0.0, 0.0, 0.0 };
-		ASTC_MIP_UNROLL
-		for (unsigned int kx = 0; kx < 3; kx++)
-		{
-			if (kx >= tx.count) break;
-			float v[4];
-			load(tx.first + kx, ty.first + ky, v);
-			for (int c = 0; c < 4; c++)
-			{
-				const double p = (double)tx.w[kx] * (double)v[c];
-				row[c] = kx == 0 ? p : row[c] + p;
-			}
-		}
-		for (int c = 0; c < 4; c++)
-		{
-			const double q = (double)ty.w[ky] * row[c];
-			acc[c] = ky == 0 ? q : acc[c] + q;
-		}
-	}
-	const double den = (double)tx.den * (double)ty.den;
-	for (int c = 0; c < 4; c++) out[c] = (float)(acc[c] / den);
-}
-
-/* One destination texel of RGBA8 data: load(x, y) reads a source texel (packed, R in the low byte).  lin == null: every channel
- * linear, the exact rational mean rounded to nearest, ties up.  Otherwise (sRGB): channels 0-2 are decoded through lin[256]
- * (the sRGB EOTF of c / 255), averaged as mip_texel_float averages and encoded with mip_srgb_encode(thr); channel 3 is linear. */
-template <typename Load>
-ASTC_MIP_FN unsigned int mip_texel_u8(const MipTaps& tx, const MipTaps& ty, Load load, const double* lin, const double* thr)
-{
-	unsigned long long sum[4] = { 0, 0, 0, 0 };
-	double acc[3] = { 0.0, 0.0, 0.0 };
-	ASTC_MIP_UNROLL
-	for (unsigned int ky = 0; ky < 3; ky++)
-	{
-		if (ky >= ty.count) break;
-		double row[3] = { 0.0, 0.0, 0.0 };
-		ASTC_MIP_UNROLL
-		for (unsigned int kx = 0; kx < 3; kx++)
-		{
-			if (kx >= tx.count) break;
-			const unsigned int p = load(tx.first + kx, ty.first + ky);
-			const unsigned long long w = (unsigned long long)tx.w[kx] * ty.w[ky];
-			for (int c = 0; c < 4; c++) sum[c] += w * ((p >> (8 * c)) & 0xFFu);
-			if (lin)
-				for (int c = 0; c < 3; c++)
-				{
-					const double v = (double)tx.w[kx] * lin[(p >> (8 * c)) & 0xFFu];
-					row[c] = kx == 0 ? v : row[c] + v;
-				}
-		}
-		if (lin)
-			for (int c = 0; c < 3; c++)
-			{
-				const double q = (double)ty.w[ky] * row[c];
-				acc[c] = ky == 0 ? q : acc[c] + q;
-			}
-	}
-	const unsigned long long den = (unsigned long long)tx.den * ty.den;
-	unsigned int out = mip_round_mean(sum[3], den) << 24;
-	if (lin)
-	{
-		const double dden = (double)tx.den * (double)ty.den;
-		for (int c = 0; c < 3; c++) out |= mip_srgb_encode(acc[c] / dden, thr) << (8 * c);
-	}
-	else
-		for (int c = 0; c < 3; c++) out |= mip_round_mean(sum[c], den) << (8 * c);
-	return out;
-}
-
-/* One destination texel of float data in a volume: for each z tap in increasing slice, the 2D acc of that slice exactly as
- * mip_texel_float computes it (before its division), then vol = w_z0 * acc0 + w_z1 * acc1 (+ ...) in float64 (starting at its
- * first product), then vol / ((den_x * den_y) * den_z) in float64, rounded to float32.  load(x, y, z, float v[4]).  With one z
- * tap (a source of depth 1: weight 1, denominator 1) every step is exact and the result is mip_texel_float's. */
+ * One destination texel of float data (F16 / F32 sources, stored as float channels): for each z tap in increasing slice and
+ * each y tap in increasing row, row = w_x0 * v0 + w_x1 * v1 (+ w_x2 * v2); per slice acc = w_y0 * row0 + w_y1 * row1 (+ ...);
+ * vol = w_z0 * acc0 + w_z1 * acc1 (+ ...); all in float64 (each sum starts at its first product), then
+ * vol / ((den_x * den_y) * den_z) in float64, rounded to float32.  load(x, y, z, float v[4]) reads a source texel.  With the
+ * z taps of depth 1, vol = 1.0 * acc and the denominator is (den_x * den_y) * 1.0, both exact. */
 template <typename Load>
 ASTC_MIP_FN void mip_texel_float_3d(const MipTaps& tx, const MipTaps& ty, const MipTaps& tz, Load load, float out[4])
 {
@@ -272,10 +195,10 @@ ASTC_MIP_FN void mip_texel_float_3d(const MipTaps& tx, const MipTaps& ty, const 
 	for (int c = 0; c < 4; c++) out[c] = (float)(vol[c] / den);
 }
 
-/* One destination texel of RGBA8 data in a volume, load(x, y, z) -> packed texel.  Linear channels: weight w_x * w_y * w_z,
- * denominator den_x * den_y * den_z (at most the source level's texel count), the exact rational mean rounded to nearest,
- * ties up.  sRGB channels 0-2 (lin != null): the decoded values averaged as mip_texel_float_3d averages, encoded with
- * mip_srgb_encode(thr); channel 3 linear. */
+/* One destination texel of RGBA8 data: load(x, y, z) reads a source texel (packed, R in the low byte).  lin == null: every
+ * channel linear, weight w_x * w_y * w_z, denominator den_x * den_y * den_z (at most the source level's texel count), the exact
+ * rational mean rounded to nearest, ties up.  Otherwise (sRGB): channels 0-2 are decoded through lin[256] (the sRGB EOTF of
+ * c / 255), averaged as mip_texel_float_3d averages and encoded with mip_srgb_encode(thr); channel 3 is linear. */
 template <typename Load>
 ASTC_MIP_FN unsigned int mip_texel_u8_3d(const MipTaps& tx, const MipTaps& ty, const MipTaps& tz, Load load, const double* lin,
                                          const double* thr)
@@ -330,6 +253,20 @@ ASTC_MIP_FN unsigned int mip_texel_u8_3d(const MipTaps& tx, const MipTaps& ty, c
 	else
 		for (int c = 0; c < 3; c++) out |= mip_round_mean(sum[c], den) << (8 * c);
 	return out;
+}
+
+/* A 2D texel: the texel of depth 1 (z taps mip_axis_taps(1, 0)), its source texels read by load(x, y, float v[4]) /
+ * load(x, y) -> packed texel. */
+template <typename Load>
+ASTC_MIP_FN void mip_texel_float(const MipTaps& tx, const MipTaps& ty, Load load, float out[4])
+{
+	mip_texel_float_3d(tx, ty, mip_axis_taps(1, 0), [&](unsigned int x, unsigned int y, unsigned int, float v[4]) { load(x, y, v); }, out);
+}
+
+template <typename Load>
+ASTC_MIP_FN unsigned int mip_texel_u8(const MipTaps& tx, const MipTaps& ty, Load load, const double* lin, const double* thr)
+{
+	return mip_texel_u8_3d(tx, ty, mip_axis_taps(1, 0), [&](unsigned int x, unsigned int y, unsigned int) { return load(x, y); }, lin, thr);
 }
 
 } // namespace astcd

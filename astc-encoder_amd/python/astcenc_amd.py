@@ -361,26 +361,11 @@ class Library:
         return err, layout
 
     def _mip_chain_buffers(self, ctx, image, levels, blocks):
-        """(w, h, dtype code, layout, device_levels tensor, level tensors [level 0 = image], blocks tensor or None) of a chain;
-        the context's config gives the footprint."""
-        import torch
-        types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
-        assert image.is_contiguous() and image.dim() == 3 and image.shape[-1] == 4, "a contiguous [H, W, 4] device tensor"
-        h, w = image.shape[0], image.shape[1]
-        cfg = Config()
-        cfg.block_x, cfg.block_y, cfg.block_z = self._ctx_block(ctx)
-        err, layout = self.mip_chain_layout(cfg, w, h, types[image.dtype], levels)
-        if err:
-            raise AstcError(err, "astcenc_amd_mip_chain_layout")
-        n = layout.level_count
-        store = torch.empty(max(layout.texels_len, 1), dtype=torch.uint8, device=image.device)
-        tensors = [image]
-        for i in range(1, n):
-            size = layout.dim_x[i] * layout.dim_y[i] * 4 * image.element_size()
-            tensors.append(store[layout.texels_offset[i]:layout.texels_offset[i] + size].view(image.dtype)
-                           .view(layout.dim_y[i], layout.dim_x[i], 4))
-        out = torch.empty(layout.blocks_len, dtype=torch.uint8, device=image.device) if blocks else None
-        return w, h, types[image.dtype], layout, store, tensors, out
+        """(w, h, dtype code, layout, device_levels tensor, level tensors [level 0 = image], blocks tensor or None) of the chain of
+        an [H, W, 4] device tensor: the volume of depth 1's; the context's config gives the footprint."""
+        assert image.dim() == 3, "a contiguous [H, W, 4] device tensor"
+        (w, h, _), dtype, layout, store, tensors, out = self._mip_chain_volume_buffers(ctx, image[None], MIP_VOLUME, levels, blocks)
+        return w, h, dtype, layout, store, [image] + [t[0] for t in tensors[1:]], out
 
     def _ctx_block(self, ctx):
         """The footprint of a context (astcenc_get_block_info on a zero block: it reports the context's block size)."""
@@ -682,41 +667,19 @@ def read_ktx(path):
 
 def write_ktx_mips(path, level_blocks, width, height, block, srgb=False):
     """Write the blocks of a mip chain (level_blocks[i]: level i, max(1, width >> i) x max(1, height >> i) texels) as one KTX 1.1
-    file: numberOfMipmapLevels = len(level_blocks), each level preceded by its imageSize (ASTC levels are whole 16-byte blocks,
-    so no mip padding)."""
-    import struct
+    file: write_ktx_chain of one 2D image (depth 1, no array, one face), so a level of the wrong size is a ValueError."""
     if len(block) > 2 and block[2] > 1:
         raise ValueError("mip chains are 2D: a 2D footprint")
-    header = KTX_MAGIC + struct.pack("<13I", 0x04030201, 0, 1, 0, ktx_gl_format(block, srgb), GL_RGBA,
-                                     width, height, 0, 0, 1, len(level_blocks), 0)
-    with open(path, "wb") as f:
-        f.write(header)
-        for blocks in level_blocks:
-            data = np.ascontiguousarray(blocks if isinstance(blocks, np.ndarray) else blocks.cpu().numpy(), dtype=np.uint8).tobytes()
-            f.write(struct.pack("<I", len(data)) + data)
+    write_ktx_chain(path, level_blocks, width, height, block, depth=1, layers=0, faces=1, srgb=srgb)
 
 
 def read_ktx_mips(path):
     """-> ([blocks uint8[] per level], width, height, (bx, by, bz), is_srgb) of a 2D KTX 1.1 file with any number of mip levels
-    (either byte order); the level sizes are checked against the footprint."""
-    import struct
-    raw = open(path, "rb").read()
-    _, w, h, d, block, srgb = read_ktx(path)
-    if d != 1:
+    (either byte order): read_ktx_chain's levels; the level sizes are checked against the footprint."""
+    k = read_ktx_chain(path)
+    if k["depth"] != 1 or k["layers"] != 0 or k["faces"] != 1:
         raise ValueError("not a 2D KTX file")
-    e = "<" if struct.unpack_from("<I", raw, 12)[0] == 0x04030201 else ">"
-    mips, kv = struct.unpack_from(e + "2I", raw, 56)
-    at, levels = 64 + kv, []
-    for i in range(max(mips, 1)):
-        if len(raw) < at + 4:
-            raise ValueError("truncated KTX file")
-        n = struct.unpack_from(e + "I", raw, at)[0]
-        lw, lh = max(1, w >> i), max(1, h >> i)
-        if n != -(-lw // block[0]) * -(-lh // block[1]) * 16 or len(raw) < at + 4 + n:
-            raise ValueError("bad KTX mip level %d" % i)
-        levels.append(np.frombuffer(raw, dtype=np.uint8, count=n, offset=at + 4).copy())
-        at += 4 + n + (-n % 4)
-    return levels, w, h, block, srgb
+    return k["levels"], k["w"], k["h"], k["block"], k["srgb"]
 
 
 def _ktx_chain_level_bytes(w, h, depth, layers, faces, block, i):

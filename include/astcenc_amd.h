@@ -139,7 +139,7 @@ struct astcenc_amd_mip_chain_layout {
 
 /* The layout of a chain for the footprint of `config` (a 3D footprint makes one layer of blocks per 2D level).  Pure host
  * arithmetic, no device and no context: usable before any allocation.  A null config or layout, a zero dimension or an unknown
- * data_type: ASTCENC_ERR_BAD_PARAM. */
+ * data_type: ASTCENC_ERR_BAD_PARAM.  So is a chain whose texel or block bytes overflow size_t. */
 ASTCENC_PUBLIC enum astcenc_error astcenc_amd_mip_chain_layout(
 	const struct astcenc_config* config,
 	unsigned int dim_x, unsigned int dim_y,

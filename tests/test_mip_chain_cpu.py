@@ -2,7 +2,7 @@
 """Mip chains without a GPU (astcenc_amd_mip_chain_layout, csrc/mip_filter.h).
 
   * the layout of a chain: level count, dimensions, 256-byte aligned texel offsets, block offsets and totals, for several
-    footprints (3D ones on 2D images too) and all three data types; a level_count beyond the full chain, a null layout;
+    footprints (3D ones on 2D images too) and all three data types; a level_count beyond the full chain, overflow, a null layout;
   * the filter header compiled with g++, bit for bit against the numpy model (tests/mip_model.py): every odd / even size up to
     9 x 9, strips, U8 linear and sRGB, F16, F32 at extreme magnitudes and of mixed sign;
   * the argument checks that need no device: a null context on every entry point."""
@@ -229,10 +229,11 @@ def test_layout(product, A, block):
                 for i in range(len(dims), A.MAX_MIP_LEVELS):
                     assert lay.dim_x[i] == 0 and lay.texels_offset[i] == 0
             assert product.mip_chain_layout(cfg, w, h, dtype, M.full_levels(w, h) + 1)[0] == A.ERR_BAD_PARAM
-    # the full chain of the widest image has 32 levels; the dimensions that make no image, an unknown type, a null layout
+    # the full chain of the widest image has 32 levels; the dimensions that make no image, an unknown type, bytes beyond size_t,
+    # a null layout
     assert product.mip_chain_layout(cfg, 0xFFFFFFFF, 1, A.TYPE_U8, 0)[1].level_count == 32
     assert M.full_levels(8192, 8192) == 14 and M.full_levels(1, 1) == 1 and M.full_levels(255, 190) == 8
-    for w, h, t in ((0, 5, A.TYPE_U8), (5, 0, A.TYPE_U8), (5, 5, 3), (5, 5, -1)):
+    for w, h, t in ((0, 5, A.TYPE_U8), (5, 0, A.TYPE_U8), (5, 5, 3), (5, 5, -1), (0xFFFFFFFF, 0xFFFFFFFF, A.TYPE_F32)):
         assert product.mip_chain_layout(cfg, w, h, t, 0)[0] == A.ERR_BAD_PARAM
     assert product.lib.astcenc_amd_mip_chain_layout(C.byref(cfg), 5, 5, A.TYPE_U8, 0, None) == A.ERR_BAD_PARAM
     assert product.lib.astcenc_amd_mip_chain_layout(None, 5, 5, A.TYPE_U8, 0, C.byref(A.MipChainLayout())) == A.ERR_BAD_PARAM
