@@ -55,6 +55,46 @@ struct DecompressDeviceJob {
 	void*    stream;
 };
 
+/* Geometry shared by the backends (host code only: this header is not part of the run-time build's source). */
+inline size_t texel_bytes(uint32_t data_type) { return data_type == 0 ? 4 : data_type == 1 ? 8 : 16; }   // astcenc_type
+
+/* The blocks of a job's image in the context's footprint. */
+struct BlockGrid {
+	uint32_t x, y, z;
+	uint32_t dim_z;            // the image's slices (a job's dim_z of 0 counts as 1)
+	size_t count() const { return (size_t)x * y * z; }
+};
+template <class Job> inline BlockGrid block_grid(const TableRoot& root, const Job& job)
+{
+	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
+	return { (job.dim_x + root.dim_x - 1) / root.dim_x, (job.dim_y + root.dim_y - 1) / root.dim_y, (dim_z + root.dim_z - 1) / root.dim_z, dim_z };
+}
+
+/* The reference's fast RGBA8 loader (ref: astcenc_entry.cpp:946): identity swizzle, LDR, U8 data and a 2D footprint.  Part of the
+ * bit-exactness contract. */
+inline bool uses_fast_load(const TableRoot& root, int32_t profile, const CompressJob& job)
+{
+	const bool identity = job.swz[0] == 0 && job.swz[1] == 1 && job.swz[2] == 2 && job.swz[3] == 3;
+	return identity && profile < 2 && job.data_type == 0 && root.dim_z == 1;
+}
+
+/* The kernel's record of the image of `job` whose texels start at `data` (alpha_avg: null, set by the pre-pass). */
+inline ImageDesc image_desc(const TableRoot& root, int32_t profile, const CompressJob& job, const void* data)
+{
+	const BlockGrid g = block_grid(root, job);
+	ImageDesc img;
+	img.data = data;
+	img.dim_x = job.dim_x; img.dim_y = job.dim_y; img.dim_z = g.dim_z;
+	img.data_type = job.data_type;
+	for (int i = 0; i < 4; i++) img.swz[i] = job.swz[i];
+	img.blocks_x = g.x; img.blocks_y = g.y; img.blocks_z = g.z;
+	img.use_fast_load = uses_fast_load(root, profile, job) ? 1 : 0;
+	img.fast_load_slice0 = job.fast_load_slice0;
+	img.alpha_avg = nullptr;
+	img.a_scale_radius = job.a_scale_radius;
+	return img;
+}
+
 /* An image set on one device (astcenc_amd_compress_images_device): every entry is described by the device-resident fields
  * of a CompressJob (device_data, device_out, dimensions, data_type, swz, a_scale_radius, fast_load_slice0); the blocks of all
  * entries are compressed as one block range, entry after entry. */

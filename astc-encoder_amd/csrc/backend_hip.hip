@@ -22,6 +22,8 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace astcd {
@@ -43,36 +45,36 @@ struct SlotWorker {
 // Everything that lives on one GPU: the table blob, two streams, events and the staging buffers of the
 // host-pointer API.  A context owns one slot per device it may run on (see backend_create).
 struct DeviceSlot {
-	int device;
-	uint8_t* d_base;              // device allocation: context records, then the table blob
-	uint8_t* d_tab;               // the blob inside it
-	uint8_t* d_dectab;            // the decoder's per-footprint tables inside it (after the blob)
-	const double* d_srgb;         // the sRGB tables of mip chain generation inside it (after the decoder's)
-	hipStream_t stream;
-	hipStream_t copy_stream;      // PCIe traffic of the banded host-pointer path
-	hipEvent_t ev0, ev1, ev_copy[2], ev_band, ev_done[3], ev_out[2];
-	hipEvent_t ev_gen;            // start of a mip chain's generation: its compression's kernel_ms counts from here
+	int device = 0;
+	uint8_t* d_base = nullptr;    // device allocation: context records, then the table blob
+	uint8_t* d_tab = nullptr;     // the blob inside it
+	uint8_t* d_dectab = nullptr;  // the decoder's per-footprint tables inside it (after the blob)
+	const double* d_srgb = nullptr;   // the sRGB tables of mip chain generation inside it (after the decoder's)
+	hipStream_t stream = nullptr;
+	hipStream_t copy_stream = nullptr;   // PCIe traffic of the banded host-pointer path
+	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_copy[2] = {}, ev_band = nullptr, ev_done[3] = {}, ev_out[2] = {};
+	hipEvent_t ev_gen = nullptr;  // start of a mip chain's generation: its compression's kernel_ms counts from here
 	// pinned staging of the banded host-pointer path: two bands of input in flight, the blocks of two bands on their way back
-	uint8_t* h_in[2]; size_t h_in_cap;
-	uint8_t* h_out[2]; size_t h_out_cap;
+	uint8_t* h_in[2] = {}; size_t h_in_cap = 0;
+	uint8_t* h_out[2] = {}; size_t h_out_cap = 0;
 	// staging for the host-pointer API
-	void* d_image; size_t image_cap;
-	uint8_t* d_out; size_t out_cap;
-	float* d_alpha; size_t alpha_cap;   // alpha averages of the a_scale_radius pre-pass
-	float* d_alpha_scratch; size_t alpha_scratch_cap;   // padded tiles of the pre-pass when they outgrow LDS (large radii)
-	uint8_t* d_set; size_t set_cap;     // the table of an image set (image_set.h), compression or decompression
+	void* d_image = nullptr; size_t image_cap = 0;
+	uint8_t* d_out = nullptr; size_t out_cap = 0;
+	float* d_alpha = nullptr; size_t alpha_cap = 0;   // alpha averages of the a_scale_radius pre-pass
+	float* d_alpha_scratch = nullptr; size_t alpha_scratch_cap = 0;   // padded tiles of the pre-pass when they outgrow LDS (large radii)
+	uint8_t* d_set = nullptr; size_t set_cap = 0;     // the table of an image set (image_set.h), compression or decompression
 	std::vector<uint8_t> h_set;         // ... and its host copy (kept until the next set call: the upload is asynchronous)
-	unsigned long long* d_prof;   // stage timers (ASTC_PROFILE builds) / search trace (ASTC_TRACE builds)
-	size_t trace_cap;             // bytes at d_prof in ASTC_TRACE builds
-	double* d_sums;               // totals of the image comparison kernel
+	unsigned long long* d_prof = nullptr;   // stage timers (ASTC_PROFILE builds) / search trace (ASTC_TRACE builds)
+	size_t trace_cap = 0;         // bytes at d_prof in ASTC_TRACE builds
+	double* d_sums = nullptr;     // totals of the image comparison kernel
 	std::mutex busy;              // one call at a time per slot: the staging buffers and events are shared state
 	std::vector<int> local_cpus;  // host CPUs on the device's NUMA node (Linux sysfs); empty: unknown, no binding
-	SlotWorker* worker;           // the slot's parked host thread (slots 1.. of a multi-device context), or null
+	SlotWorker* worker = nullptr; // the slot's parked host thread (slots 1.. of a multi-device context), or null
 	// the context's run-time specialised build on this device (kernel_jit.h): loaded once it is ready, then launched
 	// instead of the library's own generic build
-	hipModule_t jit_module;
-	hipFunction_t jit_fn;
-	bool jit_tried;
+	hipModule_t jit_module = nullptr;
+	hipFunction_t jit_fn = nullptr;
+	bool jit_tried = false;
 };
 
 struct Backend {
@@ -151,6 +153,28 @@ struct DeviceGuard {
 	DeviceGuard() : saved(0), ok(hipGetDevice(&saved) == hipSuccess) {}
 	~DeviceGuard() { if (ok) (void)hipSetDevice(saved); }
 };
+
+/* Grows a staging buffer of the slot to at least `need` bytes (its contents are not kept).  0 ok, 1 out of memory: the buffer is
+ * then null and its capacity 0, so that the next call tries again. */
+template <class T> int grow(T*& buf, size_t& cap, size_t need)
+{
+	if (cap >= need) return 0;
+	if (buf) (void)hipFree(buf);
+	buf = nullptr; cap = 0;
+	HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), need + ALLOC_SLACK), return 1);
+	cap = need;
+	return 0;
+}
+/* ... and a pair of pinned host buffers. */
+int grow_pinned(uint8_t* (&pair)[2], size_t& cap, size_t need)
+{
+	if (cap >= need) return 0;
+	for (uint8_t*& h : pair) { if (h) (void)hipHostFree(h); h = nullptr; }
+	cap = 0;
+	for (uint8_t*& h : pair) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h), need, hipHostMallocDefault), return 1);
+	cap = need;
+	return 0;
+}
 
 /* The builds of the compression kernel.  Generic ones: LDR / HDR coders x footprints of at most 64 texels (whose texel
  * loops make one trip, kernel_ldr64.hip) / the larger ones.  Fixed-context ones (kernel_ldr_6x6m.hip, ...): compiled for
@@ -239,15 +263,14 @@ bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 	std::vector<uint8_t> out(2 * nblocks * 16);
 	if (ok)
 	{
+		CompressJob job;
+		memset(&job, 0, sizeof(job));
+		job.dim_x = dim_x; job.dim_y = dim_y; job.dim_z = dim_z;
+		for (int i = 0; i < 4; i++) job.swz[i] = (uint32_t)i;
 		KernelLaunch k;
 		k.d_tab = s->d_tab; k.lds_bytes = b->lds_bytes; k.d_prof = nullptr; k.d_set = nullptr; k.stream = s->stream;
 		k.first = 0; k.count = (uint32_t)nblocks;
-		ImageDesc& im = k.img;
-		im.data = d_img; im.dim_x = dim_x; im.dim_y = dim_y; im.data_type = 0;
-		for (int i = 0; i < 4; i++) im.swz[i] = (uint32_t)i;
-		im.blocks_x = nbx; im.blocks_y = nby; im.dim_z = dim_z; im.blocks_z = nbz;
-		im.use_fast_load = (b->cfg.profile < 2 && bsz == 1) ? 1 : 0;
-		im.fast_load_slice0 = 0; im.alpha_avg = nullptr; im.a_scale_radius = 0;
+		k.img = image_desc(b->root, b->cfg.profile, job, d_img);
 		ok = hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, s->stream) == hipSuccess;
 		k.d_out = d_out;
 		ok = ok && kernel_variants[b->variant].launch(k) == 0;
@@ -383,8 +406,8 @@ static void bind_worker_to_device(const DeviceSlot* s)
 /* Hands `task` to the slot's parked thread (started on first use, bound to the device's CPUs once); false when no
  * thread can be had -- std::system_error must not cross the C ABI --, or when the thread is busy with another call on
  * the same context (a second call used to wait here for the first call's whole shard before it even started its
- * own first one): a compression then deals that device's share to the others, a decompression runs the shard itself.  The
- * worker stays locked (w->mu) until worker_wait(). */
+ * own first one): the call then deals that device's share to the others (deal_portions).  The worker stays locked (w->mu)
+ * until worker_wait(). */
 static bool worker_run(DeviceSlot* s, std::function<void()> task)
 {
 	SlotWorker* w = s->worker;
@@ -441,18 +464,6 @@ DeviceSlot* slot_create(Backend* b, int device, int* status)
 {
 	DeviceSlot* s = new DeviceSlot();
 	s->device = device;
-	s->d_base = nullptr; s->d_tab = nullptr; s->stream = nullptr; s->copy_stream = nullptr;
-	s->ev0 = s->ev1 = s->ev_copy[0] = s->ev_copy[1] = s->ev_band = nullptr;
-	s->ev_done[0] = s->ev_done[1] = s->ev_done[2] = nullptr;
-	s->ev_out[0] = s->ev_out[1] = nullptr;
-	s->ev_gen = nullptr;
-	s->h_in[0] = s->h_in[1] = nullptr; s->h_in_cap = 0; s->h_out[0] = s->h_out[1] = nullptr; s->h_out_cap = 0;
-	s->d_image = nullptr; s->image_cap = 0; s->d_out = nullptr; s->out_cap = 0; s->d_alpha = nullptr; s->alpha_cap = 0;
-	s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
-	s->d_set = nullptr; s->set_cap = 0;
-	s->d_prof = nullptr; s->trace_cap = 0; s->d_sums = nullptr;
-	s->worker = nullptr;
-	s->jit_module = nullptr; s->jit_fn = nullptr; s->jit_tried = false;
 #define SLOT_TRY(expr, code) HIP_TRY(expr, { slot_destroy(s); *status = code; return nullptr; })
 	SLOT_TRY(hipSetDevice(device), 2);
 	{
@@ -561,6 +572,62 @@ bool pick_stream(const DeviceSlot* s, void* caller_stream, hipStream_t* out)
 	}
 	*out = stream;
 	return true;
+}
+
+/* Image sets.  Every buffer of the set must live on the device that owns entry 0's first buffer (or be unknown to the runtime,
+ * which the single-image path allows as well); otherwise rc 3 and nothing is launched. */
+bool set_on_one_device(const DeviceSlot* s, const void* const* ptrs, size_t count)
+{
+	for (size_t i = 0; i < count; i++)
+	{
+		hipPointerAttribute_t attr;
+		memset(&attr, 0, sizeof(attr));
+		if (!ptrs[i] || hipPointerGetAttributes(&attr, ptrs[i]) != hipSuccess) { (void)hipGetLastError(); continue; }
+		if (attr.device != s->device)
+		{
+			log_msg("image set entry %zu: a buffer of device %d, entry 0's are on device %d", i / 2, attr.device, s->device);
+			return false;
+		}
+	}
+	return true;
+}
+
+/* Runs body(s, stream) with slot `s` locked and its device current, on the caller's stream (rc 3 if it is another device's) or
+ * the slot's own. */
+template <class Body> int run_locked(DeviceSlot* s, void* caller_stream, Body body)
+{
+	std::lock_guard<std::mutex> busy(s->busy);
+	HIP_TRY(hipSetDevice(s->device), return 2);
+	hipStream_t stream;
+	if (!pick_stream(s, caller_stream, &stream)) return 3;
+	return body(s, stream);
+}
+
+/* The setup of a call on device-resident buffers: run_locked on the slot that owns `owner` (a missing slot: the status of
+ * slot_for_pointer, or 2), once the `count` pointers at `same_device` are known to be on its device as well (else rc 3). */
+template <class Body> int run_on_owner(Backend* b, const void* owner, const void* const* same_device, size_t count, void* caller_stream, Body body)
+{
+	DeviceGuard guard;
+	int st = 0;
+	DeviceSlot* s = slot_for_pointer(b, owner, &st);
+	if (!s) return st ? st : 2;
+	if (!set_on_one_device(s, same_device, count)) return 3;
+	return run_locked(s, caller_stream, body);
+}
+
+/* The decode launch of the image of `job` (a DecompressJob or DecompressDeviceJob) on slot `s`. */
+template <class Job> DecodeLaunch decode_launch(const Backend* b, const DeviceSlot* s, const Job& job, const uint8_t* d_blocks, void* d_image, hipStream_t stream)
+{
+	DecodeLaunch d;
+	d.d_blocks = d_blocks;
+	d.d_image = d_image;
+	d.d_tables = s->d_dectab;
+	d.dim_x = job.dim_x; d.dim_y = job.dim_y; d.dim_z = job.dim_z ? job.dim_z : 1u; d.data_type = job.data_type;
+	for (int i = 0; i < 4; i++) d.swz[i] = job.swz[i];
+	d.block_x = b->root.dim_x; d.block_y = b->root.dim_y; d.block_z = b->root.dim_z;
+	d.profile = b->cfg.profile;
+	d.stream = stream;
+	return d;
 }
 
 /* Completed-block counter shared by the slots of one call; the callback sees a monotonic percentage
@@ -695,35 +762,12 @@ int backend_specialize(Backend* b)
 	return b->jit_active.load() ? 0 : 1;
 }
 
-static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob& job, Progress* progress);
-
 /* The context's run-time build: adopted as soon as the compiler has delivered it; asked for (JIT_LAZY) once the context has
  * compressed enough to be worth a compile.  Called by every compression of `nblocks` blocks on slot `s`. */
 static void jit_count_blocks(Backend* b, DeviceSlot* s, size_t nblocks)
 {
 	slot_adopt_jit(b, s);
 	if (b->jit && b->jit_mode == JIT_LAZY && b->blocks_done.fetch_add(nblocks) + nblocks >= b->jit_lazy_blocks) jit_start(b->jit);
-}
-
-/* The kernel's record of the image of `job` whose texels start at `data` (alpha_avg: null, set by the pre-pass). */
-static ImageDesc image_desc(const Backend* b, const CompressJob& job, const void* data)
-{
-	const uint32_t bsx = b->root.dim_x, bsy = b->root.dim_y, bsz = b->root.dim_z;
-	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	ImageDesc img;
-	img.data = data;
-	img.dim_x = job.dim_x; img.dim_y = job.dim_y;
-	img.data_type = job.data_type;
-	for (int i = 0; i < 4; i++) img.swz[i] = job.swz[i];
-	img.blocks_x = (job.dim_x + bsx - 1) / bsx; img.blocks_y = (job.dim_y + bsy - 1) / bsy;
-	img.dim_z = dim_z; img.blocks_z = (dim_z + bsz - 1) / bsz;
-	bool needs_swz = job.swz[0] != 0 || job.swz[1] != 1 || job.swz[2] != 2 || job.swz[3] != 3;
-	bool hdr = b->cfg.profile >= 2;
-	img.use_fast_load = (!needs_swz && !hdr && job.data_type == 0 && bsz == 1) ? 1 : 0;   // ref: astcenc_entry.cpp:946
-	img.fast_load_slice0 = job.fast_load_slice0;
-	img.alpha_avg = nullptr;
-	img.a_scale_radius = job.a_scale_radius;
-	return img;
 }
 
 /* The alpha-average pre-pass of one image (`rows` texel rows of dim_x, dim_z slices) into d_averages.  Returns 0 ok, 1 out of
@@ -744,13 +788,7 @@ static int alpha_prepass(DeviceSlot* s, hipStream_t stream, const void* d_image,
 	}
 	if (scratch)
 	{
-		if (s->alpha_scratch_cap < scratch)
-		{
-			if (s->d_alpha_scratch) (void)hipFree(s->d_alpha_scratch);
-			s->d_alpha_scratch = nullptr; s->alpha_scratch_cap = 0;
-			HIP_TRY(hipMalloc(&s->d_alpha_scratch, scratch + ALLOC_SLACK), return 1);
-			s->alpha_scratch_cap = scratch;
-		}
+		if (grow(s->d_alpha_scratch, s->alpha_scratch_cap, scratch) != 0) return 1;
 		a.d_scratch = s->d_alpha_scratch;
 	}
 	int arc = astc_alpha_launch(a);
@@ -824,12 +862,12 @@ static int run_chunks(const Backend* b, DeviceSlot* s, ChunkLoop& L)
 	return 0;
 }
 
-/* The blocks of `job` on one slot.  Returns 0 ok, 1 out of memory, 2 device failure, 3 bad argument. */
-static int compress_on_slot(Backend* b, DeviceSlot* s, const CompressJob& job, Progress* progress)
+static int compress_pipeline(Backend* b, DeviceSlot* s, hipStream_t stream, const CompressJob& job, Progress* progress);
+
+/* The blocks of `job` on slot `s` (a body of run_locked).  Returns 0 ok, 1 out of memory, 2 device failure. */
+static int compress_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const CompressJob& job, Progress* progress)
 {
-	std::lock_guard<std::mutex> busy(s->busy);
-	HIP_TRY(hipSetDevice(s->device), return 2);
-	const int rc = compress_on_slot_locked(b, s, job, progress);
+	const int rc = compress_pipeline(b, s, stream, job, progress);
 	if (rc != 0)
 	{
 		// A failed call may leave asynchronous copies of the banded pipeline in flight that read or write the pinned
@@ -841,40 +879,27 @@ static int compress_on_slot(Backend* b, DeviceSlot* s, const CompressJob& job, P
 	return rc;
 }
 
-static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob& job, Progress* progress)
+static int compress_pipeline(Backend* b, DeviceSlot* s, hipStream_t stream, const CompressJob& job, Progress* progress)
 {
-
-	const uint32_t bsx = b->root.dim_x, bsy = b->root.dim_y, bsz = b->root.dim_z;
-	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const uint32_t blocks_x = (job.dim_x + bsx - 1) / bsx;
-	const uint32_t blocks_y = (job.dim_y + bsy - 1) / bsy;
-	const uint32_t blocks_z = (dim_z + bsz - 1) / bsz;
-	const size_t nblocks = (size_t)blocks_x * blocks_y * blocks_z;
+	const BlockGrid grid = block_grid(b->root, job);
+	const uint32_t bsy = b->root.dim_y, dim_z = grid.dim_z, blocks_x = grid.x, blocks_y = grid.y;
+	const size_t nblocks = grid.count();
 	jit_count_blocks(b, s, nblocks);
-	const size_t texel_bytes = job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16;
+	const size_t row_bytes = (size_t)job.dim_x * texel_bytes(job.data_type);
 	// (a shard of the alpha-scale split carries halo rows around its own: they are uploaded and averaged, not compressed)
 	const uint32_t halo_above = dim_z == 1 && job.a_scale_radius != 0 ? job.halo_above : 0u;
 	const uint32_t halo_below = dim_z == 1 && job.a_scale_radius != 0 ? job.halo_below : 0u;
 	const uint32_t rows_with_halo = job.dim_y + halo_above + halo_below;
-	const size_t slice_bytes = (size_t)job.dim_x * rows_with_halo * texel_bytes;
+	const size_t slice_bytes = rows_with_halo * row_bytes;
 	const size_t image_bytes = slice_bytes * dim_z;
 	const size_t out_bytes = nblocks * 16;
-
-	hipStream_t stream;
-	if (!pick_stream(s, job.stream, &stream)) return 3;
 
 	const void* d_image = job.device_data;
 	uint8_t* d_out = job.device_out;
 
 	if (job.host_slices)
 	{
-		if (s->image_cap < image_bytes)
-		{
-			if (s->d_image) (void)hipFree(s->d_image);
-			s->d_image = nullptr; s->image_cap = 0;
-			HIP_TRY(hipMalloc(&s->d_image, image_bytes + ALLOC_SLACK), return 1);
-			s->image_cap = image_bytes;
-		}
+		if (grow(s->d_image, s->image_cap, image_bytes) != 0) return 1;
 		d_image = s->d_image;
 	}
 	// Host-pointer calls on a plain 2D image are pipelined by bands of block rows: band k+1 travels over
@@ -889,28 +914,15 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 	}
 	if (job.host_out)
 	{
-		if (s->out_cap < out_bytes)
-		{
-			if (s->d_out) (void)hipFree(s->d_out);
-			s->d_out = nullptr; s->out_cap = 0;
-			HIP_TRY(hipMalloc(&s->d_out, out_bytes + ALLOC_SLACK), return 1);
-			s->out_cap = out_bytes;
-		}
+		if (grow(s->d_out, s->out_cap, out_bytes) != 0) return 1;
 		d_out = s->d_out;
 	}
 	if (!d_image || !d_out) return 2;
 
-	ImageDesc img = image_desc(b, job, static_cast<const uint8_t*>(d_image) + (size_t)halo_above * job.dim_x * texel_bytes);
+	ImageDesc img = image_desc(b->root, b->cfg.profile, job, static_cast<const uint8_t*>(d_image) + halo_above * row_bytes);
 	if (job.a_scale_radius != 0)
 	{
-		const size_t need = (size_t)job.dim_x * rows_with_halo * sizeof(float);
-		if (s->alpha_cap < need)
-		{
-			if (s->d_alpha) (void)hipFree(s->d_alpha);
-			s->d_alpha = nullptr; s->alpha_cap = 0;
-			HIP_TRY(hipMalloc(&s->d_alpha, need + ALLOC_SLACK), return 1);
-			s->alpha_cap = need;
-		}
+		if (grow(s->d_alpha, s->alpha_cap, (size_t)job.dim_x * rows_with_halo * sizeof(float)) != 0) return 1;
 		const int arc = alpha_prepass(s, stream, d_image, s->d_alpha, job.dim_x, rows_with_halo, dim_z, job.data_type, job.swz[3], job.a_scale_radius);
 		if (arc != 0) return arc;
 		img.alpha_avg = s->d_alpha + (size_t)halo_above * job.dim_x;
@@ -931,7 +943,6 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 		if (rows < 1) rows = 1;
 		chunk = rows * blocks_x;
 	}
-	const size_t row_bytes = (size_t)job.dim_x * texel_bytes;
 	if (banded)
 	{
 		// Pinned staging: a copy from or to the caller's pageable memory would hold the host thread until it is done (and the
@@ -939,21 +950,7 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 		// copies a band into a pinned buffer (two of them: band k+1 is staged while band k's transfer is in flight) and the
 		// blocks come back through pinned buffers as well; every transfer is then a true asynchronous DMA.
 		const size_t band_rows = (chunk / blocks_x) * bsy;
-		const size_t in_need = band_rows * row_bytes, out_need = chunk * 16;
-		if (s->h_in_cap < in_need)
-		{
-			for (int i = 0; i < 2; i++) { if (s->h_in[i]) (void)hipHostFree(s->h_in[i]); s->h_in[i] = nullptr; }
-			s->h_in_cap = 0;
-			for (int i = 0; i < 2; i++) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_in[i]), in_need, hipHostMallocDefault), return 1);
-			s->h_in_cap = in_need;
-		}
-		if (s->h_out_cap < out_need)
-		{
-			for (int i = 0; i < 2; i++) { if (s->h_out[i]) (void)hipHostFree(s->h_out[i]); s->h_out[i] = nullptr; }
-			s->h_out_cap = 0;
-			for (int i = 0; i < 2; i++) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_out[i]), out_need, hipHostMallocDefault), return 1);
-			s->h_out_cap = out_need;
-		}
+		if (grow_pinned(s->h_in, s->h_in_cap, band_rows * row_bytes) != 0 || grow_pinned(s->h_out, s->h_out_cap, chunk * 16) != 0) return 1;
 	}
 	auto upload_band = [&](size_t band_first, size_t band_blocks) -> int {
 		const size_t band = band_first / chunk;
@@ -979,13 +976,7 @@ static int compress_on_slot_locked(Backend* b, DeviceSlot* s, const CompressJob&
 	{
 		// debug build: one trace slice per block, dumped to $ASTCENC_AMD_TRACE_FILE after the call (wave_ctx.h: TRACE_PUT)
 		const size_t need = nblocks * TRACE_WORDS_PER_BLOCK_HOST * sizeof(uint32_t);
-		if (s->trace_cap < need)
-		{
-			if (s->d_prof) (void)hipFree(s->d_prof);
-			s->d_prof = nullptr; s->trace_cap = 0;
-			HIP_TRY(hipMalloc(&s->d_prof, need), return 1);
-			s->trace_cap = need;
-		}
+		if (grow(s->d_prof, s->trace_cap, need) != 0) return 1;
 		HIP_TRY(hipMemsetAsync(s->d_prof, 0, need, stream), return 2);
 	}
 #endif
@@ -1073,25 +1064,121 @@ constexpr size_t DEAL_PORTIONS_PER_DEVICE = 4;
  * first band crosses before anything is compressed -- which eight portions of 16 k blocks pay for visibly (profiles/r06z). */
 constexpr size_t MIN_BLOCKS_PER_PORTION = 4 * MIN_BLOCKS_PER_DEVICE;
 
+/* A 2D image is cut into block rows, a volume / stack of slices into layers of blocks. */
+static uint32_t shard_units(const BlockGrid& grid) { return grid.dim_z == 1 ? grid.y : grid.z; }
+
+/* How many of the context's devices a host image is shared out to. */
+static size_t devices_for(const Backend* b, const BlockGrid& grid)
+{
+	size_t ndev = b->slots.size();
+	const size_t by_size = grid.count() / MIN_BLOCKS_PER_DEVICE;
+	if (ndev > by_size) ndev = by_size < 1 ? 1 : by_size;
+	if (ndev > shard_units(grid)) ndev = shard_units(grid);
+	return ndev;
+}
+
+static const void* advance(const void* p, size_t bytes) { return static_cast<const uint8_t*>(p) + bytes; }
+static void* advance(void* p, size_t bytes) { return static_cast<uint8_t*>(p) + bytes; }
+
+/* A contiguous range of a host image: whole block rows of a 2D image or whole block layers of a volume, blocks
+ * [first_block, first_block + blocks) of the image.  `job` is the image's job cut down to the range (host_slices = slices, dim_y
+ * or dim_z its own); the caller points it at the range's blocks. */
+template <class Job> struct Shard {
+	Job job;
+	std::vector<std::decay_t<decltype(*std::declval<Job&>().host_slices)>> slices;   // (const void* / void*)
+	uint32_t first_row;                // 2D: the range's first texel row
+	size_t first_block, blocks;
+};
+
+/* The host image of `job` cut into at most `count` ranges of equal size (the last one shorter). */
+template <class Job> static std::vector<Shard<Job>> cut_shards(const Backend* b, const BlockGrid& grid, const Job& job, size_t count)
+{
+	const uint32_t units = shard_units(grid), units_per = (uint32_t)((units + count - 1) / count);
+	const size_t unit_blocks = grid.dim_z == 1 ? (size_t)grid.x : (size_t)grid.x * grid.y;
+	const size_t row_bytes = (size_t)job.dim_x * texel_bytes(job.data_type);
+	std::vector<Shard<Job>> shards;
+	for (uint32_t u0 = 0; u0 < units; u0 += units_per)
+	{
+		const uint32_t u1 = u0 + units_per < units ? u0 + units_per : units;
+		Shard<Job> sh;
+		sh.job = job;
+		sh.first_row = 0;
+		sh.first_block = u0 * unit_blocks;
+		sh.blocks = (u1 - u0) * unit_blocks;
+		if (grid.dim_z == 1)
+		{
+			const uint32_t y0 = u0 * b->root.dim_y;
+			const uint32_t y1 = u1 * b->root.dim_y < job.dim_y ? u1 * b->root.dim_y : job.dim_y;
+			sh.first_row = y0;
+			sh.slices.push_back(advance(job.host_slices[0], y0 * row_bytes));
+			sh.job.dim_y = y1 - y0;
+		}
+		else
+		{
+			const uint32_t z0 = u0 * b->root.dim_z;
+			const uint32_t z1 = u1 * b->root.dim_z < grid.dim_z ? u1 * b->root.dim_z : grid.dim_z;
+			sh.slices.assign(job.host_slices + z0, job.host_slices + z1);
+			sh.job.dim_z = z1 - z0;
+		}
+		shards.push_back(std::move(sh));
+	}
+	for (Shard<Job>& sh : shards) sh.job.host_slices = sh.slices.data();      // (after the vector stopped growing)
+	return shards;
+}
+
+/* Runs portions 0 .. count - 1 of a host image as run(slot, portion) on the first `ndev` slots.  The portions are DEALT, not
+ * pre-assigned: the calling thread drives slot 0, the parked thread of every further slot drives that one, and each takes the next
+ * portion from one counter when it has finished its last.  A slot whose thread is busy with another call on the context or cannot
+ * be had (std::system_error must not cross the C ABI, and the earlier workers must still be joined) takes no portions: the others
+ * deal its share out.  A failed portion fails the call -- nobody starts another --; the first failure is returned, out of memory
+ * before any other.  log_as: the name in the per-slot log line, or null for none. */
+static int deal_portions(Backend* b, size_t ndev, size_t count, const std::function<int(DeviceSlot*, size_t)>& run, const char* log_as)
+{
+	std::vector<int> rcs(count, 0);
+	std::atomic<size_t> next_portion{0};
+	std::atomic<bool> failed{false};
+	const size_t nslots = ndev < count ? ndev : count;
+	std::vector<double> busy_ms(nslots, 0.0);
+	std::vector<unsigned> taken(nslots, 0u);
+	auto deal = [&](size_t g)
+	{
+		const auto t0 = std::chrono::steady_clock::now();
+		for (;;)
+		{
+			if (failed.load()) break;
+			const size_t p = next_portion.fetch_add(1);
+			if (p >= count) break;
+			rcs[p] = run(b->slots[g], p);
+			if (rcs[p] != 0) failed.store(true);
+			taken[g]++;
+		}
+		busy_ms[g] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	};
+	std::vector<size_t> on_workers;
+	for (size_t g = 1; g < nslots; g++)
+	{
+		// (building the task may allocate: nothing may be thrown across the C ABI -- ADVICE r05)
+		try { if (worker_run(b->slots[g], [&deal, g]() { deal(g); })) on_workers.push_back(g); }
+		catch (...) { }
+	}
+	deal(0);
+	for (size_t g : on_workers) worker_wait(b->slots[g]);
+	if (log_as)
+		for (size_t g = 0; g < nslots; g++) log_msg("%s: device slot %zu took %u of %zu portions, busy %.2f ms", log_as, g, taken[g], count, busy_ms[g]);
+	int rc = 0;
+	for (int r : rcs) if (r != 0 && (rc == 0 || r == 1)) rc = r;
+	return rc;
+}
+
 int backend_compress(Backend* b, const CompressJob& job)
 {
-	DeviceGuard guard;
+	const BlockGrid grid = block_grid(b->root, job);
 	Progress progress;
-	progress.done = 0; progress.callback = job.progress;
-	{
-		const uint32_t bsx = b->root.dim_x, bsy = b->root.dim_y, bsz = b->root.dim_z;
-		const uint32_t dz = job.dim_z ? job.dim_z : 1u;
-		progress.total = (size_t)((job.dim_x + bsx - 1) / bsx) * ((job.dim_y + bsy - 1) / bsy) * ((dz + bsz - 1) / bsz);
-	}
+	progress.done = 0; progress.callback = job.progress; progress.total = grid.count();
 
 	// Buffers that already live on a device are compressed there.
 	if (!job.host_slices)
-	{
-		int st = 0;
-		DeviceSlot* s = slot_for_pointer(b, job.device_data, &st);
-		if (!s) return st ? st : 2;
-		return compress_on_slot(b, s, job, &progress);
-	}
+		return run_on_owner(b, job.device_data, nullptr, 0, job.stream, [&](DeviceSlot* s, hipStream_t stream) { return compress_on_slot(b, s, stream, job, &progress); });
 
 	// Host images: contiguous ranges of block rows (2D) or of block layers (volumes, stacks of slices), one per device,
 	// each running its own pipeline on its own streams from its own host thread; the caller's thread takes the first
@@ -1100,25 +1187,18 @@ int backend_compress(Backend* b, const CompressJob& job)
 	// worker threads, astcenc_entry.cpp:1190-1211, astcenc_compute_variance.cpp:507) a shard also takes the texel rows its
 	// averages reach into: enough rows above and below for every 32 x 32 tile of the pre-pass that touches the shard to
 	// see exactly the texels it sees in the whole image -- same tiles, same summed-area arithmetic, same floats.
-	const uint32_t bsy = b->root.dim_y, bsz = b->root.dim_z;
-	const uint32_t blocks_x = (job.dim_x + b->root.dim_x - 1) / b->root.dim_x;
-	const uint32_t blocks_y = (job.dim_y + bsy - 1) / bsy;
-	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const uint32_t blocks_z = (dim_z + bsz - 1) / bsz;
-	size_t ndev = b->slots.size();
+	DeviceGuard guard;
+	auto on_slot = [b, &progress](DeviceSlot* slot, const CompressJob& j)
+	{
+		return run_locked(slot, j.stream, [&](DeviceSlot* s, hipStream_t stream) { return compress_on_slot(b, s, stream, j, &progress); });
+	};
 	// (a stack of slices with the alpha-scale pre-pass averages around slice 0 for the whole stack: one device)
-	if ((job.a_scale_radius != 0 && dim_z > 1) || !job.host_out) ndev = 1;
-	const size_t by_size = progress.total / MIN_BLOCKS_PER_DEVICE;
-	if (ndev > by_size) ndev = by_size < 1 ? 1 : by_size;
-	// a 2D image is cut into block rows, a volume / stack of slices into layers of blocks
-	const uint32_t units = dim_z == 1 ? blocks_y : blocks_z;
-	if (ndev > units) ndev = units;
+	size_t ndev = (job.a_scale_radius != 0 && grid.dim_z > 1) || !job.host_out ? 1 : devices_for(b, grid);
 #if defined(ASTC_TRACE)
 	ndev = 1;      // (debug build: every shard would write the same trace file)
 #endif
-	if (ndev <= 1) return compress_on_slot(b, b->slots[0], job, &progress);
+	if (ndev <= 1) return on_slot(b->slots[0], job);
 
-	const size_t texel_bytes = job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16;
 	// The units are DEALT, not pre-assigned (ref: the reference's workers take blocks from one atomic ticket counter, 16 at a
 	// time, astcenc_internal_entry.h:225-236 / astcenc_entry.cpp:959 -- a worker that lands on cheap content takes more):
 	// block cost depends on content (a photograph runs three times faster per texel than noise), so with one contiguous range
@@ -1135,283 +1215,110 @@ int backend_compress(Backend* b, const CompressJob& job)
 			// (ASTCENC_AMD_DEAL_MIN_BLOCKS: a smaller minimum, for tests/test_multi_device.py -- many portions on a small image)
 			size_t min_portion = MIN_BLOCKS_PER_PORTION;
 			if (const char* e = getenv("ASTCENC_AMD_DEAL_MIN_BLOCKS")) { const long v = strtol(e, nullptr, 10); if (v >= 1) min_portion = (size_t)v; }
-			const size_t by_portion_size = progress.total / min_portion;
+			const size_t by_portion_size = grid.count() / min_portion;
 			if (nportions > by_portion_size) nportions = by_portion_size;
-			if (nportions > units) nportions = units;
+			if (nportions > shard_units(grid)) nportions = shard_units(grid);
 			if (nportions < ndev) nportions = ndev;
 		}
 	}
-	const uint32_t units_per = (uint32_t)((units + nportions - 1) / nportions);
-	struct Shard { CompressJob job; std::vector<const void*> slices; int rc; };
-	std::vector<Shard> shards;
+	std::vector<Shard<CompressJob>> shards = cut_shards(b, grid, job, nportions);
 	// The reference's fast loader reads slice 0 whatever the block's z (CompressJob::fast_load_slice0): a shard that
 	// starts further up the stack must then see the image's first slice as its own first slice.
-	const bool needs_swz = job.swz[0] != 0 || job.swz[1] != 1 || job.swz[2] != 2 || job.swz[3] != 3;
-	const bool slice0_quirk = dim_z > 1 && job.fast_load_slice0 && !needs_swz && b->cfg.profile < 2 && job.data_type == 0 && bsz == 1;
-	for (size_t g = 0; g < nportions; g++)
+	const bool slice0_quirk = grid.dim_z > 1 && job.fast_load_slice0 && uses_fast_load(b->root, b->cfg.profile, job);
+	for (Shard<CompressJob>& sh : shards)
 	{
-		const uint32_t u0 = (uint32_t)g * units_per;
-		if (u0 >= units) break;
-		const uint32_t u1 = u0 + units_per < units ? u0 + units_per : units;
-		Shard sh;
-		sh.job = job;
 		sh.job.progress = nullptr;
-		sh.rc = 0;
-		if (dim_z == 1)
+		sh.job.host_out = job.host_out + sh.first_block * 16;
+		if (slice0_quirk) for (const void*& slice : sh.slices) slice = job.host_slices[0];
+		if (grid.dim_z == 1 && job.a_scale_radius != 0)
 		{
-			const uint32_t y0 = u0 * bsy;
-			const uint32_t y1 = u1 * bsy < job.dim_y ? u1 * bsy : job.dim_y;
-			uint32_t first_row = y0;
-			if (job.a_scale_radius != 0)
-			{
-				// tiles of the pre-pass start at multiples of ALPHA_TILE from the image origin; a tile's summed-area table
-				// takes in radius + 1 rows above its first row and radius rows below its last
-				const uint32_t tile = ALPHA_TILE_ROWS_2D, r = job.a_scale_radius;
-				const uint32_t tile_top = y0 / tile * tile, tile_bottom = (y1 + tile - 1) / tile * tile;
-				const uint32_t want_top = tile_top > r + 1 ? (tile_top - (r + 1)) / tile * tile : 0u;
-				const uint64_t want_bottom = (uint64_t)tile_bottom + r + 1;
-				first_row = want_top;
-				const uint32_t last_row = want_bottom < job.dim_y ? (uint32_t)want_bottom : job.dim_y;
-				sh.job.halo_above = y0 - first_row;
-				sh.job.halo_below = last_row - y1;
-			}
-			sh.slices.push_back(static_cast<const uint8_t*>(job.host_slices[0]) + (size_t)first_row * job.dim_x * texel_bytes);
-			sh.job.dim_y = y1 - y0;
-			sh.job.host_out = job.host_out + (size_t)u0 * blocks_x * 16;
+			// tiles of the pre-pass start at multiples of ALPHA_TILE from the image origin; a tile's summed-area table
+			// takes in radius + 1 rows above its first row and radius rows below its last
+			const uint32_t y0 = sh.first_row, y1 = y0 + sh.job.dim_y;
+			const uint32_t tile = ALPHA_TILE_ROWS_2D, r = job.a_scale_radius;
+			const uint32_t tile_top = y0 / tile * tile, tile_bottom = (y1 + tile - 1) / tile * tile;
+			const uint32_t want_top = tile_top > r + 1 ? (tile_top - (r + 1)) / tile * tile : 0u;
+			const uint64_t want_bottom = (uint64_t)tile_bottom + r + 1;
+			const uint32_t last_row = want_bottom < job.dim_y ? (uint32_t)want_bottom : job.dim_y;
+			sh.job.halo_above = y0 - want_top;
+			sh.job.halo_below = last_row - y1;
+			sh.slices[0] = advance(job.host_slices[0], (size_t)want_top * job.dim_x * texel_bytes(job.data_type));
 		}
-		else
-		{
-			const uint32_t z0 = u0 * bsz;
-			const uint32_t z1 = u1 * bsz < dim_z ? u1 * bsz : dim_z;
-			for (uint32_t z = z0; z < z1; z++) sh.slices.push_back(slice0_quirk ? job.host_slices[0] : job.host_slices[z]);
-			sh.job.dim_z = z1 - z0;
-			sh.job.host_out = job.host_out + (size_t)u0 * blocks_x * blocks_y * 16;
-		}
-		shards.push_back(std::move(sh));
 	}
-	for (Shard& sh : shards) sh.job.host_slices = sh.slices.data();      // (after the vector stopped growing)
-	// one host thread per further device; a device whose thread cannot be created (std::system_error must not cross the
-	// C ABI, and the earlier workers must still be joined) simply takes no portions: the others deal its share out
-	std::atomic<size_t> next_portion{0};
-	std::atomic<bool> failed{false};
-	const size_t nslots = ndev < shards.size() ? ndev : shards.size();
-	std::vector<double> busy_ms(nslots, 0.0);
-	std::vector<unsigned> taken(nslots, 0u);
-	auto deal = [&](size_t g)
-	{
-		const auto t0 = std::chrono::steady_clock::now();
-		for (;;)
-		{
-			if (failed.load()) break;                          // (a failed portion fails the call: nobody starts another)
-			const size_t p = next_portion.fetch_add(1);
-			if (p >= shards.size()) break;
-			shards[p].rc = compress_on_slot(b, b->slots[g], shards[p].job, &progress);
-			if (shards[p].rc != 0) failed.store(true);
-			taken[g]++;
-		}
-		busy_ms[g] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	};
-	std::vector<size_t> on_workers;
-	for (size_t g = 1; g < nslots; g++)
-	{
-		// (building the task may allocate: nothing may be thrown across the C ABI -- ADVICE r05)
-		try { if (worker_run(b->slots[g], [&deal, g]() { deal(g); })) on_workers.push_back(g); }
-		catch (...) { }
-	}
-	deal(0);
-	for (size_t g : on_workers) worker_wait(b->slots[g]);
-	for (size_t g = 0; g < nslots; g++) log_msg("compress: device slot %zu took %u of %zu portions, busy %.2f ms", g, taken[g], shards.size(), busy_ms[g]);
-	int rc = 0;
-	for (const Shard& sh : shards) if (sh.rc != 0 && (rc == 0 || sh.rc == 1)) rc = sh.rc;
-	return rc;
+	return deal_portions(b, ndev, shards.size(), [&](DeviceSlot* s, size_t p) { return on_slot(s, shards[p].job); }, "compress");
 }
 
-/* The blocks of `job` decoded on one slot. */
-static int decompress_on_slot(Backend* bk, DeviceSlot* b, const DecompressJob& job)
+/* The blocks of `job` decoded on slot `s` (a body of run_locked). */
+static int decompress_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const DecompressJob& job)
 {
-	std::lock_guard<std::mutex> busy(b->busy);
-	HIP_TRY(hipSetDevice(b->device), return 2);
-	const size_t texel_bytes = job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16;
 	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * texel_bytes;
-	const size_t image_bytes = slice_bytes * dim_z;
-
+	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * texel_bytes(job.data_type);
 	// the staging buffers of the compress path are reused the other way round
-	if (b->image_cap < image_bytes)
-	{
-		if (b->d_image) (void)hipFree(b->d_image);
-		b->d_image = nullptr; b->image_cap = 0;
-		HIP_TRY(hipMalloc(&b->d_image, image_bytes + ALLOC_SLACK), return 1);
-		b->image_cap = image_bytes;
-	}
-	if (b->out_cap < job.block_bytes)
-	{
-		if (b->d_out) (void)hipFree(b->d_out);
-		b->d_out = nullptr; b->out_cap = 0;
-		HIP_TRY(hipMalloc(&b->d_out, job.block_bytes + ALLOC_SLACK), return 1);
-		b->out_cap = job.block_bytes;
-	}
-	HIP_TRY(hipMemcpyAsync(b->d_out, job.host_blocks, job.block_bytes, hipMemcpyHostToDevice, b->stream), return 2);
-
-	DecodeLaunch d;
-	d.d_blocks = b->d_out;
-	d.d_image = b->d_image;
-	d.d_tables = b->d_dectab;
-	d.dim_x = job.dim_x; d.dim_y = job.dim_y; d.dim_z = dim_z; d.data_type = job.data_type;
-	for (int i = 0; i < 4; i++) d.swz[i] = job.swz[i];
-	d.block_x = bk->root.dim_x; d.block_y = bk->root.dim_y; d.block_z = bk->root.dim_z;
-	d.profile = bk->cfg.profile;
-	d.stream = b->stream;
-	int lrc = astc_decode_launch(d);
+	if (grow(s->d_image, s->image_cap, slice_bytes * dim_z) != 0 || grow(s->d_out, s->out_cap, job.block_bytes) != 0) return 1;
+	HIP_TRY(hipMemcpyAsync(s->d_out, job.host_blocks, job.block_bytes, hipMemcpyHostToDevice, stream), return 2);
+	int lrc = astc_decode_launch(decode_launch(b, s, job, s->d_out, s->d_image, stream));
 	if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
 	for (uint32_t z = 0; z < dim_z; z++)
-		HIP_TRY(hipMemcpyAsync(job.host_slices[z], static_cast<uint8_t*>(b->d_image) + z * slice_bytes, slice_bytes, hipMemcpyDeviceToHost, b->stream), return 2);
-	HIP_TRY(hipStreamSynchronize(b->stream), return 2);
+		HIP_TRY(hipMemcpyAsync(job.host_slices[z], static_cast<uint8_t*>(s->d_image) + z * slice_bytes, slice_bytes, hipMemcpyDeviceToHost, stream), return 2);
+	HIP_TRY(hipStreamSynchronize(stream), return 2);
 	return 0;
 }
 
 /* Host blocks -> host image.  Like compression the work is dealt to the context's devices in contiguous ranges --
  * block rows of a 2D image, layers of blocks of a volume -- each decoded into its own rows / slices of the caller's
- * image (ref: the block loop of astcenc_decompress_image, astcenc_entry.cpp:1340-1385: blocks are independent). */
-int backend_decompress(Backend* bk, const DecompressJob& job)
+ * image (ref: the block loop of astcenc_decompress_image, astcenc_entry.cpp:1340-1385: blocks are independent), one
+ * portion per device. */
+int backend_decompress(Backend* b, const DecompressJob& job)
 {
 	DeviceGuard guard;
-	const uint32_t bsx = bk->root.dim_x, bsy = bk->root.dim_y, bsz = bk->root.dim_z;
-	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const uint32_t blocks_x = (job.dim_x + bsx - 1) / bsx, blocks_y = (job.dim_y + bsy - 1) / bsy, blocks_z = (dim_z + bsz - 1) / bsz;
-	const size_t total = (size_t)blocks_x * blocks_y * blocks_z;
-	size_t ndev = bk->slots.size();
-	const size_t by_size = total / MIN_BLOCKS_PER_DEVICE;
-	if (ndev > by_size) ndev = by_size < 1 ? 1 : by_size;
-	const uint32_t units = dim_z == 1 ? blocks_y : blocks_z;
-	if (ndev > units) ndev = units;
-	if (ndev <= 1) return decompress_on_slot(bk, bk->slots[0], job);
-
-	const size_t texel_bytes = job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16;
-	const uint32_t units_per = (uint32_t)((units + ndev - 1) / ndev);
-	struct Shard { DecompressJob job; std::vector<void*> slices; int rc; };
-	std::vector<Shard> shards;
-	for (size_t g = 0; g < ndev; g++)
+	const BlockGrid grid = block_grid(b->root, job);
+	auto on_slot = [b](DeviceSlot* slot, const DecompressJob& j)
 	{
-		const uint32_t u0 = (uint32_t)g * units_per;
-		if (u0 >= units) break;
-		const uint32_t u1 = u0 + units_per < units ? u0 + units_per : units;
-		Shard sh;
-		sh.job = job;
-		sh.rc = 0;
-		if (dim_z == 1)
-		{
-			const uint32_t y0 = u0 * bsy;
-			const uint32_t y1 = u1 * bsy < job.dim_y ? u1 * bsy : job.dim_y;
-			sh.slices.push_back(static_cast<uint8_t*>(job.host_slices[0]) + (size_t)y0 * job.dim_x * texel_bytes);
-			sh.job.dim_y = y1 - y0;
-			sh.job.host_blocks = job.host_blocks + (size_t)u0 * blocks_x * 16;
-			sh.job.block_bytes = (size_t)(u1 - u0) * blocks_x * 16;
-		}
-		else
-		{
-			const uint32_t z0 = u0 * bsz;
-			const uint32_t z1 = u1 * bsz < dim_z ? u1 * bsz : dim_z;
-			for (uint32_t z = z0; z < z1; z++) sh.slices.push_back(job.host_slices[z]);
-			sh.job.dim_z = z1 - z0;
-			sh.job.host_blocks = job.host_blocks + (size_t)u0 * blocks_x * blocks_y * 16;
-			sh.job.block_bytes = (size_t)(u1 - u0) * blocks_x * blocks_y * 16;
-		}
-		shards.push_back(std::move(sh));
-	}
-	for (Shard& sh : shards) sh.job.host_slices = sh.slices.data();
-	std::vector<size_t> on_workers, inline_shards;
-	for (size_t g = 1; g < shards.size(); g++)
+		return run_locked(slot, nullptr, [&](DeviceSlot* s, hipStream_t stream) { return decompress_on_slot(b, s, stream, j); });
+	};
+	const size_t ndev = devices_for(b, grid);
+	if (ndev <= 1) return on_slot(b->slots[0], job);
+	std::vector<Shard<DecompressJob>> shards = cut_shards(b, grid, job, ndev);
+	for (Shard<DecompressJob>& sh : shards)
 	{
-		bool handed = false;
-		try { handed = worker_run(bk->slots[g], [&shards, bk, g]() { shards[g].rc = decompress_on_slot(bk, bk->slots[g], shards[g].job); }); }
-		catch (...) { }                                     // (building the task may allocate: nothing is thrown across the C ABI)
-		if (handed) on_workers.push_back(g);
-		else inline_shards.push_back(g);
+		sh.job.host_blocks = job.host_blocks + sh.first_block * 16;
+		sh.job.block_bytes = sh.blocks * 16;
 	}
-	shards[0].rc = decompress_on_slot(bk, bk->slots[0], shards[0].job);
-	for (size_t g : inline_shards) shards[g].rc = decompress_on_slot(bk, bk->slots[g], shards[g].job);
-	for (size_t g : on_workers) worker_wait(bk->slots[g]);
-	int rc = 0;
-	for (const Shard& sh : shards) if (sh.rc != 0 && (rc == 0 || sh.rc == 1)) rc = sh.rc;
-	return rc;
+	return deal_portions(b, ndev, shards.size(), [&](DeviceSlot* s, size_t p) { return on_slot(s, shards[p].job); }, nullptr);
 }
 
-int backend_decompress_device(Backend* bk, const DecompressDeviceJob& job)
+int backend_decompress_device(Backend* b, const DecompressDeviceJob& job)
 {
-	DeviceGuard guard;
-	int st = 0;
-	DeviceSlot* b = slot_for_pointer(bk, job.device_image, &st);
-	if (!b) return st ? st : 2;
-	std::lock_guard<std::mutex> busy(b->busy);
-	HIP_TRY(hipSetDevice(b->device), return 2);
-	hipStream_t stream;
-	if (!pick_stream(b, job.stream, &stream)) return 3;
-	DecodeLaunch d;
-	d.d_blocks = job.device_blocks;
-	d.d_image = job.device_image;
-	d.d_tables = b->d_dectab;
-	d.dim_x = job.dim_x; d.dim_y = job.dim_y; d.dim_z = job.dim_z ? job.dim_z : 1u; d.data_type = job.data_type;
-	for (int i = 0; i < 4; i++) d.swz[i] = job.swz[i];
-	d.block_x = bk->root.dim_x; d.block_y = bk->root.dim_y; d.block_z = bk->root.dim_z;
-	d.profile = bk->cfg.profile;
-	d.stream = stream;
-	int lrc = astc_decode_launch(d);
-	if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
-	HIP_TRY(hipStreamSynchronize(stream), return 2);
-	return 0;
-}
-
-int backend_compare(Backend* bk, const CompareJob& job)
-{
-	DeviceGuard guard;
-	int st = 0;
-	DeviceSlot* b = slot_for_pointer(bk, job.device_a, &st);
-	if (!b) return st ? st : 2;
-	std::lock_guard<std::mutex> busy(b->busy);
-	HIP_TRY(hipSetDevice(b->device), return 2);
-	hipStream_t stream;
-	if (!pick_stream(b, job.stream, &stream)) return 3;
-	if (!b->d_sums) HIP_TRY(hipMalloc(&b->d_sums, astc_compare_scratch_doubles() * sizeof(double)), return 1);
-	CompareLaunch c;
-	c.d_a = job.device_a; c.type_a = job.type_a; c.d_b = job.device_b; c.type_b = job.type_b;
-	c.texels = job.texels; c.d_sums = b->d_sums; c.stream = stream;
-	c.hdr = job.hdr; c.fstop_lo = job.fstop_lo; c.fstop_hi = job.fstop_hi;
-	int lrc = astc_compare_launch(c);
-	if (lrc != 0) { log_msg("compare kernel launch failed (hip error %d)", lrc); return 2; }
-	HIP_TRY(hipMemcpyAsync(job.sums, b->d_sums, METRIC_SUMS_HOST * sizeof(double), hipMemcpyDeviceToHost, stream), return 2);
-	HIP_TRY(hipStreamSynchronize(stream), return 2);
-	return 0;
-}
-
-/* Image sets.  Every buffer of the set must live on the device that owns entry 0's first buffer (or be unknown to the runtime,
- * which the single-image path allows as well); otherwise rc 3 and nothing is launched. */
-static bool set_on_one_device(const DeviceSlot* s, const void* const* ptrs, size_t count)
-{
-	for (size_t i = 0; i < count; i++)
+	return run_on_owner(b, job.device_image, nullptr, 0, job.stream, [&](DeviceSlot* s, hipStream_t stream)
 	{
-		hipPointerAttribute_t attr;
-		memset(&attr, 0, sizeof(attr));
-		if (!ptrs[i] || hipPointerGetAttributes(&attr, ptrs[i]) != hipSuccess) { (void)hipGetLastError(); continue; }
-		if (attr.device != s->device)
-		{
-			log_msg("image set entry %zu: a buffer of device %d, entry 0's are on device %d", i / 2, attr.device, s->device);
-			return false;
-		}
-	}
-	return true;
+		int lrc = astc_decode_launch(decode_launch(b, s, job, job.device_blocks, job.device_image, stream));
+		if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		return 0;
+	});
+}
+
+int backend_compare(Backend* b, const CompareJob& job)
+{
+	return run_on_owner(b, job.device_a, nullptr, 0, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		if (!s->d_sums) HIP_TRY(hipMalloc(&s->d_sums, astc_compare_scratch_doubles() * sizeof(double)), return 1);
+		CompareLaunch c;
+		c.d_a = job.device_a; c.type_a = job.type_a; c.d_b = job.device_b; c.type_b = job.type_b;
+		c.texels = job.texels; c.d_sums = s->d_sums; c.stream = stream;
+		c.hdr = job.hdr; c.fstop_lo = job.fstop_lo; c.fstop_hi = job.fstop_hi;
+		int lrc = astc_compare_launch(c);
+		if (lrc != 0) { log_msg("compare kernel launch failed (hip error %d)", lrc); return 2; }
+		HIP_TRY(hipMemcpyAsync(job.sums, s->d_sums, METRIC_SUMS_HOST * sizeof(double), hipMemcpyDeviceToHost, stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		return 0;
+	});
 }
 
 /* Grows the slot's table buffer to `bytes` and queues the upload of the host copy (s->h_set). */
 static int set_table_upload(DeviceSlot* s, hipStream_t stream, size_t bytes)
 {
-	if (s->set_cap < bytes)
-	{
-		if (s->d_set) (void)hipFree(s->d_set);
-		s->d_set = nullptr; s->set_cap = 0;
-		HIP_TRY(hipMalloc(&s->d_set, bytes + ALLOC_SLACK), return 1);
-		s->set_cap = bytes;
-	}
+	if (grow(s->d_set, s->set_cap, bytes) != 0) return 1;
 	HIP_TRY(hipMemcpyAsync(s->d_set, s->h_set.data(), bytes, hipMemcpyHostToDevice, stream), return 2);
 	return 0;
 }
@@ -1424,10 +1331,9 @@ static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChai
 	return 0;
 }
 
-static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& job, Progress* progress)
+/* An image set on slot `s` (a body of run_locked). */
+static int compress_set_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const CompressSetJob& job, Progress* progress)
 {
-	hipStream_t stream;
-	if (!pick_stream(s, job.stream, &stream)) return 3;
 	if (job.generate)
 	{
 		// the levels first (kernel_ms counts from here), then everything below reads them in stream order
@@ -1447,7 +1353,7 @@ static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& 
 	for (uint32_t e = 0; e < count; e++)
 	{
 		const CompressJob& en = job.entries[e];
-		rec[e].img = image_desc(b, en, en.device_data);
+		rec[e].img = image_desc(b->root, b->cfg.profile, en, en.device_data);
 		rec[e].out = en.device_out;
 		first[e] = (uint32_t)nblocks;
 		nblocks += (size_t)rec[e].img.blocks_x * rec[e].img.blocks_y * rec[e].img.blocks_z;
@@ -1465,20 +1371,12 @@ static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& 
 
 	if (alpha_floats)
 	{
-		const size_t need = alpha_floats * sizeof(float);
-		if (s->alpha_cap < need)
-		{
-			if (s->d_alpha) (void)hipFree(s->d_alpha);
-			s->d_alpha = nullptr; s->alpha_cap = 0;
-			HIP_TRY(hipMalloc(&s->d_alpha, need + ALLOC_SLACK), return 1);
-			s->alpha_cap = need;
-		}
+		if (grow(s->d_alpha, s->alpha_cap, alpha_floats * sizeof(float)) != 0) return 1;
 		for (uint32_t e = 0; e < count; e++)
 		{
 			const CompressJob& en = job.entries[e];
 			if (en.a_scale_radius == 0) continue;
-			const uint32_t dim_z = en.dim_z ? en.dim_z : 1u;
-			const int arc = alpha_prepass(s, stream, en.device_data, s->d_alpha + alpha_at[e], en.dim_x, en.dim_y, dim_z, en.data_type, en.swz[3], en.a_scale_radius);
+			const int arc = alpha_prepass(s, stream, en.device_data, s->d_alpha + alpha_at[e], en.dim_x, en.dim_y, rec[e].img.dim_z, en.data_type, en.swz[3], en.a_scale_radius);
 			if (arc != 0) return arc;
 			rec[e].img.alpha_avg = s->d_alpha + alpha_at[e];
 		}
@@ -1506,83 +1404,46 @@ static int compress_set_locked(Backend* b, DeviceSlot* s, const CompressSetJob& 
 
 int backend_compress_set(Backend* b, const CompressSetJob& job)
 {
-	DeviceGuard guard;
-	int st = 0;
-	DeviceSlot* s = slot_for_pointer(b, job.entries[0].device_data, &st);
-	if (!s) return st ? st : 2;
+	if (job.generate && job.generate->device_image != job.entries[0].device_data) return 3;
 	std::vector<const void*> ptrs;
 	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_data); ptrs.push_back(job.entries[e].device_out); }
-	if (!set_on_one_device(s, ptrs.data(), ptrs.size())) return 3;
-	if (job.generate && job.generate->device_image != job.entries[0].device_data) return 3;
 	Progress progress;
 	progress.done = 0; progress.callback = job.progress; progress.total = 0;
-	for (uint32_t e = 0; e < job.count; e++)
-	{
-		const CompressJob& en = job.entries[e];
-		const uint32_t dz = en.dim_z ? en.dim_z : 1u;
-		progress.total += (size_t)((en.dim_x + b->root.dim_x - 1) / b->root.dim_x) * ((en.dim_y + b->root.dim_y - 1) / b->root.dim_y) *
-		                  ((dz + b->root.dim_z - 1) / b->root.dim_z);
-	}
-	std::lock_guard<std::mutex> busy(s->busy);
-	HIP_TRY(hipSetDevice(s->device), return 2);
-	return compress_set_locked(b, s, job, &progress);
+	for (uint32_t e = 0; e < job.count; e++) progress.total += block_grid(b->root, job.entries[e]).count();
+	return run_on_owner(b, job.entries[0].device_data, ptrs.data(), ptrs.size(), job.stream, [&](DeviceSlot* s, hipStream_t stream) { return compress_set_on_slot(b, s, stream, job, &progress); });
 }
 
-int backend_decompress_set(Backend* bk, const DecompressSetJob& job)
+int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 {
-	DeviceGuard guard;
-	int st = 0;
-	DeviceSlot* s = slot_for_pointer(bk, job.entries[0].device_image, &st);
-	if (!s) return st ? st : 2;
 	std::vector<const void*> ptrs;
 	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_image); ptrs.push_back(job.entries[e].device_blocks); }
-	if (!set_on_one_device(s, ptrs.data(), ptrs.size())) return 3;
-	std::lock_guard<std::mutex> busy(s->busy);
-	HIP_TRY(hipSetDevice(s->device), return 2);
-	hipStream_t stream;
-	if (!pick_stream(s, job.stream, &stream)) return 3;
-	std::vector<DecodeLaunch> d(job.count);
-	for (uint32_t e = 0; e < job.count; e++)
+	return run_on_owner(b, job.entries[0].device_image, ptrs.data(), ptrs.size(), job.stream, [&](DeviceSlot* s, hipStream_t stream)
 	{
-		const DecompressDeviceJob& en = job.entries[e];
-		DecodeLaunch& x = d[e];
-		x.d_blocks = en.device_blocks;
-		x.d_image = en.device_image;
-		x.d_tables = s->d_dectab;
-		x.dim_x = en.dim_x; x.dim_y = en.dim_y; x.dim_z = en.dim_z ? en.dim_z : 1u; x.data_type = en.data_type;
-		for (int i = 0; i < 4; i++) x.swz[i] = en.swz[i];
-		x.block_x = bk->root.dim_x; x.block_y = bk->root.dim_y; x.block_z = bk->root.dim_z;
-		x.profile = bk->cfg.profile;
-		x.stream = nullptr;
-	}
-	const size_t bytes = astc_decode_set_bytes(job.count);
-	s->h_set.assign(bytes, 0);
-	const uint32_t runs = astc_decode_set_build(s->h_set.data(), d.data(), job.count);
-	const int urc = set_table_upload(s, stream, bytes);
-	if (urc != 0) return urc;
-	int lrc = astc_decode_set_launch(s->d_set, runs, stream);
-	if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
-	HIP_TRY(hipStreamSynchronize(stream), return 2);
-	return 0;
+		std::vector<DecodeLaunch> d(job.count);
+		for (uint32_t e = 0; e < job.count; e++) d[e] = decode_launch(b, s, job.entries[e], job.entries[e].device_blocks, job.entries[e].device_image, nullptr);
+		const size_t bytes = astc_decode_set_bytes(job.count);
+		s->h_set.assign(bytes, 0);
+		const uint32_t runs = astc_decode_set_build(s->h_set.data(), d.data(), job.count);
+		const int urc = set_table_upload(s, stream, bytes);
+		if (urc != 0) return urc;
+		int lrc = astc_decode_set_launch(s->d_set, runs, stream);
+		if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		return 0;
+	});
 }
 
 int backend_generate_mips(Backend* b, const MipChainJob& job)
 {
-	DeviceGuard guard;
-	int st = 0;
-	DeviceSlot* s = slot_for_pointer(b, job.device_image, &st);
-	if (!s) return st ? st : 2;
 	// (the device check of a set: the image and the levels buffer -- the one allocation every generated level lies in)
 	const void* ptrs[2] = { job.device_image, job.level_count > 1 ? job.device_levels : nullptr };
-	if (!set_on_one_device(s, ptrs, 2)) return 3;
-	std::lock_guard<std::mutex> busy(s->busy);
-	HIP_TRY(hipSetDevice(s->device), return 2);
-	hipStream_t stream;
-	if (!pick_stream(s, job.stream, &stream)) return 3;
-	const int grc = generate_mips_locked(s, stream, job);
-	if (grc != 0) return grc;
-	HIP_TRY(hipStreamSynchronize(stream), return 2);
-	return 0;
+	return run_on_owner(b, job.device_image, ptrs, 2, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		const int grc = generate_mips_locked(s, stream, job);
+		if (grc != 0) return grc;
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		return 0;
+	});
 }
 
 } // namespace astcd

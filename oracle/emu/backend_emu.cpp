@@ -141,33 +141,16 @@ int backend_compress(Backend* b, const CompressJob& job)
 	g_wave_ctx = &c;
 	g_wave_one_trip_texel_loops = root->texel_count <= 64;      // what kernel_{ldr,hdr}64.hip assume (wave.h: WV_FOR_T)
 
-	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * (job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16);
+	ImageDesc img = image_desc(*root, b->cfg.profile, job, job.host_slices ? job.host_slices[0] : job.device_data);
+	const uint32_t dim_z = img.dim_z;
+	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * texel_bytes(job.data_type);
 	std::vector<uint8_t> volume;               // the slices back to back, as the device copy has them
-	ImageDesc img;
-	img.data = job.device_data;
-	if (job.host_slices)
+	if (job.host_slices && dim_z > 1)
 	{
-		img.data = job.host_slices[0];
-		if (dim_z > 1)
-		{
-			volume.resize(slice_bytes * dim_z);
-			for (uint32_t z = 0; z < dim_z; z++) memcpy(volume.data() + z * slice_bytes, job.host_slices[z], slice_bytes);
-			img.data = volume.data();
-		}
+		volume.resize(slice_bytes * dim_z);
+		for (uint32_t z = 0; z < dim_z; z++) memcpy(volume.data() + z * slice_bytes, job.host_slices[z], slice_bytes);
+		img.data = volume.data();
 	}
-	img.dim_x = job.dim_x; img.dim_y = job.dim_y;
-	img.data_type = job.data_type;
-	for (int i = 0; i < 4; i++) img.swz[i] = job.swz[i];
-	img.blocks_x = (job.dim_x + root->dim_x - 1) / root->dim_x;
-	img.blocks_y = (job.dim_y + root->dim_y - 1) / root->dim_y;
-	img.dim_z = dim_z; img.blocks_z = (dim_z + root->dim_z - 1) / root->dim_z;
-	bool needs_swz = job.swz[0] != 0 || job.swz[1] != 1 || job.swz[2] != 2 || job.swz[3] != 3;
-	bool hdr = b->cfg.profile >= 2;
-	img.use_fast_load = (!needs_swz && !hdr && job.data_type == 0 && root->dim_z == 1) ? 1 : 0;
-	img.fast_load_slice0 = job.fast_load_slice0;
-	img.alpha_avg = nullptr;
-	img.a_scale_radius = job.a_scale_radius;
 	std::vector<float> averages;
 	if (job.a_scale_radius != 0)
 	{
@@ -219,8 +202,9 @@ int backend_compress(Backend* b, const CompressJob& job)
 int backend_decompress(Backend* b, const DecompressJob& job)
 {
 	const TableRoot* root = reinterpret_cast<const TableRoot*>(b->blob.data() + CTX_LAYOUT_BACK);
-	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * (job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16);
+	const BlockGrid grid = block_grid(*root, job);
+	const uint32_t dim_z = grid.dim_z;
+	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * texel_bytes(job.data_type);
 	std::vector<uint8_t> volume(dim_z > 1 ? slice_bytes * dim_z : 0);   // the slices back to back, as the device copy has them
 	DecodeImage img;
 	img.data = dim_z > 1 ? static_cast<void*>(volume.data()) : job.host_slices[0];
@@ -228,9 +212,7 @@ int backend_decompress(Backend* b, const DecompressJob& job)
 	img.data_type = job.data_type;
 	for (int i = 0; i < 4; i++) img.swz[i] = job.swz[i];
 	img.block_x = root->dim_x; img.block_y = root->dim_y; img.block_z = root->dim_z;
-	img.blocks_x = (job.dim_x + root->dim_x - 1) / root->dim_x;
-	img.blocks_y = (job.dim_y + root->dim_y - 1) / root->dim_y;
-	img.blocks_z = (dim_z + root->dim_z - 1) / root->dim_z;
+	img.blocks_x = grid.x; img.blocks_y = grid.y; img.blocks_z = grid.z;
 	img.profile = b->cfg.profile;
 	decode_image_prepare(img);
 	// the same batched routine the kernel runs (decode_row_batch): runs of DECODE_BATCH blocks of a block row
@@ -255,7 +237,7 @@ int backend_decompress_device(Backend* b, const DecompressDeviceJob& job)
 {
 	// "device" memory of the emulator is host memory: one contiguous volume, decode straight into it
 	const uint32_t dim_z = job.dim_z ? job.dim_z : 1u;
-	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * (job.data_type == 0 ? 4 : job.data_type == 1 ? 8 : 16);
+	const size_t slice_bytes = (size_t)job.dim_x * job.dim_y * texel_bytes(job.data_type);
 	std::vector<void*> slices(dim_z);
 	for (uint32_t z = 0; z < dim_z; z++) slices[z] = static_cast<uint8_t*>(job.device_image) + z * slice_bytes;
 	DecompressJob h;
