@@ -4,7 +4,8 @@
 // the backend then compresses (decompresses) the blocks of all entries as one range (backend_compress_set).
 // Product library only: the sequential build of oracle/emu has no backend_*_set.
 // The mip chain entry points live here too: a compressed chain is an image set of one entry per level, its generation queued
-// ahead of the set's launches (backend_compress_set with CompressSetJob::generate; the filter: mip_filter.h).
+// ahead of the set's launches (backend_compress_set with CompressSetJob::generate; the filter: mip_filter.h, the post-passes of
+// the _ex_ calls: mip_post.h).  Every mip call is one path: the calls without options pass null ones.
 #include "../../include/astcenc.h"
 #include "../../include/astcenc_amd.h"
 #include "backend.h"
@@ -227,16 +228,50 @@ static astcenc_error check_mip_volume_args(const char* fn, astcenc_context* ctx,
 	return ASTCENC_SUCCESS;
 }
 
-/* The generation and compression entry points; fn: the name of the one called, for the log. */
+/* The options of the _ex_ calls (null: none) into the job, with the constants the host derives from them (mip_post.h). */
+static astcenc_error check_mip_options(const char* fn, const astcenc_context* ctx, const astcenc_amd_mip_options* options, MipChainJob& gen)
+{
+	if (!options || options->flags == 0) return ASTCENC_SUCCESS;
+	const unsigned int known = ASTCENC_AMD_MIP_NORMALIZE | ASTCENC_AMD_MIP_ALPHA_COVERAGE;
+	if (options->flags & ~known)
+	{
+		backend_log("%s: options->flags 0x%x has unknown bits 0x%x", fn, options->flags, options->flags & ~known);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	const float cutoff = options->alpha_cutoff;
+	if ((options->flags & ASTCENC_AMD_MIP_ALPHA_COVERAGE) && !(cutoff > 0.0f && cutoff <= 1.0f))
+	{
+		backend_log("%s: options->alpha_cutoff %g is not in (0, 1]", fn, (double)cutoff);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	// (sRGB codes are not the linear components of a vector)
+	if ((options->flags & ASTCENC_AMD_MIP_NORMALIZE) && ctx->config.profile == ASTCENC_PRF_LDR_SRGB)
+	{
+		backend_log("%s: options->flags has ASTCENC_AMD_MIP_NORMALIZE in an ASTCENC_PRF_LDR_SRGB context", fn);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	gen.post_flags = options->flags;
+	if (options->flags & ASTCENC_AMD_MIP_ALPHA_COVERAGE)
+	{
+		gen.alpha_cutoff = cutoff;
+		gen.cover_t = mip_cover_u8_threshold(cutoff);
+		mip_cover_bounds(cutoff, gen.data_type == ASTCENC_TYPE_F16, gen.cover_hi, gen.cover_lo);
+	}
+	return ASTCENC_SUCCESS;
+}
+
+/* The generation and compression entry points; fn: the name of the one called, for the log; options: null for the calls
+ * without them. */
 static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
                                         unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
-                                        void* device_levels, size_t levels_len, void* hip_stream)
+                                        const astcenc_amd_mip_options* options, void* device_levels, size_t levels_len, void* hip_stream)
 {
 	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
 	MipChainJob gen;
 	astcenc_error status = check_mip_volume_args(fn, ctx, device_image, dim_x, dim_y, dim_z, kind, data_type, level_count, device_levels, levels_len,
 	                                             hip_stream, layout, gen);
+	if (status == ASTCENC_SUCCESS) status = check_mip_options(fn, ctx, options, gen);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (layout.level_count == 1) return ASTCENC_SUCCESS;
 	status = rc_to_error(backend_generate_mips(ctx->backend, gen));
@@ -246,14 +281,15 @@ static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, co
 
 static astcenc_error compress_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
                                         unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, const astcenc_swizzle* swizzle,
-                                        unsigned int level_count, void* device_levels, size_t levels_len, void* device_blocks,
-                                        size_t blocks_len, void* hip_stream, float* kernel_ms)
+                                        unsigned int level_count, const astcenc_amd_mip_options* options, void* device_levels, size_t levels_len,
+                                        void* device_blocks, size_t blocks_len, void* hip_stream, float* kernel_ms)
 {
 	if (!ctx || !swizzle) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
 	MipChainJob gen;
 	astcenc_error status = check_mip_volume_args(fn, ctx, device_image, dim_x, dim_y, dim_z, kind, data_type, level_count, device_levels, levels_len,
 	                                             hip_stream, layout, gen);
+	if (status == ASTCENC_SUCCESS) status = check_mip_options(fn, ctx, options, gen);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (!device_blocks) { backend_log("%s: device_blocks is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
 	if (blocks_len < layout.blocks_len)
@@ -283,7 +319,7 @@ astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx,
                                                            unsigned int level_count, void* device_levels, size_t levels_len, void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          level_count, device_levels, levels_len, hip_stream);
+	                          level_count, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -293,7 +329,26 @@ astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx,
                                                            float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          swizzle, level_count, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+}
+
+astcenc_error astcenc_amd_generate_mip_chain_ex_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                       unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                                       unsigned int level_count, const struct astcenc_amd_mip_options* options,
+                                                       void* device_levels, size_t levels_len, void* hip_stream)
+{
+	return generate_mip_chain("astcenc_amd_generate_mip_chain_ex_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          level_count, options, device_levels, levels_len, hip_stream);
+}
+
+astcenc_error astcenc_amd_compress_mip_chain_ex_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                                       unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                                       const astcenc_swizzle* swizzle, unsigned int level_count,
+                                                       const struct astcenc_amd_mip_options* options, void* device_levels, size_t levels_len,
+                                                       void* device_blocks, size_t blocks_len, void* hip_stream, float* kernel_ms)
+{
+	return compress_mip_chain("astcenc_amd_compress_mip_chain_ex_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          swizzle, level_count, options, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 astcenc_error astcenc_amd_mip_chain_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, astcenc_type data_type,
@@ -318,7 +373,7 @@ astcenc_error astcenc_amd_generate_mip_chain_device(astcenc_context* ctx, const 
                                                     void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
-	                          level_count, device_levels, levels_len, hip_stream);
+	                          level_count, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -327,7 +382,7 @@ astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const 
                                                     void* hip_stream, float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
-	                          swizzle, level_count, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 } // extern "C"

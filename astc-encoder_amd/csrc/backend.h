@@ -10,6 +10,7 @@
 #include "astc_tables.h"
 #include "image_set.h"
 #include "mip_filter.h"
+#include "mip_post.h"
 
 namespace astcd {
 
@@ -119,6 +120,11 @@ struct MipChainJob {
 	uint8_t* device_levels;
 	size_t texels_offset[MIP_MAX_LEVELS];
 	void* stream;
+	// the post-passes of levels 1 .. n-1 (mip_post.h, astcenc_amd_generate_mip_chain_ex_device): MIP_POST_* flags, 0 = none
+	uint32_t post_flags;
+	float alpha_cutoff;        // ALPHA_COVERAGE: the alpha test's reference value, and what the host derived from it:
+	uint32_t cover_t;          //   U8: a code is covered when >= cover_t (mip_cover_u8_threshold)
+	float cover_hi, cover_lo;  //   F16 / F32: the output type's values just at / below the cutoff (mip_cover_bounds)
 };
 
 /* ... and its decompression (astcenc_amd_decompress_images_device): every entry as a DecompressDeviceJob (stream unused). */
@@ -250,6 +256,10 @@ void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uin
 int astc_mip_launch(const MipChainJob& job, const void* d_srgb, void* stream);
 size_t astc_mip_srgb_table_bytes();
 void astc_mip_srgb_tables_build(void* out);
+/* ... and its post-passes (kernel_mip_post.hip), queued after the generation of the same job when job.post_flags != 0.
+ * d_scratch: astc_mip_post_scratch_bytes(job) bytes of device memory (0 when no scratch is needed; never above 64 MiB). */
+size_t astc_mip_post_scratch_bytes(const MipChainJob& job);
+int astc_mip_post_launch(const MipChainJob& job, void* d_scratch, void* stream);
 
 /* Image comparison launch (kernel_metrics.hip); d_sums = astc_compare_scratch_doubles() doubles of device memory,
  * the totals arrive in the first ten. */

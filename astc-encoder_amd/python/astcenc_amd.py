@@ -94,10 +94,12 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_set_log_callback", "astcenc_amd_context_specialize", "astcenc_amd_compress_images_device",
                "astcenc_amd_decompress_images_device", "astcenc_amd_mip_chain_layout", "astcenc_amd_generate_mip_chain_device",
                "astcenc_amd_compress_mip_chain_device", "astcenc_amd_mip_chain_volume_layout",
-               "astcenc_amd_generate_mip_chain_volume_device", "astcenc_amd_compress_mip_chain_volume_device"]
+               "astcenc_amd_generate_mip_chain_volume_device", "astcenc_amd_compress_mip_chain_volume_device",
+               "astcenc_amd_generate_mip_chain_ex_device", "astcenc_amd_compress_mip_chain_ex_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
+MIP_NORMALIZE, MIP_ALPHA_COVERAGE = 0x1, 0x2
 
 
 class MipChainLayout(C.Structure):
@@ -112,6 +114,11 @@ class MipChainVolumeLayout(C.Structure):
     _fields_ = [("level_count", C.c_uint), ("dim_x", C.c_uint * MAX_MIP_LEVELS), ("dim_y", C.c_uint * MAX_MIP_LEVELS),
                 ("dim_z", C.c_uint * MAX_MIP_LEVELS), ("texels_offset", C.c_size_t * MAX_MIP_LEVELS),
                 ("blocks_offset", C.c_size_t * MAX_MIP_LEVELS), ("texels_len", C.c_size_t), ("blocks_len", C.c_size_t)]
+
+
+class MipOptions(C.Structure):
+    """struct astcenc_amd_mip_options (include/astcenc_amd.h): flags = MIP_NORMALIZE | MIP_ALPHA_COVERAGE, alpha_cutoff."""
+    _fields_ = [("flags", C.c_uint), ("alpha_cutoff", C.c_float)]
 
 
 class ImageSetEntry(C.Structure):
@@ -256,6 +263,14 @@ class Library:
                                                                        C.POINTER(Swizzle), C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p,
                                                                        C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
             L.astcenc_amd_compress_mip_chain_volume_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_generate_mip_chain_ex_device"):
+            L.astcenc_amd_generate_mip_chain_ex_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                                   C.c_uint, C.POINTER(MipOptions), C.c_void_p, C.c_size_t, C.c_void_p]
+            L.astcenc_amd_generate_mip_chain_ex_device.restype = C.c_int
+            L.astcenc_amd_compress_mip_chain_ex_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                                   C.POINTER(Swizzle), C.c_uint, C.POINTER(MipOptions), C.c_void_p,
+                                                                   C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_mip_chain_ex_device.restype = C.c_int
 
     # -- thin wrappers returning error codes, as the C API does --
     def config_init(self, profile, bx, by, bz, quality, flags):
@@ -447,6 +462,39 @@ class Library:
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_compress_mip_chain_volume_device")
+        n = layout.level_count
+        ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
+        return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+
+    @staticmethod
+    def _mip_options(options):
+        """A MipOptions, a (flags, alpha_cutoff) tuple or None (null options) -> the ctypes argument."""
+        if options is None:
+            return None
+        return C.byref(options if isinstance(options, MipOptions) else MipOptions(*options))
+
+    def generate_mip_chain_ex_device(self, ctx, image, kind=MIP_VOLUME, levels=0, options=None, stream=None):
+        """astcenc_amd_generate_mip_chain_ex_device: generate_mip_chain_volume_device with mip options (see _mip_options)."""
+        (w, h, d), dtype, layout, store, tensors, _ = self._mip_chain_volume_buffers(ctx, image, kind, levels, False)
+        err = self.lib.astcenc_amd_generate_mip_chain_ex_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
+                                                                self._mip_options(options), store.data_ptr(), layout.texels_len,
+                                                                torch_stream(stream))
+        if err:
+            raise AstcError(err, "astcenc_amd_generate_mip_chain_ex_device")
+        return tensors
+
+    def compress_mip_chain_ex_device(self, ctx, image, kind=MIP_VOLUME, levels=0, options=None, swizzle=SWZ_RGBA, stream=None):
+        """astcenc_amd_compress_mip_chain_ex_device: compress_mip_chain_volume_device with mip options; returns (level tensors,
+        per-level block tensors), the kernel time of the call in self.last_kernel_ms."""
+        (w, h, d), dtype, layout, store, tensors, out = self._mip_chain_volume_buffers(ctx, image, kind, levels, True)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_mip_chain_ex_device(ctx, image.data_ptr(), w, h, d, kind, dtype, C.byref(Swizzle(*swizzle)),
+                                                                layout.level_count, self._mip_options(options), store.data_ptr(),
+                                                                layout.texels_len, out.data_ptr(), layout.blocks_len, torch_stream(stream),
+                                                                C.byref(ms))
+        self.last_kernel_ms = ms.value
+        if err:
+            raise AstcError(err, "astcenc_amd_compress_mip_chain_ex_device")
         n = layout.level_count
         ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
         return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]

@@ -124,8 +124,8 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_images_device(
  *   - F16 / F32: per y tap in increasing row, row = sum over the x taps (increasing x) of w_x * v, acc = sum over the y taps of
  *     w_y * row (each sum starting at its first product), all float64; then acc / den in float64, rounded to float32, then
  *     to F16 for F16 levels (round to nearest even both times);
- *   - channels are independent (no premultiplication, no renormalisation); the swizzle does not touch the levels, it applies
- *     when they are compressed. */
+ *   - channels are independent (no premultiplication; renormalisation and coverage: the options of the _ex_ calls below);
+ *     the swizzle does not touch the levels, it applies when they are compressed. */
 #define ASTCENC_AMD_MAX_MIP_LEVELS 32
 
 struct astcenc_amd_mip_chain_layout {
@@ -250,6 +250,73 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_volume_device(
 	enum astcenc_type data_type,
 	const struct astcenc_swizzle* swizzle,
 	unsigned int level_count,
+	void* device_levels, size_t levels_len,
+	void* device_blocks, size_t blocks_len,
+	void* hip_stream,
+	float* kernel_ms);
+
+/* Mip chain options: post-passes over the levels the calls above make.
+ *
+ * astcenc_amd_generate_mip_chain_ex_device and astcenc_amd_compress_mip_chain_ex_device take the arguments of their _volume_
+ * counterparts plus `options` after level_count.  A null `options`, or flags == 0, gives exactly the _volume_ calls' bytes
+ * (those calls, and the 2D ones, are these with null options).  Level 0, the caller's image, is never written.  The options
+ * apply to levels 1 .. n-1 after the whole chain has been generated -- level i+1 is filtered from level i as the plain filter
+ * made it -- so, level by level, levels(options) == post(levels(no options)).  The two options touch disjoint channels.  All
+ * float arithmetic is float64, each operation rounded (no fused operations), with a true division and a correctly rounded sqrt.
+ *
+ *   ASTCENC_AMD_MIP_NORMALIZE (channel 3 untouched):
+ *     1. decode channels 0-2: U8 v = (double)(2 code - 255) / 255.0; F16 / F32 v = 2.0 x - 1.0;
+ *     2. len2 = (v0 v0 + v1 v1) + v2 v2; a texel whose len2 is 0 or not finite is written unchanged (U8 never has len2 == 0);
+ *     3. n = v / sqrt(len2);
+ *     4. encode: U8 code = clamp(floor((n + 1.0) * 127.5 + 0.5), 0, 255); F32 (float)((n + 1.0) * 0.5), to nearest even; F16
+ *        the same float, then to half as the filter rounds.
+ *   ASTCENC_AMD_MIP_ALPHA_COVERAGE (channel 3):
+ *     - surfaces: one per level of a 2D image or a VOLUME, one per (level, layer) of an ARRAY (a cube face is a layer);
+ *     - a texel is covered when, U8: code >= t, t = the smallest integer in 1..255 with (double)t >= (double)alpha_cutoff * 255.0;
+ *       F16 / F32: (double)a >= (double)alpha_cutoff (NaN never);
+ *     - a level-i surface of N texels whose level-0 surface (N0 texels) has C0 covered targets k = floor((2 C0 N + N0) / (2 N0)),
+ *       computed exactly;
+ *     - a_k = the k-th largest alpha of the surface (ties count individually; floats ranked by the order-preserving map of their
+ *       bits, NaN below everything).  The surface is left unchanged when k == 0, or a_k <= 0 or not finite;
+ *     - U8: q = floor((2 a t + a_k) / (2 a_k)) in integers; the new alpha is min(255, q) if a >= a_k, else min(t - 1, q);
+ *     - F16 / F32: r = (a * alpha_cutoff) / a_k in float64, rounded to float32 (then to half for F16); a >= a_k: max(hi, min(r, 1.0)),
+ *       else min(r, lo), hi / lo being the smallest / largest value of the output type that is >= / < alpha_cutoff.  A NaN
+ *       alpha is written unchanged;
+ *     - so a texel is covered afterwards exactly when a >= a_k: the covered count is >= k, and == k when a_k is unique.
+ *
+ * The options need no caller memory: the layout calls are unchanged.  The library's own scratch for them is bounded (64 MiB,
+ * an array's layers being processed in groups); when it cannot be allocated the call returns ASTCENC_ERR_OUT_OF_MEM with
+ * nothing written.  Errors of the options, checked with the other arguments before anything is launched, return
+ * ASTCENC_ERR_BAD_PARAM with nothing written and are named "options" in the log: unknown flag bits; ALPHA_COVERAGE with an
+ * alpha_cutoff that is NaN, <= 0 or > 1; NORMALIZE in an ASTCENC_PRF_LDR_SRGB context (sRGB codes are not linear vectors).
+ * Everything else -- checks, stream order, cancel, progress, kernel_ms (which covers the post-passes) -- is the _volume_ calls'. */
+#define ASTCENC_AMD_MIP_NORMALIZE      0x1u   /* channels 0-2 hold a unit normal (x, y, z) encoded as v = (n + 1) / 2 */
+#define ASTCENC_AMD_MIP_ALPHA_COVERAGE 0x2u   /* keep channel 3's alpha-test coverage of level 0 on every level */
+struct astcenc_amd_mip_options {
+	unsigned int flags;      /* a set of the bits above; 0 = plain chain */
+	float alpha_cutoff;      /* ALPHA_COVERAGE: the alpha test's reference value, in (0, 1] */
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_generate_mip_chain_ex_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	const struct astcenc_amd_mip_options* options,
+	void* device_levels, size_t levels_len,
+	void* hip_stream);
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_ex_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	unsigned int level_count,
+	const struct astcenc_amd_mip_options* options,
 	void* device_levels, size_t levels_len,
 	void* device_blocks, size_t blocks_len,
 	void* hip_stream,
