@@ -7,6 +7,7 @@
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
   python bench.py --gpus N --single-process     one process, the library's own N-device split behind the C ABI
   ... --dump-outputs DIR                        also write the last timed step's compressed stream to DIR/*.npy
+  ... --full                                    also run the legs beside the headline (below)
 
 A "step" is one pass of the block compressor over one image per rank.  The path shards by independent
 images / block rows with no data-path collective, so N ranks compress N images: weak
@@ -14,21 +15,26 @@ scaling, value = N * texels * K / max-over-ranks time.  torch is used for device
 the rank barrier only; the work is libastcenc_amd.so called through its C ABI
 (astcenc_amd_compress_image_device).
 
-Rank 0 prints ONE JSON line with the driver's fields plus:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints: rank 0 prints ONE JSON line with
+the driver's fields plus `context` (the kernel the context launches, context creation time), `dump_outputs` and
   roofline       : algorithmic HBM bytes per launch / mean kernel time (HIP events recorded by the library on
                    the launch stream) vs the 8 TB/s HBM peak; `traffic` (HBM bytes per launch from the PMC passes) and
                    `valu` (the bound that actually binds: wave instructions per block, active lanes, and the issue rate
                    of THIS run = committed instruction count x blocks / measured kernel time, against the chip's
                    1.23e12 wave-instructions/s) come from the latest committed rocprofv3 PMC passes of the same
                    workload (profiles/*/traffic.json, named in traffic_source: rocprofv3 cannot run inside this process).
-  parity_full    : config 2 only: the WHOLE 8192^2 image through the reference's AVX2 build, every one of the
-                   1 865 956 blocks compared with the GPU's (ref: the block loop of astcenc_entry.cpp:1009-1038).
+With --full the line also carries what is measured and checked beside the headline, all of it after the timed region
+(each leg can be dropped again by its --no-* option):
   value_host_api : the same image through astcenc_compress_image (host pointers, PCIe both ways included).
+  quality        : PSNR of the output decoded by oracle/astc_decode.c, and from the product's decode and comparison
+                   kernels on the device, those two calls timed on their own.
   cpu_baseline   : the reference encoder's AVX2 build (oracle/_ref/libastcenc-avx2.so; the build with
                    ASTCENC_X86_GATHERS=1, the reference's x86 default, is timed too and the faster one reported) on this
                    box's host cores: thread-count sweep on a 2048^2 crop, best of 3 with astcenc_compress_reset in
                    between, plus the 1-thread rate, the rate per host core-second, and the host's CPU model / cgroup
                    quota / load; then a byte comparison of the crop against the GPU output.  N = 1 only.
+  parity_full    : config 2 only: the WHOLE 8192^2 image through the reference's AVX2 build, every one of the
+                   1 865 956 blocks compared with the GPU's (ref: the block loop of astcenc_entry.cpp:1009-1038).
   extra_configs  : BASELINE configs[2] (8192^2 8x8 -thorough) and configs[3] (4096^2 RGBA16F HDR 6x6 -medium):
                    kernel time, Mtexels/s, roofline, byte parity of the WHOLE stream against the reference (crop + tail if
                    a probe says that would take more than a minute of host time), and (HDR) mPSNR / log RMSE from the
@@ -70,10 +76,57 @@ CONFIGS = {
 }
 
 
-def make_image(cfg, seed):
-    if cfg["hdr"]:
-        return A.synthetic_hdr_image(cfg["size"], cfg["size"], seed)
-    return A.synthetic_image(cfg["size"], cfg["size"], seed)
+def _tri(v):
+    m = v & 511
+    return np.where(m < 256, m, 511 - m)
+
+
+def synthetic_rows(width, y0, y1, seed, hdr):
+    """Rows [y0, y1) of A.synthetic_image(width, height, seed) -- or of A.synthetic_hdr_image when `hdr` -- by the same
+    integer arithmetic texel by texel, so that bands computed apart join into the very same bytes
+    (tests/test_bench_setup.py compares them with the binding's generators)."""
+    y, x = np.meshgrid(np.arange(y0, y1, dtype=np.int64), np.arange(width, dtype=np.int64), indexing="ij")
+    r = (3 * _tri(x + 2 * y) + _tri((3 * x - y) >> 1)) >> 2
+    checker = ((x >> 5) + (y >> 5)) & 1
+    r = np.where(checker == 1, 255 - r, r)
+    g = (3 * _tri(2 * x - y + 128) + _tri((x + 3 * y) >> 2)) >> 2
+    b = 255 - ((_tri(x + y) + _tri((x - y) >> 1)) >> 1)
+    a = 192 + (_tri((x >> 1) + (y >> 2)) >> 2)
+
+    def noise(c, amp):
+        h = (x * 0x85EBCA6B + y * 0xC2B2AE35 + c * 0x27D4EB2F + seed) & 0xFFFFFFFF
+        h ^= h >> 15
+        h = (h * 0x2C1B3C6D) & 0xFFFFFFFF
+        h ^= h >> 12
+        h = (h * 0x297A2D39) & 0xFFFFFFFF
+        h ^= h >> 15
+        return (h % (2 * amp + 1)) - amp
+
+    out = np.stack([r + noise(0, 10), g + noise(1, 10), b + noise(2, 10), a + noise(3, 3)], axis=-1)
+    out = np.clip(out, 0, 255).astype(np.uint8)
+    if not hdr:
+        return out
+    base = out.astype(np.float32) / np.float32(255.0)
+    expo = ((_tri(x >> 3) + _tri(y >> 3)) >> 6) - 2
+    base[..., :3] *= np.ldexp(np.float32(1.0), expo.astype(np.int32)).astype(np.float32)[..., None]
+    return base.astype(np.float16)
+
+
+def make_image(cfg, seed, band=256):
+    """The bench image of `cfg`: A.synthetic_image / A.synthetic_hdr_image of the config's size, computed in bands of
+    `band` rows on up to 16 host threads (numpy drops the GIL inside its loops): one call on the whole 8192^2 image
+    keeps one core busy for 6 to 25 s, most of what a plain run spent outside its steps."""
+    from concurrent.futures import ThreadPoolExecutor
+    size, hdr = cfg["size"], cfg["hdr"]
+    img = np.empty((size, size, 4), dtype=np.float16 if hdr else np.uint8)
+
+    def fill(y0):
+        img[y0:y0 + band] = synthetic_rows(size, y0, min(y0 + band, size), seed, hdr)
+
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    with ThreadPoolExecutor(max(1, min(16, cores))) as pool:
+        list(pool.map(fill, range(0, size, band)))
+    return img
 
 
 def make_context(lib, cfg, threads=1):
@@ -618,6 +671,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2", help="BASELINE config timed as the headline line (default c2 = configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every leg beside it: value_host_api, quality, cpu_baseline, parity_full, "
+                         "extra_configs (about 90 s more on an MI355X box; the --no-* options below drop single legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-quality", action="store_true", help="skip decoding the output for PSNR")
     ap.add_argument("--no-parity-full", action="store_true", help="skip the whole-image byte comparison with the reference (config 2, ~10 s of host time)")
@@ -632,6 +688,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if not args.full:
+        args.no_cpu_baseline = args.no_quality = args.no_parity_full = args.no_extra = args.no_host_api = True
     cfg = CONFIGS[args.config]
 
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -16,7 +16,7 @@ timeout 150 python tools/time_decode_ab.py 8192 astc-encoder_amd/variants/libast
 (cd /tmp && AB_CASES=1 timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o dec -- python $R/tools/time_decode_ab.py 8192 $R/astc-encoder_amd/libastcenc_amd.so > $O/prof.log 2>&1); echo "prof rc $? ($((SECONDS - T0)) s)"
 find $O/prof -name "*kernel_stats*" | head -1 | xargs -r cat | grep -i "decompress\|Name" | head -4
 find $O/prof -name "*.db" -delete 2>/dev/null; find $O/prof -name "*kernel_trace*" -size +4M -delete 2>/dev/null
-timeout 240 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $? ($((SECONDS - T0)) s)"; head -c 1500 $O/bench_default.json; echo
+timeout 240 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $? ($((SECONDS - T0)) s)"; head -c 1500 $O/bench_default.json; echo
 if [ "${2:-}" = "full" ]; then
   timeout 330 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; echo "pytest gpu rc $? ($((SECONDS - T0)) s)"; tail -3 $O/pytest_gpu.txt
 fi

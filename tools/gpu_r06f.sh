@@ -13,5 +13,5 @@ for deal in static dynamic static dynamic; do
   echo "== deal $deal 8192"; ASTCENC_AMD_LOG=stderr ASTCENC_AMD_DEAL=$deal ASTCENC_AMD_DEVICES=0,0,0,0,0,0,0,0 python tools/time_deal.py 8192 2>&1 | grep -v amdgpu.ids
 done 2>&1 | tee $O/deal_static_vs_dynamic_8192.txt
 tools/gpu_pmc_decode.sh astc-encoder_amd/libastcenc_amd.so r06f/decode_pmc 6 > $O/decode_pmc_6x6.txt 2>&1; tail -40 $O/decode_pmc_6x6.txt
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; python -c "
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; python -c "
 import json; d=json.load(open('$O/bench_default.json')); print(d['value'], d['ms_per_step'], d.get('context'), d['cpu_baseline']['value'], d['speedup_vs_cpu_baseline']); print(json.dumps(d['extra_configs'][-1])[:1500])"
