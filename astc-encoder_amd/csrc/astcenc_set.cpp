@@ -4,8 +4,9 @@
 // the backend then compresses (decompresses) the blocks of all entries as one range (backend_compress_set).
 // Product library only: the sequential build of oracle/emu has no backend_*_set.
 // The mip chain entry points live here too: a compressed chain is an image set of one entry per level, its generation queued
-// ahead of the set's launches (backend_compress_set with CompressSetJob::generate; the filter: mip_filter.h, the post-passes of
-// the _ex_ calls: mip_post.h).  Every mip call is one path: the calls without options pass null ones.
+// ahead of the set's launches (backend_compress_set with CompressSetJob::generate; the filter: mip_filter.h, the windowed
+// filters of the _filtered_ calls: mip_resample.h, the post-passes of the _ex_ calls: mip_post.h).  Every mip call is one path:
+// the calls without options or a filter pass null ones.
 #include "../../include/astcenc.h"
 #include "../../include/astcenc_amd.h"
 #include "backend.h"
@@ -260,11 +261,33 @@ static astcenc_error check_mip_options(const char* fn, const astcenc_context* ct
 	return ASTCENC_SUCCESS;
 }
 
-/* The generation and compression entry points; fn: the name of the one called, for the log; options: null for the calls
- * without them. */
+/* The filter of the _filtered_ calls (null: the box) into the job: the box leaves it as it is (kind 0, the box kernels). */
+static astcenc_error check_mip_filter(const char* fn, const astcenc_amd_mip_filter* filter, MipChainJob& gen)
+{
+	if (!filter) return ASTCENC_SUCCESS;
+	const int kind = (int)filter->kind, edge = (int)filter->edge;
+	if (kind < ASTCENC_AMD_MIP_FILTER_BOX || kind > ASTCENC_AMD_MIP_FILTER_KAISER)
+	{
+		backend_log("%s: filter->kind %d is not an astcenc_amd_mip_filter_kind", fn, kind);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (edge != ASTCENC_AMD_MIP_EDGE_CLAMP && edge != ASTCENC_AMD_MIP_EDGE_WRAP)
+	{
+		backend_log("%s: filter->edge %d is not an astcenc_amd_mip_edge", fn, edge);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (kind == ASTCENC_AMD_MIP_FILTER_BOX) return ASTCENC_SUCCESS;
+	gen.filter_kind = (uint32_t)kind;
+	gen.filter_edge = (uint32_t)edge;
+	return ASTCENC_SUCCESS;
+}
+
+/* The generation and compression entry points; fn: the name of the one called, for the log; options, filter: null for the
+ * calls without them. */
 static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
                                         unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
-                                        const astcenc_amd_mip_options* options, void* device_levels, size_t levels_len, void* hip_stream)
+                                        const astcenc_amd_mip_options* options, const astcenc_amd_mip_filter* filter, void* device_levels,
+                                        size_t levels_len, void* hip_stream)
 {
 	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
@@ -272,6 +295,7 @@ static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, co
 	astcenc_error status = check_mip_volume_args(fn, ctx, device_image, dim_x, dim_y, dim_z, kind, data_type, level_count, device_levels, levels_len,
 	                                             hip_stream, layout, gen);
 	if (status == ASTCENC_SUCCESS) status = check_mip_options(fn, ctx, options, gen);
+	if (status == ASTCENC_SUCCESS) status = check_mip_filter(fn, filter, gen);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (layout.level_count == 1) return ASTCENC_SUCCESS;
 	status = rc_to_error(backend_generate_mips(ctx->backend, gen));
@@ -281,8 +305,9 @@ static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, co
 
 static astcenc_error compress_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
                                         unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, const astcenc_swizzle* swizzle,
-                                        unsigned int level_count, const astcenc_amd_mip_options* options, void* device_levels, size_t levels_len,
-                                        void* device_blocks, size_t blocks_len, void* hip_stream, float* kernel_ms)
+                                        unsigned int level_count, const astcenc_amd_mip_options* options, const astcenc_amd_mip_filter* filter,
+                                        void* device_levels, size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
+                                        float* kernel_ms)
 {
 	if (!ctx || !swizzle) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
@@ -290,6 +315,7 @@ static astcenc_error compress_mip_chain(const char* fn, astcenc_context* ctx, co
 	astcenc_error status = check_mip_volume_args(fn, ctx, device_image, dim_x, dim_y, dim_z, kind, data_type, level_count, device_levels, levels_len,
 	                                             hip_stream, layout, gen);
 	if (status == ASTCENC_SUCCESS) status = check_mip_options(fn, ctx, options, gen);
+	if (status == ASTCENC_SUCCESS) status = check_mip_filter(fn, filter, gen);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (!device_blocks) { backend_log("%s: device_blocks is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
 	if (blocks_len < layout.blocks_len)
@@ -319,7 +345,7 @@ astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx,
                                                            unsigned int level_count, void* device_levels, size_t levels_len, void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          level_count, nullptr, device_levels, levels_len, hip_stream);
+	                          level_count, nullptr, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -329,7 +355,7 @@ astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx,
                                                            float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          swizzle, level_count, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 astcenc_error astcenc_amd_generate_mip_chain_ex_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -338,7 +364,7 @@ astcenc_error astcenc_amd_generate_mip_chain_ex_device(astcenc_context* ctx, con
                                                        void* device_levels, size_t levels_len, void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_ex_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          level_count, options, device_levels, levels_len, hip_stream);
+	                          level_count, options, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_ex_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -348,7 +374,31 @@ astcenc_error astcenc_amd_compress_mip_chain_ex_device(astcenc_context* ctx, con
                                                        void* device_blocks, size_t blocks_len, void* hip_stream, float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_ex_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          swizzle, level_count, options, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, options, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+}
+
+astcenc_error astcenc_amd_generate_mip_chain_filtered_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x,
+                                                             unsigned int dim_y, unsigned int dim_z, astcenc_amd_mip_kind kind,
+                                                             astcenc_type data_type, unsigned int level_count,
+                                                             const struct astcenc_amd_mip_options* options,
+                                                             const struct astcenc_amd_mip_filter* filter, void* device_levels,
+                                                             size_t levels_len, void* hip_stream)
+{
+	return generate_mip_chain("astcenc_amd_generate_mip_chain_filtered_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          level_count, options, filter, device_levels, levels_len, hip_stream);
+}
+
+astcenc_error astcenc_amd_compress_mip_chain_filtered_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x,
+                                                             unsigned int dim_y, unsigned int dim_z, astcenc_amd_mip_kind kind,
+                                                             astcenc_type data_type, const astcenc_swizzle* swizzle, unsigned int level_count,
+                                                             const struct astcenc_amd_mip_options* options,
+                                                             const struct astcenc_amd_mip_filter* filter, void* device_levels,
+                                                             size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
+                                                             float* kernel_ms)
+{
+	return compress_mip_chain("astcenc_amd_compress_mip_chain_filtered_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          swizzle, level_count, options, filter, device_levels, levels_len, device_blocks, blocks_len, hip_stream,
+	                          kernel_ms);
 }
 
 astcenc_error astcenc_amd_mip_chain_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, astcenc_type data_type,
@@ -373,7 +423,7 @@ astcenc_error astcenc_amd_generate_mip_chain_device(astcenc_context* ctx, const 
                                                     void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
-	                          level_count, nullptr, device_levels, levels_len, hip_stream);
+	                          level_count, nullptr, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -382,7 +432,7 @@ astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const 
                                                     void* hip_stream, float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
-	                          swizzle, level_count, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 } // extern "C"

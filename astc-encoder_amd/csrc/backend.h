@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <atomic>
+#include <vector>
 #include "astc_tables.h"
 #include "image_set.h"
 #include "mip_filter.h"
@@ -125,6 +126,9 @@ struct MipChainJob {
 	float alpha_cutoff;        // ALPHA_COVERAGE: the alpha test's reference value, and what the host derived from it:
 	uint32_t cover_t;          //   U8: a code is covered when >= cover_t (mip_cover_u8_threshold)
 	float cover_hi, cover_lo;  //   F16 / F32: the output type's values just at / below the cutoff (mip_cover_bounds)
+	// the filter (mip_resample.h, astcenc_amd_generate_mip_chain_filtered_device): MIP_FILTER_* and MIP_EDGE_*; 0 = the box
+	// filter of mip_filter.h
+	uint32_t filter_kind, filter_edge;
 };
 
 /* ... and its decompression (astcenc_amd_decompress_images_device): every entry as a DecompressDeviceJob (stream unused). */
@@ -256,6 +260,11 @@ void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uin
 int astc_mip_launch(const MipChainJob& job, const void* d_srgb, void* stream);
 size_t astc_mip_srgb_table_bytes();
 void astc_mip_srgb_tables_build(void* out);
+/* ... with a windowed filter (kernel_mip_filter.hip, job.filter_kind != 0): astc_mip_filter_table_build writes the taps of every
+ * level into `out` on the host (0; 1 when they would exceed the library's 64 MiB scratch bound, nothing built; 2 on an internal
+ * limit), astc_mip_filter_launch queues the levels from the table's device copy d_table. */
+int astc_mip_filter_table_build(const MipChainJob& job, std::vector<uint8_t>& out);
+int astc_mip_filter_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream);
 /* ... and its post-passes (kernel_mip_post.hip), queued after the generation of the same job when job.post_flags != 0.
  * d_scratch: astc_mip_post_scratch_bytes(job) bytes of device memory (0 when no scratch is needed; never above 64 MiB). */
 size_t astc_mip_post_scratch_bytes(const MipChainJob& job);

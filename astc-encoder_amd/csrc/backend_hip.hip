@@ -63,6 +63,8 @@ struct DeviceSlot {
 	float* d_alpha = nullptr; size_t alpha_cap = 0;   // alpha averages of the a_scale_radius pre-pass
 	float* d_alpha_scratch = nullptr; size_t alpha_scratch_cap = 0;   // padded tiles of the pre-pass when they outgrow LDS (large radii)
 	uint8_t* d_mip_post = nullptr; size_t mip_post_cap = 0;   // counts, histograms and surface states of the mip post-passes
+	uint8_t* d_mip_filter = nullptr; size_t mip_filter_cap = 0;   // the taps of a windowed mip filter (kernel_mip_filter.hip)
+	std::vector<uint8_t> h_mip_filter;  // ... and their host copy (kept until the next call: the upload is asynchronous)
 	uint8_t* d_set = nullptr; size_t set_cap = 0;     // the table of an image set (image_set.h), compression or decompression
 	std::vector<uint8_t> h_set;         // ... and its host copy (kept until the next set call: the upload is asynchronous)
 	unsigned long long* d_prof = nullptr;   // stage timers (ASTC_PROFILE builds) / search trace (ASTC_TRACE builds)
@@ -345,6 +347,7 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_alpha) (void)hipFree(s->d_alpha);
 	if (s->d_alpha_scratch) (void)hipFree(s->d_alpha_scratch);
 	if (s->d_mip_post) (void)hipFree(s->d_mip_post);
+	if (s->d_mip_filter) (void)hipFree(s->d_mip_filter);
 	if (s->d_set) (void)hipFree(s->d_set);
 	if (s->d_sums) (void)hipFree(s->d_sums);
 	if (s->d_prof) (void)hipFree(s->d_prof);
@@ -1325,14 +1328,30 @@ static int set_table_upload(DeviceSlot* s, hipStream_t stream, size_t bytes)
 	return 0;
 }
 
-/* Queues the generation of a mip chain and its post-passes on `stream` (the slot's lock held).  The post-passes' scratch is
- * sized first: if it cannot be had, nothing is launched. */
+/* Queues the generation of a mip chain and its post-passes on `stream` (the slot's lock held).  The windowed filter's taps and
+ * the post-passes' scratch are sized first: if they cannot be had, nothing is launched. */
 static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChainJob& job)
 {
+	if (job.filter_kind)
+	{
+		const int trc = astc_mip_filter_table_build(job, s->h_mip_filter);
+		if (trc == 1) { log_msg("the mip filter's taps exceed the 64 MiB scratch bound"); return 1; }
+		if (trc != 0) { log_msg("mip filter table: a tile's taps exceed the kernel's rows"); return 2; }
+		if (grow(s->d_mip_filter, s->mip_filter_cap, s->h_mip_filter.size()) != 0) return 1;
+	}
 	const size_t post = job.post_flags ? astc_mip_post_scratch_bytes(job) : 0;
 	if (post && grow(s->d_mip_post, s->mip_post_cap, post) != 0) return 1;
-	const int lrc = astc_mip_launch(job, s->d_srgb, stream);
-	if (lrc != 0) { log_msg("mip generation kernel launch failed (hip error %d)", lrc); return 2; }
+	if (job.filter_kind)
+	{
+		HIP_TRY(hipMemcpyAsync(s->d_mip_filter, s->h_mip_filter.data(), s->h_mip_filter.size(), hipMemcpyHostToDevice, stream), return 2);
+		const int frc = astc_mip_filter_launch(job, s->d_mip_filter, s->d_srgb, stream);
+		if (frc != 0) { log_msg("mip filter kernel launch failed (hip error %d)", frc); return 2; }
+	}
+	else
+	{
+		const int lrc = astc_mip_launch(job, s->d_srgb, stream);
+		if (lrc != 0) { log_msg("mip generation kernel launch failed (hip error %d)", lrc); return 2; }
+	}
 	const int prc = astc_mip_post_launch(job, s->d_mip_post, stream);
 	if (prc != 0) { log_msg("mip post-pass kernel launch failed (hip error %d)", prc); return 2; }
 	return 0;

@@ -322,6 +322,85 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_ex_device(
 	void* hip_stream,
 	float* kernel_ms);
 
+/* Mip chain filters: windowed filters in place of the box.
+ *
+ * astcenc_amd_generate_mip_chain_filtered_device and astcenc_amd_compress_mip_chain_filtered_device take the arguments of the
+ * _ex_ calls plus `filter` after `options`.  A null `filter`, or kind == ASTCENC_AMD_MIP_FILTER_BOX with either edge, gives exactly
+ * the _ex_ calls' bytes (the box never reads outside the source, so its edge does not matter).  Level sizes, offsets and the
+ * layout calls are unchanged; everything else -- the argument checks, all before anything is launched; error codes with nothing
+ * written; stream order, cancel, progress and kernel_ms; the options, applied after the whole chain has been generated -- is the
+ * _ex_ calls'.  An unknown kind or edge returns ASTCENC_ERR_BAD_PARAM with nothing written, named "filter" in the log.  2D images
+ * are the VOLUME of depth 1; ARRAY layers (cube faces) are filtered independently, with no seamless cube filtering; a VOLUME's z
+ * axis takes the same filter.  Every level is filtered from the level above it as stored.
+ *
+ * The filter, exactly (a numpy model reproduces it bit for bit):
+ *   - axis geometry: a source of s texels makes d = max(1, s >> 1).  s == 1: one tap on texel 0, weight 1.0.  Otherwise
+ *     r = (double)s / (double)d and destination j has the centre c = (double)((2j + 1) * s) / (double)(2d) (the product in 64-bit
+ *     integers); its taps are every integer i with |t| < S, t = (((double)i + 0.5) - c) / r, in increasing i, S the support;
+ *     f is evaluated on a = |t|, and w_i = f_i / sum, sum = f_first + ... in increasing i.  Tap i reads source texel
+ *     clamp(i, 0, s - 1) (CLAMP) or the non-negative i mod s (WRAP); taps on the same texel are not merged;
+ *   - the functions, a2 = a * a, a3 = a2 * a, every operation a separate IEEE double operation in the order written:
+ *       MITCHELL (B = C = 1/3, S = 2): a < 1: ((7.0 * a3 - 12.0 * a2) + 16.0 / 3.0) / 6.0,
+ *                                      else ((((-7.0 / 3.0) * a3 + 12.0 * a2) - 20.0 * a) + 32.0 / 3.0) / 6.0;
+ *       LANCZOS3 (S = 3): sinc(a) * sinc(a / 3.0);
+ *       KAISER (S = 3): q = a / 3.0; (sinc(a) * I0(4.0 * sqrt(1.0 - q * q))) / I0(4.0);
+ *     sinc(x) = 1.0 for x == 0, else sin(px) / px, px = 3.141592653589793 * x, sin the C library's; I0(x): q2 = (x * 0.5) *
+ *     (x * 0.5), term = sum = 1.0, then for k = 1 .. 24: term = (term * q2) / (double)(k * k), sum = sum + term.  The weights are
+ *     computed on the host, once per call; the device never evaluates a transcendental;
+ *   - per texel, in float64: for each z tap in increasing order and each y tap in increasing order row = sum_x w_x v; per slice
+ *     acc = sum_y w_y row; then vol = sum_z w_z acc.  Each sum starts at its first product; each multiply and add is rounded on
+ *     its own (no fused operations); no padding taps (a zero weight would turn -0.0 into +0.0 and inf into NaN).  An ARRAY layer
+ *     (and a 2D image) has the one z tap of weight 1.0;
+ *   - values and results: U8 v = (double)code, result clamp(floor(vol + 0.5), 0, 255); U8 in an ASTCENC_PRF_LDR_SRGB context,
+ *     channels 0-2: v = EOTF(code / 255) (the box filter's float64 table), result the number of codes c in 1..255 with
+ *     vol >= EOTF((c - 0.5) / 255), channel 3 linear; F32 (float)vol; F16 that float to half (round to nearest even both times).
+ *     Float data is not clamped: negative lobes may ring.
+ *
+ * The taps live in library scratch (no caller memory), one row per destination texel of an odd axis and one per even axis below
+ * 2^26 texels; when they exceed the library's 64 MiB scratch bound (odd axes of several hundred thousand texels) or cannot be
+ * allocated, the call returns ASTCENC_ERR_OUT_OF_MEM with nothing written.
+ *
+ * Which filter: MITCHELL is the usual middle ground (little ringing, slightly soft); LANCZOS3 is the sharpest and rings most;
+ * KAISER is close to LANCZOS3 with less ringing.  The basisu and toktx tools default to Kaiser or Lanczos. */
+enum astcenc_amd_mip_filter_kind {
+	ASTCENC_AMD_MIP_FILTER_BOX      = 0,   /* the exact box filter of the calls above */
+	ASTCENC_AMD_MIP_FILTER_MITCHELL = 1,   /* Mitchell-Netravali, B = C = 1/3, support 2 */
+	ASTCENC_AMD_MIP_FILTER_LANCZOS3 = 2,   /* sinc(t) sinc(t/3), support 3 */
+	ASTCENC_AMD_MIP_FILTER_KAISER   = 3    /* sinc(t) I0(4 sqrt(1 - (t/3)^2)) / I0(4), support 3 */
+};
+enum astcenc_amd_mip_edge { ASTCENC_AMD_MIP_EDGE_CLAMP = 0, ASTCENC_AMD_MIP_EDGE_WRAP = 1 };
+struct astcenc_amd_mip_filter {
+	enum astcenc_amd_mip_filter_kind kind;
+	enum astcenc_amd_mip_edge edge;
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_generate_mip_chain_filtered_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	const struct astcenc_amd_mip_options* options,
+	const struct astcenc_amd_mip_filter* filter,
+	void* device_levels, size_t levels_len,
+	void* hip_stream);
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_filtered_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	unsigned int level_count,
+	const struct astcenc_amd_mip_options* options,
+	const struct astcenc_amd_mip_filter* filter,
+	void* device_levels, size_t levels_len,
+	void* device_blocks, size_t blocks_len,
+	void* hip_stream,
+	float* kernel_ms);
+
 /* Error sums of two device-resident images of the same size, the quantities the reference CLI's quality
  * report is made of (ref: compute_error_metrics, Source/astcenccli_error_metrics.cpp:110-300):
  *   PSNR (LDR-RGBA)     = 10 log10(4 texels / (squared_error[0] + .. + [3]))
