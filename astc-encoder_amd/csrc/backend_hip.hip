@@ -229,23 +229,29 @@ int kernel_launch(const Backend* b, const DeviceSlot* s, const KernelLaunch& k)
 	return kernel_variants[b->variant].launch(k);
 }
 
-/* The self-check of slot_adopt_jit: 16 x 16 blocks (volumes: 8 x 8 x 4) of deterministic RGBA8 content through `fn` and through
- * the library's build of the context; true when the two block streams are byte-identical. */
+/* The self-check of slot_adopt_jit: 48 x 48 blocks (volumes: 16 x 16 x 8) of deterministic RGBA8 content through `fn` and
+ * through the library's build of the context; true when the two block streams are byte-identical.  (2304 blocks, nine content
+ * classes: a build compiled with floating-point contraction differs from the generic build on one block in a hundred of
+ * grey content and one in four hundred of lightly noisy ramps, and passed the 256 blocks of six classes this check once was
+ * -- tests/test_jit_matrix.py keeps such builds and expects them to be turned away here.) */
 bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 {
 	const uint32_t bsx = b->root.dim_x, bsy = b->root.dim_y, bsz = b->root.dim_z;
-	const uint32_t nbx = bsz > 1 ? 8u : 16u, nby = bsz > 1 ? 8u : 16u, nbz = bsz > 1 ? 4u : 1u;
+	const uint32_t nbx = bsz > 1 ? 16u : 48u, nby = bsz > 1 ? 16u : 48u, nbz = bsz > 1 ? 8u : 1u;
 	const uint32_t dim_x = nbx * bsx - 1u, dim_y = nby * bsy - 1u, dim_z = bsz > 1 ? nbz * bsz - 1u : 1u;      // (the last blocks are partial)
 	const size_t texels = (size_t)dim_x * dim_y * dim_z, nblocks = (size_t)nbx * nby * nbz;
 	std::vector<uint8_t> img(texels * 4);
 	uint32_t rng = 0x9E3779B1u;
+	auto tri = [](uint32_t v) { const uint32_t m = v & 511u; return (int)(m < 256u ? m : 511u - m); };
 	for (uint32_t z = 0; z < dim_z; z++)
 		for (uint32_t y = 0; y < dim_y; y++)
 			for (uint32_t x = 0; x < dim_x; x++)
 			{
-				// per block-sized tile: noise amplitude 0 (ramps), 6, 40, 255 (pure noise), two colours, a constant
-				const uint32_t tile = (x / bsx + 3u * (y / bsy) + 5u * (z / bsz)) % 6u;
+				// per block-sized tile: noise amplitude 0 (ramps), 6, 40, 255 (pure noise), two colours, a constant, grey with
+				// noise (opaque / with a varying alpha), smooth ramps without a step
+				const uint32_t tile = (x / bsx + 3u * (y / bsy) + 5u * (z / bsz) + y / (3u * bsy)) % 9u;
 				uint8_t* px = &img[(((size_t)z * dim_y + y) * dim_x + x) * 4];
+				int grey = 0;
 				for (int ch = 0; ch < 4; ch++)
 				{
 					rng = rng * 1664525u + 1013904223u;
@@ -256,7 +262,13 @@ bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 					else if (tile == 3) v = noise;
 					else if (tile == 4) v = ((x + ch) ^ (y >> 1)) & 2 ? 220 - 20 * ch : 30 + 25 * ch;
 					else if (tile == 5) v = 40 + 50 * ch;
-					if (ch == 3 && tile != 3 && tile != 2) v = 255;
+					else if (tile == 6 || tile == 7)
+					{
+						if (ch == 0) grey = (3 * tri(x + 2u * y + 5u * z) + tri((3u * x + 512u - y) >> 1)) / 4 + noise % 21 - 10;
+						v = ch < 3 ? grey : 192 + tri((x >> 1) + (y >> 2)) / 4 + noise % 7 - 3;
+					}
+					else if (tile == 8) v = tri(x * (2u + ch) + y * (5u - ch) + z * 3u);
+					if (ch == 3 && tile != 3 && tile != 2 && tile != 7) v = 255;
 					px[ch] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 				}
 			}
@@ -306,9 +318,9 @@ void slot_adopt_jit(Backend* b, DeviceSlot* s)
 		log_msg("run-time build %s does not load on device %d: the generic build stays", jit_kernel_name(b->jit), s->device);
 		return;
 	}
-	// Trust, but verify: before the build takes over, it and the library's own build compress the same 256 blocks of built-in
-	// content -- noise of several amplitudes over ramps, flat and two-colour stretches, i.e. blocks that run every trial of the
-	// search -- and the bytes must be equal.  (A build is compiled from the same source with the same numerics flags, so they
+	// Trust, but verify: before the build takes over, it and the library's own build compress the same 2304 blocks of built-in
+	// content -- noise of several amplitudes over ramps, flat, two-colour, grey and smooth stretches, i.e. blocks that run every
+	// trial of the search -- and the bytes must be equal.  (A build is compiled from the same source with the same numerics flags, so they
 	// are -- unless the compiler did something with the constants that it does not do without them: the run-time builds of the
 	// 10x8 and 12x12 footprints do differ, DESIGN.md section 3.1, and are turned away here.)
 	// (ASTCENC_AMD_JIT_SELF_CHECK=0: debugging only -- tools/jit_debug4.py looks at a build the check turns away)

@@ -141,8 +141,10 @@ def test_set_of_volumes_and_of_multi_slice_entries(product, A):
 
 
 def test_set_through_a_run_time_build(product, ref, A, tmp_path, monkeypatch):
+    from jit_builds import prewarm
     monkeypatch.setenv("ASTCENC_AMD_CACHE_DIR", str(tmp_path / "cache"))
     monkeypatch.setenv("ASTCENC_AMD_JIT", "sync")
+    prewarm(str(tmp_path / "cache"), [(A.PRF_LDR, (6, 6), A.PRE_THOROUGH, 0)])       # (compiled on the CPU, found in the cache)
     ctx, _ = _ctx(product, A, A.PRF_LDR, (6, 6), A.PRE_THOROUGH)
     try:
         assert product.lib.astcenc_amd_context_kernel_name(ctx).decode().startswith("astc_compress_blocks_jit_")

@@ -146,7 +146,7 @@ def test_run_time_build_takes_the_library_kernels_arguments(built, emu, A, tmp_p
         pytest.skip("no llvm-readelf")
     cache = str(tmp_path / "cache")
     monkeypatch.setenv("ASTCENC_AMD_CACHE_DIR", cache)
-    from test_jit import _specialize_on_cpu
+    from jit_builds import specialize_on_cpu as _specialize_on_cpu
     rc, name = _specialize_on_cpu((cache, A.PRF_LDR, (6, 6), A.PRE_THOROUGH, 0))
     assert rc == 0 and name.startswith("astc_compress_blocks_jit_"), (rc, name)
     (co,) = os.listdir(cache)

@@ -9,9 +9,6 @@ GPU: contexts of other presets / footprints / profiles / flags launch "astc_comp
      reference's bytes; the default (lazy) mode starts on the generic build and switches; a sweep of footprints x presets x
      profiles through the run-time builds matches the reference.  (The builds of the sweep are compiled side by side on the
      box's CPUs through the sequential library -- same source, same records, same hash -- and found in the cache.)"""
-import concurrent.futures
-import multiprocessing
-import ctypes
 import os
 import subprocess
 import sys
@@ -20,38 +17,10 @@ import time
 import numpy as np
 import pytest
 
-import oracle_libs as O  # (path set up by conftest.py)
+from jit_builds import compress_both as _compress_both, prewarm as _prewarm, specialize_on_cpu as _specialize_on_cpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-
-
-def _specialize_on_cpu(args):
-    """Worker process: compile the context's run-time build through the sequential library into the shared cache."""
-    cache, profile, block, quality, flags = args
-    os.environ["ASTCENC_AMD_CACHE_DIR"] = cache
-    sys.path.insert(0, os.path.join(ROOT, "astc-encoder_amd", "python"))
-    import astcenc_amd as A
-    lib = A.Library(O.LIB_EMU)
-    bz = block[2] if len(block) > 2 else 1
-    err, cfg = lib.config_init(profile, block[0], block[1], bz, quality, flags)
-    assert err == 0
-    err, ctx = lib.context_alloc(cfg, 1)
-    assert err == 0
-    rc = lib.lib.astcenc_amd_context_specialize(ctx)
-    name = lib.lib.astcenc_amd_context_kernel_name(ctx).decode()
-    lib.context_free(ctx)
-    return rc, name
-
-
-def _prewarm(cache, contexts, strict=True):
-    workers = max(1, min(len(contexts), len(os.sched_getaffinity(0))))
-    # (fresh interpreters: the parent may hold a HIP runtime, which does not survive a fork)
-    with concurrent.futures.ProcessPoolExecutor(max_workers=workers, mp_context=multiprocessing.get_context("spawn")) as pool:
-        results = list(pool.map(_specialize_on_cpu, [(cache,) + c for c in contexts]))
-    if strict:
-        assert all(rc == 0 and name.startswith("astc_compress_blocks_jit_") for rc, name in results), results
-    return [name if rc == 0 else None for rc, name in results]
 
 
 def test_embedded_source_compiles_and_is_cached(built, emu, A, tmp_path, monkeypatch):
@@ -76,12 +45,6 @@ def test_embedded_source_compiles_and_is_cached(built, emu, A, tmp_path, monkeyp
     assert rc == 0 and other != name and len(os.listdir(cache)) == 2
 
 
-def _compress_both(product, ref, A, img, block, quality, profile, flags=0, tweak=None, specialize=True):
-    want = ref.compress(img, block, quality, profile=profile, flags=flags, tweak=tweak).reshape(-1, 16)
-    got = product.compress(img, block, quality, profile=profile, flags=flags, tweak=tweak, specialize=specialize).reshape(-1, 16)
-    return int((want != got).any(axis=1).sum()), product.last_kernel
-
-
 @pytest.mark.gpu
 def test_other_contexts_get_a_run_time_build(product, ref, A, tmp_path, monkeypatch):
     """The four contexts VERDICT r05 names, a hand-edited tuning field, an HDR one: specialised, and the reference's bytes."""
@@ -90,11 +53,10 @@ def test_other_contexts_get_a_run_time_build(product, ref, A, tmp_path, monkeypa
     monkeypatch.setenv("ASTCENC_AMD_JIT", "sync")
     img = A.synthetic_image(250, 190, 3)
 
-    def two_partitions(cfg):
-        cfg.tune_partition_count_limit = 2
+    two_partitions = {"tune_partition_count_limit": 2}
     cases = [(A.PRF_LDR, (6, 6), A.PRE_THOROUGH, 0, None), (A.PRF_LDR, (4, 4), A.PRE_MEDIUM, 0, None), (A.PRF_LDR_SRGB, (6, 6), A.PRE_MEDIUM, 0, None),
              (A.PRF_LDR, (6, 6), A.PRE_MEDIUM, A.FLG_USE_PERCEPTUAL, None), (A.PRF_LDR, (6, 6), A.PRE_MEDIUM, 0, two_partitions)]
-    _prewarm(cache, [c[:4] for c in cases[:4]])      # (the fifth is compiled in astcenc_context_alloc: ASTCENC_AMD_JIT=sync)
+    _prewarm(cache, [c if c[4] else c[:4] for c in cases])
     names = set()
     for profile, block, quality, flags, tweak in cases:
         bad, name = _compress_both(product, ref, A, img, block, quality, profile, flags, tweak)
