@@ -5,8 +5,8 @@
 // Product library only: the sequential build of oracle/emu has no backend_*_set.
 // The mip chain entry points live here too: a compressed chain is an image set of one entry per level, its generation queued
 // ahead of the set's launches (backend_compress_set with CompressSetJob::generate; the filter: mip_filter.h, the windowed
-// filters of the _filtered_ calls: mip_resample.h, the post-passes of the _ex_ calls: mip_post.h).  Every mip call is one path:
-// the calls without options or a filter pass null ones.
+// filters of the _filtered_ calls: mip_resample.h, the weighting of the _weighted_ calls: mip_weighted.h, the post-passes of the
+// _ex_ calls: mip_post.h).  Every mip call is one path: the calls without options, a filter or a weighting pass null ones.
 #include "../../include/astcenc.h"
 #include "../../include/astcenc_amd.h"
 #include "backend.h"
@@ -282,12 +282,26 @@ static astcenc_error check_mip_filter(const char* fn, const astcenc_amd_mip_filt
 	return ASTCENC_SUCCESS;
 }
 
-/* The generation and compression entry points; fn: the name of the one called, for the log; options, filter: null for the
- * calls without them. */
+/* The weighting of the _weighted_ calls (null: none) into the job: none leaves it as it is (weight 0, the plain kernels). */
+static astcenc_error check_mip_weighting(const char* fn, const astcenc_amd_mip_weighting* weighting, MipChainJob& gen)
+{
+	if (!weighting) return ASTCENC_SUCCESS;
+	const int weight = (int)weighting->weight;
+	if (weight != ASTCENC_AMD_MIP_WEIGHT_NONE && weight != ASTCENC_AMD_MIP_WEIGHT_ALPHA)
+	{
+		backend_log("%s: weighting->weight %d is not an astcenc_amd_mip_weight", fn, weight);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	gen.weight = (uint32_t)weight;
+	return ASTCENC_SUCCESS;
+}
+
+/* The generation and compression entry points; fn: the name of the one called, for the log; options, filter, weighting: null
+ * for the calls without them. */
 static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
                                         unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, unsigned int level_count,
-                                        const astcenc_amd_mip_options* options, const astcenc_amd_mip_filter* filter, void* device_levels,
-                                        size_t levels_len, void* hip_stream)
+                                        const astcenc_amd_mip_options* options, const astcenc_amd_mip_filter* filter,
+                                        const astcenc_amd_mip_weighting* weighting, void* device_levels, size_t levels_len, void* hip_stream)
 {
 	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
@@ -296,6 +310,7 @@ static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, co
 	                                             hip_stream, layout, gen);
 	if (status == ASTCENC_SUCCESS) status = check_mip_options(fn, ctx, options, gen);
 	if (status == ASTCENC_SUCCESS) status = check_mip_filter(fn, filter, gen);
+	if (status == ASTCENC_SUCCESS) status = check_mip_weighting(fn, weighting, gen);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (layout.level_count == 1) return ASTCENC_SUCCESS;
 	status = rc_to_error(backend_generate_mips(ctx->backend, gen));
@@ -306,8 +321,8 @@ static astcenc_error generate_mip_chain(const char* fn, astcenc_context* ctx, co
 static astcenc_error compress_mip_chain(const char* fn, astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
                                         unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type, const astcenc_swizzle* swizzle,
                                         unsigned int level_count, const astcenc_amd_mip_options* options, const astcenc_amd_mip_filter* filter,
-                                        void* device_levels, size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
-                                        float* kernel_ms)
+                                        const astcenc_amd_mip_weighting* weighting, void* device_levels, size_t levels_len,
+                                        void* device_blocks, size_t blocks_len, void* hip_stream, float* kernel_ms)
 {
 	if (!ctx || !swizzle) return ASTCENC_ERR_BAD_PARAM;
 	struct astcenc_amd_mip_chain_volume_layout layout;
@@ -316,6 +331,7 @@ static astcenc_error compress_mip_chain(const char* fn, astcenc_context* ctx, co
 	                                             hip_stream, layout, gen);
 	if (status == ASTCENC_SUCCESS) status = check_mip_options(fn, ctx, options, gen);
 	if (status == ASTCENC_SUCCESS) status = check_mip_filter(fn, filter, gen);
+	if (status == ASTCENC_SUCCESS) status = check_mip_weighting(fn, weighting, gen);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (!device_blocks) { backend_log("%s: device_blocks is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
 	if (blocks_len < layout.blocks_len)
@@ -345,7 +361,7 @@ astcenc_error astcenc_amd_generate_mip_chain_volume_device(astcenc_context* ctx,
                                                            unsigned int level_count, void* device_levels, size_t levels_len, void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          level_count, nullptr, nullptr, device_levels, levels_len, hip_stream);
+	                          level_count, nullptr, nullptr, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -355,7 +371,7 @@ astcenc_error astcenc_amd_compress_mip_chain_volume_device(astcenc_context* ctx,
                                                            float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_volume_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          swizzle, level_count, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, nullptr, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 astcenc_error astcenc_amd_generate_mip_chain_ex_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -364,7 +380,7 @@ astcenc_error astcenc_amd_generate_mip_chain_ex_device(astcenc_context* ctx, con
                                                        void* device_levels, size_t levels_len, void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_ex_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          level_count, options, nullptr, device_levels, levels_len, hip_stream);
+	                          level_count, options, nullptr, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_ex_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -374,7 +390,7 @@ astcenc_error astcenc_amd_compress_mip_chain_ex_device(astcenc_context* ctx, con
                                                        void* device_blocks, size_t blocks_len, void* hip_stream, float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_ex_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          swizzle, level_count, options, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, options, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 astcenc_error astcenc_amd_generate_mip_chain_filtered_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x,
@@ -385,7 +401,7 @@ astcenc_error astcenc_amd_generate_mip_chain_filtered_device(astcenc_context* ct
                                                              size_t levels_len, void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_filtered_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          level_count, options, filter, device_levels, levels_len, hip_stream);
+	                          level_count, options, filter, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_filtered_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x,
@@ -397,8 +413,34 @@ astcenc_error astcenc_amd_compress_mip_chain_filtered_device(astcenc_context* ct
                                                              float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_filtered_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
-	                          swizzle, level_count, options, filter, device_levels, levels_len, device_blocks, blocks_len, hip_stream,
-	                          kernel_ms);
+	                          swizzle, level_count, options, filter, nullptr, device_levels, levels_len, device_blocks, blocks_len,
+	                          hip_stream, kernel_ms);
+}
+
+astcenc_error astcenc_amd_generate_mip_chain_weighted_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x,
+                                                             unsigned int dim_y, unsigned int dim_z, astcenc_amd_mip_kind kind,
+                                                             astcenc_type data_type, unsigned int level_count,
+                                                             const struct astcenc_amd_mip_options* options,
+                                                             const struct astcenc_amd_mip_filter* filter,
+                                                             const struct astcenc_amd_mip_weighting* weighting, void* device_levels,
+                                                             size_t levels_len, void* hip_stream)
+{
+	return generate_mip_chain("astcenc_amd_generate_mip_chain_weighted_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          level_count, options, filter, weighting, device_levels, levels_len, hip_stream);
+}
+
+astcenc_error astcenc_amd_compress_mip_chain_weighted_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x,
+                                                             unsigned int dim_y, unsigned int dim_z, astcenc_amd_mip_kind kind,
+                                                             astcenc_type data_type, const astcenc_swizzle* swizzle, unsigned int level_count,
+                                                             const struct astcenc_amd_mip_options* options,
+                                                             const struct astcenc_amd_mip_filter* filter,
+                                                             const struct astcenc_amd_mip_weighting* weighting, void* device_levels,
+                                                             size_t levels_len, void* device_blocks, size_t blocks_len, void* hip_stream,
+                                                             float* kernel_ms)
+{
+	return compress_mip_chain("astcenc_amd_compress_mip_chain_weighted_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
+	                          swizzle, level_count, options, filter, weighting, device_levels, levels_len, device_blocks, blocks_len,
+	                          hip_stream, kernel_ms);
 }
 
 astcenc_error astcenc_amd_mip_chain_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, astcenc_type data_type,
@@ -423,7 +465,7 @@ astcenc_error astcenc_amd_generate_mip_chain_device(astcenc_context* ctx, const 
                                                     void* hip_stream)
 {
 	return generate_mip_chain("astcenc_amd_generate_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
-	                          level_count, nullptr, nullptr, device_levels, levels_len, hip_stream);
+	                          level_count, nullptr, nullptr, nullptr, device_levels, levels_len, hip_stream);
 }
 
 astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
@@ -432,7 +474,7 @@ astcenc_error astcenc_amd_compress_mip_chain_device(astcenc_context* ctx, const 
                                                     void* hip_stream, float* kernel_ms)
 {
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_device", ctx, device_image, dim_x, dim_y, 1, ASTCENC_AMD_MIP_VOLUME, data_type,
-	                          swizzle, level_count, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
+	                          swizzle, level_count, nullptr, nullptr, nullptr, device_levels, levels_len, device_blocks, blocks_len, hip_stream, kernel_ms);
 }
 
 } // extern "C"

@@ -129,6 +129,8 @@ struct MipChainJob {
 	// the filter (mip_resample.h, astcenc_amd_generate_mip_chain_filtered_device): MIP_FILTER_* and MIP_EDGE_*; 0 = the box
 	// filter of mip_filter.h
 	uint32_t filter_kind, filter_edge;
+	// the weighting (mip_weighted.h, astcenc_amd_generate_mip_chain_weighted_device): MIP_WEIGHT_*; 0 = none, the plain kernels
+	uint32_t weight;
 };
 
 /* ... and its decompression (astcenc_amd_decompress_images_device): every entry as a DecompressDeviceJob (stream unused). */
@@ -260,11 +262,15 @@ void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uin
 int astc_mip_launch(const MipChainJob& job, const void* d_srgb, void* stream);
 size_t astc_mip_srgb_table_bytes();
 void astc_mip_srgb_tables_build(void* out);
+/* ... of the box filter with alpha-weighted colour (kernel_mip_weighted.hip, job.weight != 0 and job.filter_kind == 0). */
+int astc_mip_weighted_launch(const MipChainJob& job, const void* d_srgb, void* stream);
 /* ... with a windowed filter (kernel_mip_filter.hip, job.filter_kind != 0): astc_mip_filter_table_build writes the taps of every
  * level into `out` on the host (0; 1 when they would exceed the library's 64 MiB scratch bound, nothing built; 2 on an internal
- * limit), astc_mip_filter_launch queues the levels from the table's device copy d_table. */
+ * limit), astc_mip_filter_launch queues the levels from the table's device copy d_table; astc_mip_filter_weighted_launch does
+ * from the same table when job.weight != 0 (kernel_mip_weighted.hip). */
 int astc_mip_filter_table_build(const MipChainJob& job, std::vector<uint8_t>& out);
 int astc_mip_filter_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream);
+int astc_mip_filter_weighted_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream);
 /* ... and its post-passes (kernel_mip_post.hip), queued after the generation of the same job when job.post_flags != 0.
  * d_scratch: astc_mip_post_scratch_bytes(job) bytes of device memory (0 when no scratch is needed; never above 64 MiB). */
 size_t astc_mip_post_scratch_bytes(const MipChainJob& job);

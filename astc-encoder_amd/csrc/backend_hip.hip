@@ -1356,12 +1356,13 @@ static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChai
 	if (job.filter_kind)
 	{
 		HIP_TRY(hipMemcpyAsync(s->d_mip_filter, s->h_mip_filter.data(), s->h_mip_filter.size(), hipMemcpyHostToDevice, stream), return 2);
-		const int frc = astc_mip_filter_launch(job, s->d_mip_filter, s->d_srgb, stream);
+		const int frc = job.weight ? astc_mip_filter_weighted_launch(job, s->d_mip_filter, s->d_srgb, stream)
+		                           : astc_mip_filter_launch(job, s->d_mip_filter, s->d_srgb, stream);
 		if (frc != 0) { log_msg("mip filter kernel launch failed (hip error %d)", frc); return 2; }
 	}
 	else
 	{
-		const int lrc = astc_mip_launch(job, s->d_srgb, stream);
+		const int lrc = job.weight ? astc_mip_weighted_launch(job, s->d_srgb, stream) : astc_mip_launch(job, s->d_srgb, stream);
 		if (lrc != 0) { log_msg("mip generation kernel launch failed (hip error %d)", lrc); return 2; }
 	}
 	const int prc = astc_mip_post_launch(job, s->d_mip_post, stream);

@@ -10,9 +10,7 @@
 //   - once a source level has at most MIP_RS_TAIL_TEXELS texels (per layer for an ARRAY), one workgroup per layer makes every
 //     remaining level (astc_mipfilter_tail), each level read back from global memory after a barrier.
 // The box filter keeps its own kernels (kernel_mips.hip); nothing here runs for it.
-#include "backend.h"
-#include "mip_resample.h"
-#include <hip/hip_runtime.h>
+#include "mip_filter_kernels.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -21,54 +19,10 @@ namespace astcd {
 
 namespace {
 
-enum MipRsKind { MIP_RS_U8 = 0, MIP_RS_U8_SRGB = 1, MIP_RS_F16 = 2, MIP_RS_F32 = 3 };
-constexpr uint32_t MIP_RS_TX = 32, MIP_RS_TY = 16;        // destination tile
-constexpr uint32_t MIP_RS_THREADS = 256;
-constexpr uint32_t MIP_RS_PER = MIP_RS_TX * MIP_RS_TY / MIP_RS_THREADS;   // destination texels per thread
-constexpr uint32_t MIP_RS_ROWS = 48;                      // source rows a tile's y taps may touch (checked on the host)
-constexpr uint32_t MIP_RS_TAIL_TEXELS = 4096;
-constexpr uint32_t MIP_RS_MAX_GROUPS = 1u << 20;
-constexpr size_t MIP_RS_TABLE_MAX = (size_t)64 << 20;     // the library's scratch bound
-constexpr size_t MIP_RS_ROW_BYTES = 16 + 8 * MIP_RESAMPLE_MAX_TAPS;
-
-/* One axis of a level in the table: rows of taps, each { int64 first, uint32 count, uint32 0, double w[17] }.  rows == 1 (a
- * source of one texel, or an even one below 2^26 texels, where c = 2j + 1 exactly and every destination has the taps of j = 0
- * moved by 2j): destination j takes row 0 with first + 2j; otherwise row j. */
-struct MipRsAxis {
-	uint32_t s, d, rows, edge;
-	uint64_t at;                  // byte offset of row 0 in the table
-};
-
-/* A level: made from `src` (sx x sy x sz) into `dst` (dx x dy x dz); sz / dz are the layers of an ARRAY (array != 0: no z
- * filter, a layer reads its own slice) or a VOLUME's depths. */
-struct MipRsLevel {
-	const void* src;
-	void* dst;
-	uint32_t sx, sy, sz, dx, dy, dz;
-	uint32_t array, tiles_x, tiles_y, pad;
-	MipRsAxis ax[3];
-};
-
 struct MipRsShared {
 	double rows[MIP_RS_ROWS][MIP_RS_TX][4];                 // the x pass's row sums of the tile
 	double srgb[MIP_SRGB_TABLE_DOUBLES];                    // lin[256], then thr[255] (sRGB data only)
 };
-
-struct MipRsTaps {
-	long long first;
-	uint32_t count;
-	const double* w;
-};
-
-__device__ inline MipRsTaps mip_rs_taps(const uint8_t* table, const MipRsAxis& a, uint32_t j)
-{
-	const uint8_t* p = table + a.at + (a.rows == 1 ? 0 : (size_t)j * MIP_RS_ROW_BYTES);
-	MipRsTaps t;
-	t.first = *reinterpret_cast<const long long*>(p) + (a.rows == 1 ? 2ll * j : 0ll);
-	t.count = *reinterpret_cast<const uint32_t*>(p + 8);
-	t.w = reinterpret_cast<const double*>(p + 16);
-	return t;
-}
 
 /* The values of source texel i (component loads: the caller's level 0 needs only the alignment of its components). */
 template <int K>
@@ -289,26 +243,8 @@ int astc_mip_filter_table_build(const MipChainJob& job, std::vector<uint8_t>& ou
 template <int K>
 static int mip_filter_launch_kind(const MipChainJob& job, const uint8_t* d_table, const double* srgb, hipStream_t stream)
 {
-	const bool volume = job.kind == 1;
-	const uint32_t layers = volume ? 1u : job.dim_z;
-	for (uint32_t i = 1; i < job.level_count; i++)
-	{
-		const uint32_t sx = mip_level_dim(job.dim_x, i - 1), sy = mip_level_dim(job.dim_y, i - 1);
-		const uint32_t sz = volume ? mip_level_dim(job.dim_z, i - 1) : 1u;
-		if ((size_t)sx * sy * sz <= MIP_RS_TAIL_TEXELS)
-		{
-			const uint32_t groups = layers < MIP_RS_MAX_GROUPS ? layers : MIP_RS_MAX_GROUPS;
-			hipLaunchKernelGGL(astc_mipfilter_tail<K>, dim3(groups), dim3(MIP_RS_THREADS), 0, stream, d_table, i - 1, job.level_count - 1,
-			                   layers, srgb);
-			break;
-		}
-		const uint32_t dx = mip_level_dim(job.dim_x, i), dy = mip_level_dim(job.dim_y, i);
-		const uint32_t dz = volume ? mip_level_dim(job.dim_z, i) : job.dim_z;
-		const size_t tiles = (size_t)((dx + MIP_RS_TX - 1) / MIP_RS_TX) * ((dy + MIP_RS_TY - 1) / MIP_RS_TY) * dz;
-		const uint32_t groups = tiles < MIP_RS_MAX_GROUPS ? (uint32_t)tiles : MIP_RS_MAX_GROUPS;
-		hipLaunchKernelGGL(astc_mipfilter_level<K>, dim3(groups), dim3(MIP_RS_THREADS), 0, stream, d_table, i - 1, srgb);
-	}
-	return (int)hipGetLastError();
+	// (the tail is named first: the kernels are instantiated in the order they are named, and the inliner's choices follow it)
+	return mip_rs_launch_chain(job, d_table, srgb, stream, astc_mipfilter_tail<K>, astc_mipfilter_level<K>, MIP_RS_TX);
 }
 
 int astc_mip_filter_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream)

@@ -96,13 +96,15 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_mip_chain_device", "astcenc_amd_mip_chain_volume_layout",
                "astcenc_amd_generate_mip_chain_volume_device", "astcenc_amd_compress_mip_chain_volume_device",
                "astcenc_amd_generate_mip_chain_ex_device", "astcenc_amd_compress_mip_chain_ex_device",
-               "astcenc_amd_generate_mip_chain_filtered_device", "astcenc_amd_compress_mip_chain_filtered_device"]
+               "astcenc_amd_generate_mip_chain_filtered_device", "astcenc_amd_compress_mip_chain_filtered_device",
+               "astcenc_amd_generate_mip_chain_weighted_device", "astcenc_amd_compress_mip_chain_weighted_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
 MIP_NORMALIZE, MIP_ALPHA_COVERAGE = 0x1, 0x2
 MIP_FILTER_BOX, MIP_FILTER_MITCHELL, MIP_FILTER_LANCZOS3, MIP_FILTER_KAISER = 0, 1, 2, 3
 MIP_EDGE_CLAMP, MIP_EDGE_WRAP = 0, 1
+MIP_WEIGHT_NONE, MIP_WEIGHT_ALPHA = 0, 1
 
 
 class MipChainLayout(C.Structure):
@@ -127,6 +129,11 @@ class MipOptions(C.Structure):
 class MipFilter(C.Structure):
     """struct astcenc_amd_mip_filter (include/astcenc_amd.h): kind = MIP_FILTER_*, edge = MIP_EDGE_*."""
     _fields_ = [("kind", C.c_int), ("edge", C.c_int)]
+
+
+class MipWeighting(C.Structure):
+    """struct astcenc_amd_mip_weighting (include/astcenc_amd.h): weight = MIP_WEIGHT_*."""
+    _fields_ = [("weight", C.c_int)]
 
 
 class ImageSetEntry(C.Structure):
@@ -289,6 +296,17 @@ class Library:
                                                                          C.POINTER(MipFilter), C.c_void_p, C.c_size_t, C.c_void_p,
                                                                          C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
             L.astcenc_amd_compress_mip_chain_filtered_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_generate_mip_chain_weighted_device"):
+            L.astcenc_amd_generate_mip_chain_weighted_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int,
+                                                                         C.c_int, C.c_uint, C.POINTER(MipOptions), C.POINTER(MipFilter),
+                                                                         C.POINTER(MipWeighting), C.c_void_p, C.c_size_t, C.c_void_p]
+            L.astcenc_amd_generate_mip_chain_weighted_device.restype = C.c_int
+            L.astcenc_amd_compress_mip_chain_weighted_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int,
+                                                                         C.c_int, C.POINTER(Swizzle), C.c_uint, C.POINTER(MipOptions),
+                                                                         C.POINTER(MipFilter), C.POINTER(MipWeighting), C.c_void_p,
+                                                                         C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                         C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_mip_chain_weighted_device.restype = C.c_int
 
     # -- thin wrappers returning error codes, as the C API does --
     def config_init(self, profile, bx, by, bz, quality, flags):
@@ -547,6 +565,44 @@ class Library:
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_compress_mip_chain_filtered_device")
+        n = layout.level_count
+        ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
+        return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+
+    @staticmethod
+    def _mip_weighting(weighting):
+        """A MipWeighting, a MIP_WEIGHT_* value or None (null weighting: none) -> the ctypes argument."""
+        if weighting is None:
+            return None
+        return C.byref(weighting if isinstance(weighting, MipWeighting) else MipWeighting(weighting))
+
+    def generate_mip_chain_weighted_device(self, ctx, image, kind=MIP_VOLUME, levels=0, options=None, mip_filter=None, stream=None,
+                                           weighting=None):
+        """astcenc_amd_generate_mip_chain_weighted_device: generate_mip_chain_filtered_device with a weighting (see
+        _mip_weighting)."""
+        (w, h, d), dtype, layout, store, tensors, _ = self._mip_chain_volume_buffers(ctx, image, kind, levels, False)
+        err = self.lib.astcenc_amd_generate_mip_chain_weighted_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
+                                                                      self._mip_options(options), self._mip_filter(mip_filter),
+                                                                      self._mip_weighting(weighting), store.data_ptr(), layout.texels_len,
+                                                                      torch_stream(stream))
+        if err:
+            raise AstcError(err, "astcenc_amd_generate_mip_chain_weighted_device")
+        return tensors
+
+    def compress_mip_chain_weighted_device(self, ctx, image, kind=MIP_VOLUME, levels=0, options=None, mip_filter=None, swizzle=SWZ_RGBA,
+                                           stream=None, weighting=None):
+        """astcenc_amd_compress_mip_chain_weighted_device: compress_mip_chain_filtered_device with a weighting; returns (level
+        tensors, per-level block tensors), the kernel time of the call in self.last_kernel_ms."""
+        (w, h, d), dtype, layout, store, tensors, out = self._mip_chain_volume_buffers(ctx, image, kind, levels, True)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_mip_chain_weighted_device(ctx, image.data_ptr(), w, h, d, kind, dtype, C.byref(Swizzle(*swizzle)),
+                                                                      layout.level_count, self._mip_options(options),
+                                                                      self._mip_filter(mip_filter), self._mip_weighting(weighting),
+                                                                      store.data_ptr(), layout.texels_len, out.data_ptr(), layout.blocks_len,
+                                                                      torch_stream(stream), C.byref(ms))
+        self.last_kernel_ms = ms.value
+        if err:
+            raise AstcError(err, "astcenc_amd_compress_mip_chain_weighted_device")
         n = layout.level_count
         ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
         return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]

@@ -124,7 +124,8 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_images_device(
  *   - F16 / F32: per y tap in increasing row, row = sum over the x taps (increasing x) of w_x * v, acc = sum over the y taps of
  *     w_y * row (each sum starting at its first product), all float64; then acc / den in float64, rounded to float32, then
  *     to F16 for F16 levels (round to nearest even both times);
- *   - channels are independent (no premultiplication; renormalisation and coverage: the options of the _ex_ calls below);
+ *   - channels are independent (no premultiplication: for straight-alpha textures the _weighted_ calls below weight the colour
+ *     by alpha; renormalisation and coverage: the options of the _ex_ calls below);
  *     the swizzle does not touch the levels, it applies when they are compressed. */
 #define ASTCENC_AMD_MAX_MIP_LEVELS 32
 
@@ -396,6 +397,80 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_filtered_device
 	unsigned int level_count,
 	const struct astcenc_amd_mip_options* options,
 	const struct astcenc_amd_mip_filter* filter,
+	void* device_levels, size_t levels_len,
+	void* device_blocks, size_t blocks_len,
+	void* hip_stream,
+	float* kernel_ms);
+
+/* Mip chain weighting: colour filtered with alpha as its weight.
+ *
+ * The plain filter averages the four channels independently, so the colour stored under fully transparent texels -- which
+ * nobody sees at level 0 -- is averaged into the visible edge of a cut-out shape and every level below 0 shows a fringe of it.
+ * With ASTCENC_AMD_MIP_WEIGHT_ALPHA channels 0-2 of a destination texel are the mean of the source colours weighted by
+ * tap weight x alpha.  Use it for textures with straight (non-premultiplied) alpha: foliage, decals, sprites, UI.  A texture
+ * whose colour is already premultiplied by alpha wants the plain filter.
+ *
+ * astcenc_amd_generate_mip_chain_weighted_device and astcenc_amd_compress_mip_chain_weighted_device take the arguments of the
+ * _filtered_ calls plus `weighting` after `filter`.  A null `weighting`, or weight == ASTCENC_AMD_MIP_WEIGHT_NONE, gives exactly
+ * the _filtered_ calls' bytes through their kernels.  An unknown weight returns ASTCENC_ERR_BAD_PARAM with nothing written,
+ * named "weighting" in the log; it is checked with the other arguments before anything is launched.  The weighting works with
+ * every kind of chain, data type, filter and edge, in sRGB contexts, with both options (still post-passes over the finished
+ * chain) and with compression.  Level sizes, offsets and the layout calls, the checks, error codes, stream order, cancel,
+ * progress and kernel_ms are the _filtered_ calls'; level 0 is never written and level i+1 is filtered from level i as stored.
+ *
+ * The arithmetic, exactly (a numpy model reproduces it bit for bit).  A stored texel is (c0, c1, c2, a).  "The plain filter"
+ * is the arithmetic above for the same filter, kind and type; "the plain sums" are its row / acc / vol sums: the same taps in
+ * the same order, each sum starting at its first product, one rounded IEEE operation at a time, no fused operations.  Channel
+ * 3 of every level is byte for byte the plain filter's; the weighting changes channels 0-2 only:
+ *   - box, linear U8 (integers only): W = w_x * w_y * w_z per tap, SA = sum W a and SP_c = sum W a c, both exact.  SA > 0:
+ *     (2 SP_c + SA) / (2 SA) floored, the exact weighted mean rounded to nearest, ties up (never above 255).  SA == 0: the
+ *     plain filter's result;
+ *   - box, U8 in an ASTCENC_PRF_LDR_SRGB context, channels 0-2: the value of a tap is (double)a * lin[c] (one rounded multiply,
+ *     lin the EOTF table), volP_c the plain sums over those values before any division, SA the integer above.  SA > 0: the
+ *     sRGB encode of volP_c / (double)SA.  SA == 0: the plain filter's result;
+ *   - box, F16 / F32: the value of a tap is (double)a * (double)c (exact in float64), volP_c the plain sums over those values,
+ *     volA the plain sums over (double)a (the plain filter's own alpha sum).  volA > 0.0: (float)(volP_c / volA), F16 that
+ *     float rounded to half as the filter rounds.  Otherwise -- a zero, a negative or a NaN volA -- the plain filter's result.
+ *     Nothing else is special-cased: infinities and negative alphas follow IEEE;
+ *   - windowed filters: the same definitions with the normalised float64 tap weights.  Values: (double)(a * c) and (double)a
+ *     for linear U8, (double)a * lin[c] for sRGB, (double)a * (double)c for floats; volP_c and volA are the plain separable
+ *     sums over them.  volA > 0.0: m = volP_c / volA, and the result is clamp(floor(m + 0.5), 0, 255) for linear U8 (clamped in
+ *     float64 before the conversion: a tiny volA from negative lobes can make m huge), the sRGB encode of m for sRGB,
+ *     (float)m for floats.  Otherwise the plain filter's result.
+ * Falling back to the plain result is the limit of the "alpha + epsilon" weight other resizers use: it keeps the colour that was
+ * authored under fully transparent regions, which bilinear sampling at an edge still reads, instead of turning it black. */
+enum astcenc_amd_mip_weight {
+	ASTCENC_AMD_MIP_WEIGHT_NONE  = 0,      /* the plain filter of the calls above */
+	ASTCENC_AMD_MIP_WEIGHT_ALPHA = 1       /* channels 0-2 weighted by channel 3 */
+};
+struct astcenc_amd_mip_weighting {
+	enum astcenc_amd_mip_weight weight;
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_generate_mip_chain_weighted_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	unsigned int level_count,
+	const struct astcenc_amd_mip_options* options,
+	const struct astcenc_amd_mip_filter* filter,
+	const struct astcenc_amd_mip_weighting* weighting,
+	void* device_levels, size_t levels_len,
+	void* hip_stream);
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_weighted_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	unsigned int level_count,
+	const struct astcenc_amd_mip_options* options,
+	const struct astcenc_amd_mip_filter* filter,
+	const struct astcenc_amd_mip_weighting* weighting,
 	void* device_levels, size_t levels_len,
 	void* device_blocks, size_t blocks_len,
 	void* hip_stream,
