@@ -261,7 +261,8 @@ static astcenc_error check_mip_options(const char* fn, const astcenc_context* ct
 	return ASTCENC_SUCCESS;
 }
 
-/* The filter of the _filtered_ calls (null: the box) into the job: the box leaves it as it is (kind 0, the box kernels). */
+/* The filter of the _filtered_ calls (null: the box) into the job (its kind and dimensions set): the box leaves it as it is (kind 0,
+ * the box kernels). */
 static astcenc_error check_mip_filter(const char* fn, const astcenc_amd_mip_filter* filter, MipChainJob& gen)
 {
 	if (!filter) return ASTCENC_SUCCESS;
@@ -271,9 +272,16 @@ static astcenc_error check_mip_filter(const char* fn, const astcenc_amd_mip_filt
 		backend_log("%s: filter->kind %d is not an astcenc_amd_mip_filter_kind", fn, kind);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
-	if (edge != ASTCENC_AMD_MIP_EDGE_CLAMP && edge != ASTCENC_AMD_MIP_EDGE_WRAP)
+	if (edge < ASTCENC_AMD_MIP_EDGE_CLAMP || edge > ASTCENC_AMD_MIP_EDGE_CUBE)
 	{
 		backend_log("%s: filter->edge %d is not an astcenc_amd_mip_edge", fn, edge);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	// (a cube map: square faces, six layers to a cube; checked for the box too, which never leaves a face)
+	if (edge == ASTCENC_AMD_MIP_EDGE_CUBE && (gen.kind != ASTCENC_AMD_MIP_ARRAY || gen.dim_x != gen.dim_y || gen.dim_z % 6u != 0))
+	{
+		backend_log("%s: filter->edge ASTCENC_AMD_MIP_EDGE_CUBE needs kind ASTCENC_AMD_MIP_ARRAY, dim_x == dim_y and dim_z %% 6 == 0 "
+		            "(kind %u, dim_x %u, dim_y %u, dim_z %u)", fn, gen.kind, gen.dim_x, gen.dim_y, gen.dim_z);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	if (kind == ASTCENC_AMD_MIP_FILTER_BOX) return ASTCENC_SUCCESS;

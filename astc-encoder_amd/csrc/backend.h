@@ -271,6 +271,9 @@ int astc_mip_weighted_launch(const MipChainJob& job, const void* d_srgb, void* s
 int astc_mip_filter_table_build(const MipChainJob& job, std::vector<uint8_t>& out);
 int astc_mip_filter_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream);
 int astc_mip_filter_weighted_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream);
+/* ... with job.filter_edge == MIP_EDGE_CUBE (kernel_mip_cube.hip), plain or weighted, from the same table: an ARRAY of square
+ * layers, six to a cube (the caller has checked it). */
+int astc_mip_cube_launch(const MipChainJob& job, const void* d_table, const void* d_srgb, void* stream);
 /* ... and its post-passes (kernel_mip_post.hip), queued after the generation of the same job when job.post_flags != 0.
  * d_scratch: astc_mip_post_scratch_bytes(job) bytes of device memory (0 when no scratch is needed; never above 64 MiB). */
 size_t astc_mip_post_scratch_bytes(const MipChainJob& job);

@@ -8,6 +8,7 @@
 // is one kernel launch; chunks give the host cancel/progress points.
 #include "backend.h"
 #include "kernel_jit.h"
+#include "mip_resample.h"
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -1356,8 +1357,9 @@ static int generate_mips_locked(DeviceSlot* s, hipStream_t stream, const MipChai
 	if (job.filter_kind)
 	{
 		HIP_TRY(hipMemcpyAsync(s->d_mip_filter, s->h_mip_filter.data(), s->h_mip_filter.size(), hipMemcpyHostToDevice, stream), return 2);
-		const int frc = job.weight ? astc_mip_filter_weighted_launch(job, s->d_mip_filter, s->d_srgb, stream)
-		                           : astc_mip_filter_launch(job, s->d_mip_filter, s->d_srgb, stream);
+		const int frc = job.filter_edge == MIP_EDGE_CUBE ? astc_mip_cube_launch(job, s->d_mip_filter, s->d_srgb, stream)
+		                : job.weight ? astc_mip_filter_weighted_launch(job, s->d_mip_filter, s->d_srgb, stream)
+		                : astc_mip_filter_launch(job, s->d_mip_filter, s->d_srgb, stream);
 		if (frc != 0) { log_msg("mip filter kernel launch failed (hip error %d)", frc); return 2; }
 	}
 	else

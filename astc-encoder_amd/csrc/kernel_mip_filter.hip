@@ -24,43 +24,6 @@ struct MipRsShared {
 	double srgb[MIP_SRGB_TABLE_DOUBLES];                    // lin[256], then thr[255] (sRGB data only)
 };
 
-/* The values of source texel i (component loads: the caller's level 0 needs only the alignment of its components). */
-template <int K>
-__device__ inline void mip_rs_load(const void* src, size_t i, const double* lin, double v[4])
-{
-	if constexpr (K == MIP_RS_U8 || K == MIP_RS_U8_SRGB)
-		mip_resample_load_u8(static_cast<const uint32_t*>(src)[i], K == MIP_RS_U8_SRGB ? lin : nullptr, v);
-	else if constexpr (K == MIP_RS_F16)
-	{
-		const uint16_t* p = static_cast<const uint16_t*>(src) + 4 * i;
-		const float f[4] = { mip_float_from_half(p[0]), mip_float_from_half(p[1]), mip_float_from_half(p[2]), mip_float_from_half(p[3]) };
-		mip_resample_load_float(f, v);
-	}
-	else
-	{
-		const float* p = static_cast<const float*>(src) + 4 * i;
-		const float f[4] = { p[0], p[1], p[2], p[3] };
-		mip_resample_load_float(f, v);
-	}
-}
-
-template <int K>
-__device__ inline void mip_rs_store(void* dst, size_t i, const double vol[4], const double* thr)
-{
-	if constexpr (K == MIP_RS_U8 || K == MIP_RS_U8_SRGB)
-		static_cast<uint32_t*>(dst)[i] = mip_resample_out_u8(vol, K == MIP_RS_U8_SRGB ? thr : nullptr);
-	else
-	{
-		float f[4];
-		mip_resample_out_float(vol, f);
-		if constexpr (K == MIP_RS_F16)
-			static_cast<uint2*>(dst)[i] = make_uint2((uint32_t)mip_half_from_float(f[0]) | ((uint32_t)mip_half_from_float(f[1]) << 16),
-			                                         (uint32_t)mip_half_from_float(f[2]) | ((uint32_t)mip_half_from_float(f[3]) << 16));
-		else
-			static_cast<float4*>(dst)[i] = make_float4(f[0], f[1], f[2], f[3]);
-	}
-}
-
 /* Tile `tile` of level L (tiles in x, then y, then slice order).  Every thread of the workgroup calls it (it has barriers). */
 template <int K>
 __device__ void mip_rs_tile(const uint8_t* table, const MipRsLevel& L, size_t tile, MipRsShared& sh)

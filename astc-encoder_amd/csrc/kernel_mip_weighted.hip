@@ -15,7 +15,6 @@
 // the file.
 #include "mip_kernels.h"
 #include "mip_filter_kernels.h"
-#include "mip_weighted.h"
 
 namespace astcd {
 
@@ -372,49 +371,11 @@ namespace {
 
 /* The weighted tile: mip_rs_tile with seven values per source texel and MIP_RSW_TX columns (tile index: x, then y, then slice,
  * with the tile's own tiles_x). */
-constexpr uint32_t MIP_RSW_TX = 16;
-static_assert(MIP_RSW_TX * MIP_RS_TY == MIP_RS_THREADS, "one destination texel per thread");
 
 struct MipRswShared {
 	double rows[MIP_RS_ROWS][MIP_RSW_TX][MIP_WEIGHTED_VALUES];
 	double srgb[MIP_SRGB_TABLE_DOUBLES];
 };
-
-template <int K>
-__device__ inline void mip_rsw_load(const void* src, size_t i, const double* lin, double v[7])
-{
-	if constexpr (K == MIP_RS_U8 || K == MIP_RS_U8_SRGB)
-		mip_resample_load_u8_weighted(static_cast<const uint32_t*>(src)[i], K == MIP_RS_U8_SRGB ? lin : nullptr, v);
-	else if constexpr (K == MIP_RS_F16)
-	{
-		const uint16_t* p = static_cast<const uint16_t*>(src) + 4 * i;
-		const float f[4] = { mip_float_from_half(p[0]), mip_float_from_half(p[1]), mip_float_from_half(p[2]), mip_float_from_half(p[3]) };
-		mip_resample_load_float_weighted(f, v);
-	}
-	else
-	{
-		const float* p = static_cast<const float*>(src) + 4 * i;
-		const float f[4] = { p[0], p[1], p[2], p[3] };
-		mip_resample_load_float_weighted(f, v);
-	}
-}
-
-template <int K>
-__device__ inline void mip_rsw_store(void* dst, size_t i, const double vol[7], const double* thr)
-{
-	if constexpr (K == MIP_RS_U8 || K == MIP_RS_U8_SRGB)
-		static_cast<uint32_t*>(dst)[i] = mip_resample_out_u8_weighted(vol, K == MIP_RS_U8_SRGB ? thr : nullptr);
-	else
-	{
-		float f[4];
-		mip_resample_out_float_weighted(vol, f);
-		if constexpr (K == MIP_RS_F16)
-			static_cast<uint2*>(dst)[i] = make_uint2((uint32_t)mip_half_from_float(f[0]) | ((uint32_t)mip_half_from_float(f[1]) << 16),
-			                                         (uint32_t)mip_half_from_float(f[2]) | ((uint32_t)mip_half_from_float(f[3]) << 16));
-		else
-			static_cast<float4*>(dst)[i] = make_float4(f[0], f[1], f[2], f[3]);
-	}
-}
 
 __device__ inline uint32_t mip_rsw_tiles_x(const MipRsLevel& L) { return (L.dx + MIP_RSW_TX - 1) / MIP_RSW_TX; }
 

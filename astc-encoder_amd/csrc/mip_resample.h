@@ -6,8 +6,8 @@
 // with mip_resample_out_*.  tests/mip_filter_model.py reproduces all of it bit for bit with Python floats (math.sin is the same
 // C library function).
 //
-// No includes and no HIP types: kernel_mip_filter.hip builds its kernels on these functions and tests/test_mip_filter_cpu.py
-// compiles the header with g++.
+// No includes and no HIP types: kernel_mip_filter.hip and kernel_mip_cube.hip build their kernels on these functions and
+// tests/test_mip_filter_cpu.py and tests/test_mip_cube_cpu.py compile the header with g++.
 #pragma once
 
 #include "mip_filter.h"
@@ -16,7 +16,7 @@ namespace astcd {
 
 // = enum astcenc_amd_mip_filter_kind / astcenc_amd_mip_edge
 enum MipFilterKind { MIP_FILTER_BOX = 0, MIP_FILTER_MITCHELL = 1, MIP_FILTER_LANCZOS3 = 2, MIP_FILTER_KAISER = 3 };
-enum MipFilterEdge { MIP_EDGE_CLAMP = 0, MIP_EDGE_WRAP = 1 };
+enum MipFilterEdge { MIP_EDGE_CLAMP = 0, MIP_EDGE_WRAP = 1, MIP_EDGE_CUBE = 2 };
 constexpr unsigned int MIP_RESAMPLE_MAX_TAPS = 17;      // s = 3 with support 3
 
 /* The support S of a windowed filter: taps have |t| < S. */
@@ -106,7 +106,7 @@ inline unsigned int mip_resample_taps(int kind, unsigned int s, unsigned int j, 
 }
 
 /* The source texel of tap index i (any integer, here within 9 of [0, s)): CLAMP clamp(i, 0, s - 1), WRAP the non-negative
- * i mod s. */
+ * i mod s.  (CUBE maps x and y together, mip_cube_source; an axis on its own clamps.) */
 ASTC_MIP_FN unsigned int mip_resample_source(long long i, unsigned int s, unsigned int edge)
 {
 	if (i >= 0 && i < (long long)s) return (unsigned int)i;
@@ -116,6 +116,47 @@ ASTC_MIP_FN unsigned int mip_resample_source(long long i, unsigned int s, unsign
 		return (unsigned int)(m < 0 ? m + (long long)s : m);
 	}
 	return i < 0 ? 0u : s - 1u;
+}
+
+/* MIP_EDGE_CUBE (include/astcenc_amd.h, "Cube edges"): the texel that tap (ix, iy) of face `face` reads in a cube of s x s
+ * faces, faces in the order +X, -X, +Y, -Y, +Z, -Z.  Both indices inside [0, s): the texel itself.  Both outside: the face's
+ * own corner texel.  One outside, on side 0 (x < 0), 1 (x >= s), 2 (y < 0) or 3 (y >= s): with p the index that is inside,
+ * k the overshoot (index - s or -1 - index) and kk = min(k, s - 1), the neighbour's texel at depth kk from the shared edge.
+ * Unfolding the neighbour with the face frames of the GL table (P' = sg s A + (s - (2 kk + 1)) M_f + W, x' = (P' . S_f' + s - 1)
+ * / 2, y' likewise) makes each of x' and y' one of p, s - 1 - p, kk, s - 1 - kk, so the 24 (face, side) pairs fit a table of
+ * bytes: bits 0-2 the neighbour, bits 3-4 the form of x', bits 5-6 that of y' (bit 0 of a form: mirrored, s - 1 - v; bit 1:
+ * v = kk instead of p).  tests/mip_cube_model.py works the frames out in full and tests/test_mip_cube_cpu.py compares. */
+struct MipCubeTexel {
+	unsigned int face, x, y;
+};
+
+ASTC_MIP_FN MipCubeTexel mip_cube_source(unsigned int face, long long ix, long long iy, unsigned int s)
+{
+	const long long n = (long long)s;
+	const bool in_x = ix >= 0 && ix < n, in_y = iy >= 0 && iy < n;
+	MipCubeTexel t;
+	t.face = face;
+	if (in_x == in_y)
+	{
+		t.x = in_x ? (unsigned int)ix : ix < 0 ? 0u : s - 1u;
+		t.y = in_y ? (unsigned int)iy : iy < 0 ? 0u : s - 1u;
+		return t;
+	}
+	const long long out = in_x ? iy : ix;
+	const unsigned int side = (in_x ? 2u : 0u) + (out < 0 ? 0u : 1u);
+	const unsigned int p = (unsigned int)(in_x ? ix : iy);
+	const long long k = out < 0 ? -1 - out : out - n;
+	const unsigned int kk = k < n - 1 ? (unsigned int)k : s - 1u;
+	// entry face * 4 + side, eight to a word, entry 0 in the low byte
+	const unsigned int e = face * 4u + side;
+	const unsigned long long word = e < 8u ? 0x3312141D1B3A151Cull : e < 16u ? 0x6D646069444D4841ull : 0x6B4A111843621019ull;
+	const unsigned int code = (unsigned int)(word >> (8u * (e & 7u))) & 0xFFu;
+	const unsigned int fx = (code >> 3) & 3u, fy = (code >> 5) & 3u;
+	const unsigned int vx = fx & 2u ? kk : p, vy = fy & 2u ? kk : p;
+	t.face = code & 7u;
+	t.x = fx & 1u ? s - 1u - vx : vx;
+	t.y = fy & 1u ? s - 1u - vy : vy;
+	return t;
 }
 
 /* The float64 channel values of a stored texel: U8 (double)code, or lin[code] for channels 0-2 of sRGB data (lin = the sRGB
@@ -201,6 +242,27 @@ inline void mip_resample_texel(const MipResampleTaps& tx, const MipResampleTaps&
 		}
 		mip_resample_accumulate(vol, tz.w[kz], acc, kz);
 	}
+}
+
+/* ... of face `face` of a cube with MIP_EDGE_CUBE (tx.s == ty.s, no z filter: a layer reads its own cube): the same sums, each
+ * tap read from mip_cube_source; load(face, x, y, double v[4]).  Taps that land on the same texel are not merged. */
+template <typename Load>
+inline void mip_resample_texel_cube(unsigned int face, const MipResampleTaps& tx, const MipResampleTaps& ty, Load load, double vol[4])
+{
+	double acc[4] = { 0.0, 0.0, 0.0, 0.0 };
+	for (unsigned int ky = 0; ky < ty.count; ky++)
+	{
+		double row[4] = { 0.0, 0.0, 0.0, 0.0 };
+		for (unsigned int kx = 0; kx < tx.count; kx++)
+		{
+			const MipCubeTexel t = mip_cube_source(face, tx.first + kx, ty.first + ky, tx.s);
+			double v[4];
+			load(t.face, t.x, t.y, v);
+			mip_resample_accumulate(row, tx.w[kx], v, kx);
+		}
+		mip_resample_accumulate(acc, ty.w[ky], row, ky);
+	}
+	mip_resample_accumulate(vol, 1.0, acc, 0);
 }
 
 } // namespace astcd

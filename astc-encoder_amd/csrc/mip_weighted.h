@@ -240,4 +240,24 @@ inline void mip_resample_texel_weighted(const MipResampleTaps& tx, const MipResa
 	}
 }
 
+/* ... and of a cube face with MIP_EDGE_CUBE (mip_resample_texel_cube with seven values): load(face, x, y, double v[7]). */
+template <typename Load>
+inline void mip_resample_texel_cube_weighted(unsigned int face, const MipResampleTaps& tx, const MipResampleTaps& ty, Load load, double vol[7])
+{
+	double acc[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+	for (unsigned int ky = 0; ky < ty.count; ky++)
+	{
+		double row[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+		for (unsigned int kx = 0; kx < tx.count; kx++)
+		{
+			const MipCubeTexel t = mip_cube_source(face, tx.first + kx, ty.first + ky, tx.s);
+			double v[7];
+			load(t.face, t.x, t.y, v);
+			mip_resample_accumulate7(row, tx.w[kx], v, kx);
+		}
+		mip_resample_accumulate7(acc, ty.w[ky], row, ky);
+	}
+	mip_resample_accumulate7(vol, 1.0, acc, 0);
+}
+
 } // namespace astcd

@@ -103,7 +103,7 @@ MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
 MIP_NORMALIZE, MIP_ALPHA_COVERAGE = 0x1, 0x2
 MIP_FILTER_BOX, MIP_FILTER_MITCHELL, MIP_FILTER_LANCZOS3, MIP_FILTER_KAISER = 0, 1, 2, 3
-MIP_EDGE_CLAMP, MIP_EDGE_WRAP = 0, 1
+MIP_EDGE_CLAMP, MIP_EDGE_WRAP, MIP_EDGE_CUBE = 0, 1, 2
 MIP_WEIGHT_NONE, MIP_WEIGHT_ALPHA = 0, 1
 
 

@@ -188,8 +188,8 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_device(
  *
  *   - ASTCENC_AMD_MIP_ARRAY: dim_z independent 2D layers (array layers; a cube map is an array of 6 * n layers, face-major
  *     within each array element, the KTX order).  x and y halve, the layer count stays; the full chain is counted from x and y
- *     alone.  Layer l of level i is byte for byte what astcenc_amd_generate_mip_chain_device makes from layer l alone (faces
- *     are filtered independently: no seamless cube filtering).  A 3D footprint (block_z > 1) is ASTCENC_ERR_BAD_PARAM: its
+ *     alone.  Layer l of level i is byte for byte what astcenc_amd_generate_mip_chain_device makes from layer l alone (the box
+ *     filter never reads outside a face; the windowed filters below have ASTCENC_AMD_MIP_EDGE_CUBE).  A 3D footprint (block_z > 1) is ASTCENC_ERR_BAD_PARAM: its
  *     blocks would mix layers.
  *   - ASTCENC_AMD_MIP_VOLUME: one 3D image.  Level i is max(1, d >> i) on all three axes; the full chain has
  *     floor(log2(max(dim_x, dim_y, dim_z))) + 1 levels.  The filter gains a z axis with the taps of x and y: linear U8 texels
@@ -331,7 +331,7 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_ex_device(
  * layout calls are unchanged; everything else -- the argument checks, all before anything is launched; error codes with nothing
  * written; stream order, cancel, progress and kernel_ms; the options, applied after the whole chain has been generated -- is the
  * _ex_ calls'.  An unknown kind or edge returns ASTCENC_ERR_BAD_PARAM with nothing written, named "filter" in the log.  2D images
- * are the VOLUME of depth 1; ARRAY layers (cube faces) are filtered independently, with no seamless cube filtering; a VOLUME's z
+ * are the VOLUME of depth 1; ARRAY layers are filtered independently unless the edge is CUBE ("Cube edges" below); a VOLUME's z
  * axis takes the same filter.  Every level is filtered from the level above it as stored.
  *
  * The filter, exactly (a numpy model reproduces it bit for bit):
@@ -339,7 +339,8 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_ex_device(
  *     r = (double)s / (double)d and destination j has the centre c = (double)((2j + 1) * s) / (double)(2d) (the product in 64-bit
  *     integers); its taps are every integer i with |t| < S, t = (((double)i + 0.5) - c) / r, in increasing i, S the support;
  *     f is evaluated on a = |t|, and w_i = f_i / sum, sum = f_first + ... in increasing i.  Tap i reads source texel
- *     clamp(i, 0, s - 1) (CLAMP) or the non-negative i mod s (WRAP); taps on the same texel are not merged;
+ *     clamp(i, 0, s - 1) (CLAMP) or the non-negative i mod s (WRAP); CUBE maps x and y together (below); taps on the same texel
+ *     are not merged;
  *   - the functions, a2 = a * a, a3 = a2 * a, every operation a separate IEEE double operation in the order written:
  *       MITCHELL (B = C = 1/3, S = 2): a < 1: ((7.0 * a3 - 12.0 * a2) + 16.0 / 3.0) / 6.0,
  *                                      else ((((-7.0 / 3.0) * a3 + 12.0 * a2) - 20.0 * a) + 32.0 / 3.0) / 6.0;
@@ -357,6 +358,51 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_ex_device(
  *     vol >= EOTF((c - 0.5) / 255), channel 3 linear; F32 (float)vol; F16 that float to half (round to nearest even both times).
  *     Float data is not clamped: negative lobes may ring.
  *
+ * Cube edges (ASTCENC_AMD_MIP_EDGE_CUBE): a tap that leaves a cube face reads the neighbouring face, so that both sides of a cube
+ * edge are filtered from the same data.  CLAMP smears a face's border texel outwards and WRAP reads the opposite side of the same
+ * face; either shows as a line along the cube's edges in sky boxes and reflection probes.
+ *   - Where it is valid: kind == ASTCENC_AMD_MIP_ARRAY, dim_x == dim_y and dim_z % 6 == 0.  Anything else returns
+ *     ASTCENC_ERR_BAD_PARAM with nothing written, named "filter" in the log, checked with the other arguments before anything is
+ *     launched.  The check applies to every filter kind, the box included; a valid CUBE with ASTCENC_AMD_MIP_FILTER_BOX gives
+ *     exactly the _ex_ calls' bytes through the box kernels, as the other edges do.
+ *   - Layers: layer l is face l % 6 of cube l / 6, faces in the KTX / GL order +X, -X, +Y, -Y, +Z, -Z.  Cubes never read each
+ *     other.
+ *   - Face frames: face f has a major axis M_f and the directions S_f (x grows along it) and T_f (y grows along it), the GL
+ *     cube-map table:
+ *         f  face  M           S           T
+ *         0  +X    ( 1, 0, 0)  ( 0, 0,-1)  ( 0,-1, 0)
+ *         1  -X    (-1, 0, 0)  ( 0, 0, 1)  ( 0,-1, 0)
+ *         2  +Y    ( 0, 1, 0)  ( 1, 0, 0)  ( 0, 0, 1)
+ *         3  -Y    ( 0,-1, 0)  ( 1, 0, 0)  ( 0, 0,-1)
+ *         4  +Z    ( 0, 0, 1)  ( 1, 0, 0)  ( 0,-1, 0)
+ *         5  -Z    ( 0, 0,-1)  (-1, 0, 0)  ( 0,-1, 0)
+ *     In doubled integer units the centre of texel (x, y) of a face of s x s texels is P = s M_f + U S_f + V T_f with
+ *     U = 2x + 1 - s, V = 2y + 1 - s.
+ *   - The source texel of a tap: taps, weights, tap order and every sum are those of the filter above.  Only the texel that a
+ *     tap (ix, iy) of face f reads changes, for a source face of s texels:
+ *       - ix and iy both inside [0, s): texel (ix, iy) of face f;
+ *       - exactly one of them outside: the neighbouring face, unfolded flat across the shared edge.  Let A be the direction of
+ *         the axis that is outside (S_f for x, T_f for y), sg = +1 when the index is >= s and -1 when it is < 0, k the overshoot
+ *         (index - s or -1 - index), kk = min(k, s - 1), and W the in-range coordinate's doubled value times its direction
+ *         (V T_f or U S_f).  Then P' = sg s A + (s - (2 kk + 1)) M_f + W.  The face read is the f' with M_f' = sg A, and the
+ *         texel is x' = (P' . S_f' + s - 1) / 2, y' = (P' . T_f' + s - 1) / 2 (both divisions exact).  In words: overshoot k
+ *         reads the neighbour's texel at depth k from the shared edge, at the same position along the edge; that texel is the
+ *         mirror image of this face's own texel at depth k through the plane that holds the shared edge and the cube's centre.
+ *         The depth stops at the neighbour's far side (kk): small faces have taps that reach further than one face (s = 3
+ *         reaches 7 texels out);
+ *       - both outside (the corner quadrant, where no face lies): the face's own corner texel, (clamp(ix), clamp(iy)) of face
+ *         f.  The rule is symmetric in x and y and reads a texel that touches the corner;
+ *       - s == 1 has one tap on texel 0 and never leaves the face.
+ *     The neighbours this yields, for x < 0, x >= s, y < 0, y >= s: +X: +Z, -Z, +Y, -Y; -X: -Z, +Z, +Y, -Y; +Y: -X, +X, -Z, +Z;
+ *     -Y: -X, +X, +Z, -Z; +Z: -X, +X, +Y, -Y; -Z: +X, -X, +Y, -Y.
+ *   - Everything else is unchanged: values, the float64 row / acc sums in increasing tap order (a layer has the one z tap of
+ *     weight 1.0), rounding, the sRGB tables, F16 conversion, level sizes, level i + 1 from level i as stored, the options as
+ *     post-passes (coverage surfaces stay one per face), stream order, cancel, progress, kernel_ms, compression as an image set
+ *     of one entry per level.  With ASTCENC_AMD_MIP_WEIGHT_ALPHA (below) the weighted values are read through the same mapping;
+ *     channel 3 stays byte for byte the plain CUBE filter's.
+ *   Not done: solid-angle weighting, averaging the three texels at a cube corner, or making opposite border texels equal; results
+ *   are not bit-equal under rotations of the cube (the sums run in increasing x, then y).
+ *
  * The taps live in library scratch (no caller memory), one row per destination texel of an odd axis and one per even axis below
  * 2^26 texels; when they exceed the library's 64 MiB scratch bound (odd axes of several hundred thousand texels) or cannot be
  * allocated, the call returns ASTCENC_ERR_OUT_OF_MEM with nothing written.
@@ -369,7 +415,7 @@ enum astcenc_amd_mip_filter_kind {
 	ASTCENC_AMD_MIP_FILTER_LANCZOS3 = 2,   /* sinc(t) sinc(t/3), support 3 */
 	ASTCENC_AMD_MIP_FILTER_KAISER   = 3    /* sinc(t) I0(4 sqrt(1 - (t/3)^2)) / I0(4), support 3 */
 };
-enum astcenc_amd_mip_edge { ASTCENC_AMD_MIP_EDGE_CLAMP = 0, ASTCENC_AMD_MIP_EDGE_WRAP = 1 };
+enum astcenc_amd_mip_edge { ASTCENC_AMD_MIP_EDGE_CLAMP = 0, ASTCENC_AMD_MIP_EDGE_WRAP = 1, ASTCENC_AMD_MIP_EDGE_CUBE = 2 };
 struct astcenc_amd_mip_filter {
 	enum astcenc_amd_mip_filter_kind kind;
 	enum astcenc_amd_mip_edge edge;
