@@ -11,6 +11,7 @@
 #include "../../include/astcenc_amd.h"
 #include "backend.h"
 #include "entry_internal.h"
+#include "mip_resize.h"
 
 #include <cstring>
 #include <vector>
@@ -449,6 +450,111 @@ astcenc_error astcenc_amd_compress_mip_chain_weighted_device(astcenc_context* ct
 	return compress_mip_chain("astcenc_amd_compress_mip_chain_weighted_device", ctx, device_image, dim_x, dim_y, dim_z, kind, data_type,
 	                          swizzle, level_count, options, filter, weighting, device_levels, levels_len, device_blocks, blocks_len,
 	                          hip_stream, kernel_ms);
+}
+
+/* Resizing (mip_resize.h, kernel_resize.hip).  Everything is checked before anything is launched. */
+astcenc_error astcenc_amd_resize_image_device(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y,
+                                              unsigned int dim_z, astcenc_amd_mip_kind kind, astcenc_type data_type,
+                                              const struct astcenc_amd_resize* resize, void* device_out, size_t out_len, void* hip_stream,
+                                              float* kernel_ms)
+{
+	const char* fn = "astcenc_amd_resize_image_device";
+	if (!ctx) return ASTCENC_ERR_BAD_PARAM;
+	if (!resize) { backend_log("%s: resize is null", fn); return ASTCENC_ERR_BAD_PARAM; }
+	if (dim_x == 0 || dim_y == 0 || dim_z == 0 || (int)data_type < ASTCENC_TYPE_U8 || (int)data_type > ASTCENC_TYPE_F32 ||
+	    (kind != ASTCENC_AMD_MIP_ARRAY && kind != ASTCENC_AMD_MIP_VOLUME))
+	{
+		backend_log("%s: dim_x %u, dim_y %u, dim_z %u, kind %d, data_type %d: bad image", fn, dim_x, dim_y, dim_z, (int)kind, (int)data_type);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (resize->dim_x == 0 || resize->dim_y == 0 || resize->dim_z == 0)
+	{
+		backend_log("%s: resize->dim_x %u, dim_y %u, dim_z %u: a destination dimension is zero", fn, resize->dim_x, resize->dim_y, resize->dim_z);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	const int fkind = (int)resize->filter.kind, edge = (int)resize->filter.edge, weight = (int)resize->weighting.weight;
+	if (fkind < ASTCENC_AMD_MIP_FILTER_BOX || fkind > ASTCENC_AMD_MIP_FILTER_KAISER)
+	{
+		backend_log("%s: resize->filter.kind %d is not an astcenc_amd_mip_filter_kind", fn, fkind);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (edge == ASTCENC_AMD_MIP_EDGE_CUBE)
+	{
+		backend_log("%s: resize->filter.edge ASTCENC_AMD_MIP_EDGE_CUBE is not supported when resizing", fn);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (edge != ASTCENC_AMD_MIP_EDGE_CLAMP && edge != ASTCENC_AMD_MIP_EDGE_WRAP)
+	{
+		backend_log("%s: resize->filter.edge %d is not an astcenc_amd_mip_edge", fn, edge);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (weight != ASTCENC_AMD_MIP_WEIGHT_NONE && weight != ASTCENC_AMD_MIP_WEIGHT_ALPHA)
+	{
+		backend_log("%s: resize->weighting.weight %d is not an astcenc_amd_mip_weight", fn, weight);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (kind == ASTCENC_AMD_MIP_ARRAY && resize->dim_z != dim_z)
+	{
+		backend_log("%s: resize->dim_z %u changes the %u layers of an ASTCENC_AMD_MIP_ARRAY", fn, resize->dim_z, dim_z);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	const size_t texel_bytes = data_type == ASTCENC_TYPE_U8 ? 4 : data_type == ASTCENC_TYPE_F16 ? 8 : 16;
+	bool overflow = false;
+	(void)mul_safe(mul_safe(mul_safe(dim_x, dim_y, overflow), dim_z, overflow), texel_bytes, overflow);
+	const size_t out_bytes = mul_safe(mul_safe(mul_safe(resize->dim_x, resize->dim_y, overflow), resize->dim_z, overflow), texel_bytes, overflow);
+	if (overflow)
+	{
+		backend_log("%s: the texel bytes of the image or of resize->dim_x %u, dim_y %u, dim_z %u overflow size_t", fn, resize->dim_x,
+		            resize->dim_y, resize->dim_z);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (fkind == ASTCENC_AMD_MIP_FILTER_BOX && data_type == ASTCENC_TYPE_U8)
+	{
+		// weight x value sums must stay inside 64 bits: den_x den_y den_z 65025 < 2^63
+		const unsigned int s[3] = { dim_x, dim_y, kind == ASTCENC_AMD_MIP_VOLUME ? dim_z : 1u };
+		const unsigned int d[3] = { resize->dim_x, resize->dim_y, kind == ASTCENC_AMD_MIP_VOLUME ? resize->dim_z : 1u };
+		unsigned __int128 den = 65025u;
+		for (int a = 0; a < 3; a++)
+			if (!mip_resize_passes(s[a], d[a])) den *= s[a] / mip_resize_gcd(s[a], d[a]);
+		if (den >= ((unsigned __int128)1 << 63))
+		{
+			backend_log("%s: resize to %u x %u x %u: the box filter's integer sums would leave 64 bits", fn, resize->dim_x, resize->dim_y,
+			            resize->dim_z);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+	}
+	if (!device_image) { backend_log("%s: device_image is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
+	if (!device_out) { backend_log("%s: device_out is null", fn); return ASTCENC_ERR_BAD_CONTEXT; }
+	if (out_len < out_bytes)
+	{
+		backend_log("%s: out_len %zu, resize->dim_x %u, dim_y %u, dim_z %u need %zu", fn, out_len, resize->dim_x, resize->dim_y, resize->dim_z,
+		            out_bytes);
+		return ASTCENC_ERR_OUT_OF_MEM;
+	}
+	ResizeJob job;
+	memset(&job, 0, sizeof(job));
+	job.device_image = device_image; job.device_out = device_out;
+	job.dim_x = dim_x; job.dim_y = dim_y; job.dim_z = dim_z;
+	job.out_x = resize->dim_x; job.out_y = resize->dim_y; job.out_z = resize->dim_z;
+	job.kind = (uint32_t)kind; job.data_type = (uint32_t)data_type;
+	job.srgb = ctx->config.profile == ASTCENC_PRF_LDR_SRGB ? 1u : 0u;
+	job.filter_kind = (uint32_t)fkind; job.filter_edge = (uint32_t)edge; job.weight = (uint32_t)weight;
+	job.stream = hip_stream; job.kernel_ms = kernel_ms;
+	const astcenc_error status = rc_to_error(backend_resize(ctx->backend, job));
+	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: device_out or hip_stream is not on the device of device_image", fn);
+	if (status == ASTCENC_ERR_OUT_OF_MEM) backend_log("%s: the taps of resize->dim_x %u, dim_y %u, dim_z %u do not fit the scratch bound", fn,
+	                                                  resize->dim_x, resize->dim_y, resize->dim_z);
+	return status;
+}
+
+astcenc_error astcenc_amd_resize_dims(unsigned int dim_x, unsigned int dim_y, unsigned int max_dim, astcenc_amd_resize_pow2 pow2,
+                                      unsigned int* out_x, unsigned int* out_y)
+{
+	if (!out_x || !out_y || (int)pow2 < ASTCENC_AMD_POW2_NONE || (int)pow2 > ASTCENC_AMD_POW2_PREVIOUS) return ASTCENC_ERR_BAD_PARAM;
+	unsigned int x, y;
+	if (!mip_resize_dims(dim_x, dim_y, max_dim, (unsigned int)pow2, &x, &y)) return ASTCENC_ERR_BAD_PARAM;
+	*out_x = x; *out_y = y;
+	return ASTCENC_SUCCESS;
 }
 
 astcenc_error astcenc_amd_mip_chain_layout(const astcenc_config* config, unsigned int dim_x, unsigned int dim_y, astcenc_type data_type,

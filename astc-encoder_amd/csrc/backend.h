@@ -133,6 +133,17 @@ struct MipChainJob {
 	uint32_t weight;
 };
 
+/* A device image resized to out_x x out_y x out_z (astcenc_amd_resize_image_device, mip_resize.h): kind, data_type, srgb and the
+ * filter, edge and weight as in a MipChainJob; an ARRAY keeps its layers (out_z == dim_z). */
+struct ResizeJob {
+	const void* device_image;
+	void* device_out;
+	uint32_t dim_x, dim_y, dim_z, out_x, out_y, out_z, kind, data_type, srgb;
+	uint32_t filter_kind, filter_edge, weight;
+	void* stream;
+	float* kernel_ms;
+};
+
 /* ... and its decompression (astcenc_amd_decompress_images_device): every entry as a DecompressDeviceJob (stream unused). */
 struct DecompressSetJob {
 	const DecompressDeviceJob* entries;
@@ -169,6 +180,7 @@ int backend_compare(Backend* b, const CompareJob& job);
 int backend_compress_set(Backend* b, const CompressSetJob& job);
 int backend_decompress_set(Backend* b, const DecompressSetJob& job);
 int backend_generate_mips(Backend* b, const MipChainJob& job);
+int backend_resize(Backend* b, const ResizeJob& job);
 /* A line for the diagnostics callback (astcenc_amd_set_log_callback), printf-style. */
 void backend_log(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 const char* backend_name();
@@ -278,6 +290,12 @@ int astc_mip_cube_launch(const MipChainJob& job, const void* d_table, const void
  * d_scratch: astc_mip_post_scratch_bytes(job) bytes of device memory (0 when no scratch is needed; never above 64 MiB). */
 size_t astc_mip_post_scratch_bytes(const MipChainJob& job);
 int astc_mip_post_launch(const MipChainJob& job, void* d_scratch, void* stream);
+
+/* Resizing (kernel_resize.hip): astc_resize_table_build writes the taps of the job's axes into `out` on the host (0; 1 when
+ * they would exceed the library's 64 MiB scratch bound, nothing built), astc_resize_launch queues the kernel from the table's
+ * device copy d_table. */
+int astc_resize_table_build(const ResizeJob& job, std::vector<uint8_t>& out);
+int astc_resize_launch(const ResizeJob& job, const void* d_table, const void* d_srgb, void* stream);
 
 /* Image comparison launch (kernel_metrics.hip); d_sums = astc_compare_scratch_doubles() doubles of device memory,
  * the totals arrive in the first ten. */

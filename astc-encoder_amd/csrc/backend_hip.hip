@@ -1487,4 +1487,25 @@ int backend_generate_mips(Backend* b, const MipChainJob& job)
 	});
 }
 
+/* astcenc_amd_resize_image_device: the taps are sized and built first (rc 1 when they exceed the scratch bound, nothing
+ * launched), uploaded into the slot's mip filter scratch and the kernel queued behind them; kernel_ms is the kernel's. */
+int backend_resize(Backend* b, const ResizeJob& job)
+{
+	const void* ptrs[2] = { job.device_image, job.device_out };
+	return run_on_owner(b, job.device_image, ptrs, 2, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		if (astc_resize_table_build(job, s->h_mip_filter) != 0) { log_msg("resize: the taps exceed the 64 MiB scratch bound"); return 1; }
+		const size_t bytes = s->h_mip_filter.size();
+		if (grow(s->d_mip_filter, s->mip_filter_cap, bytes) != 0) return 1;
+		HIP_TRY(hipMemcpyAsync(s->d_mip_filter, s->h_mip_filter.data(), bytes, hipMemcpyHostToDevice, stream), return 2);
+		if (job.kernel_ms) HIP_TRY(hipEventRecord(s->ev0, stream), return 2);
+		const int lrc = astc_resize_launch(job, s->d_mip_filter, s->d_srgb, stream);
+		if (lrc != 0) { log_msg("resize kernel launch failed (hip error %d)", lrc); return 2; }
+		if (job.kernel_ms) HIP_TRY(hipEventRecord(s->ev1, stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		if (job.kernel_ms) HIP_TRY(hipEventElapsedTime(job.kernel_ms, s->ev0, s->ev1), return 2);
+		return 0;
+	});
+}
+
 } // namespace astcd

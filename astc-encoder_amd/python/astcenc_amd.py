@@ -97,7 +97,8 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_generate_mip_chain_volume_device", "astcenc_amd_compress_mip_chain_volume_device",
                "astcenc_amd_generate_mip_chain_ex_device", "astcenc_amd_compress_mip_chain_ex_device",
                "astcenc_amd_generate_mip_chain_filtered_device", "astcenc_amd_compress_mip_chain_filtered_device",
-               "astcenc_amd_generate_mip_chain_weighted_device", "astcenc_amd_compress_mip_chain_weighted_device"]
+               "astcenc_amd_generate_mip_chain_weighted_device", "astcenc_amd_compress_mip_chain_weighted_device",
+               "astcenc_amd_resize_image_device", "astcenc_amd_resize_dims"]
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
@@ -105,6 +106,7 @@ MIP_NORMALIZE, MIP_ALPHA_COVERAGE = 0x1, 0x2
 MIP_FILTER_BOX, MIP_FILTER_MITCHELL, MIP_FILTER_LANCZOS3, MIP_FILTER_KAISER = 0, 1, 2, 3
 MIP_EDGE_CLAMP, MIP_EDGE_WRAP, MIP_EDGE_CUBE = 0, 1, 2
 MIP_WEIGHT_NONE, MIP_WEIGHT_ALPHA = 0, 1
+POW2_NONE, POW2_NEAREST, POW2_NEXT, POW2_PREVIOUS = 0, 1, 2, 3
 
 
 class MipChainLayout(C.Structure):
@@ -134,6 +136,11 @@ class MipFilter(C.Structure):
 class MipWeighting(C.Structure):
     """struct astcenc_amd_mip_weighting (include/astcenc_amd.h): weight = MIP_WEIGHT_*."""
     _fields_ = [("weight", C.c_int)]
+
+
+class Resize(C.Structure):
+    """struct astcenc_amd_resize (include/astcenc_amd.h): the destination size, the filter and the weighting."""
+    _fields_ = [("dim_x", C.c_uint), ("dim_y", C.c_uint), ("dim_z", C.c_uint), ("filter", MipFilter), ("weighting", MipWeighting)]
 
 
 class ImageSetEntry(C.Structure):
@@ -307,6 +314,12 @@ class Library:
                                                                          C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                                                          C.POINTER(C.c_float)]
             L.astcenc_amd_compress_mip_chain_weighted_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_resize_image_device"):
+            L.astcenc_amd_resize_image_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int,
+                                                          C.POINTER(Resize), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
+            L.astcenc_amd_resize_image_device.restype = C.c_int
+            L.astcenc_amd_resize_dims.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+            L.astcenc_amd_resize_dims.restype = C.c_int
 
     # -- thin wrappers returning error codes, as the C API does --
     def config_init(self, profile, bx, by, bz, quality, flags):
@@ -606,6 +619,33 @@ class Library:
         n = layout.level_count
         ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
         return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+
+    def resize_dims(self, w, h, max_dim=0, pow2=POW2_NONE):
+        """astcenc_amd_resize_dims: returns (error, (out_w, out_h))."""
+        x, y = C.c_uint(0), C.c_uint(0)
+        err = self.lib.astcenc_amd_resize_dims(w, h, max_dim, pow2, C.byref(x), C.byref(y))
+        return err, (x.value, y.value)
+
+    def resize_image_device(self, ctx, image, size, kind=MIP_VOLUME, mip_filter=(MIP_FILTER_LANCZOS3, MIP_EDGE_CLAMP),
+                            weighting=MIP_WEIGHT_NONE, stream=None):
+        """astcenc_amd_resize_image_device: the [Z, H, W, 4] device tensor `image` resized to size = (w, h) (the depth or the
+        layers kept) or (w, h, d); returns a new [d, h, w, 4] tensor, the kernel time in self.last_kernel_ms."""
+        import torch
+        types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
+        assert image.is_contiguous() and image.dim() == 4 and image.shape[-1] == 4, "a contiguous [Z, H, W, 4] device tensor"
+        d, h, w = image.shape[0], image.shape[1], image.shape[2]
+        ow, oh, od = (tuple(size) + (d,))[:3]
+        flt = mip_filter if isinstance(mip_filter, MipFilter) else MipFilter(*mip_filter)
+        wt = weighting if isinstance(weighting, MipWeighting) else MipWeighting(weighting)
+        out = torch.empty((od, oh, ow, 4), dtype=image.dtype, device=image.device)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_resize_image_device(ctx, image.data_ptr(), w, h, d, kind, types[image.dtype],
+                                                       C.byref(Resize(ow, oh, od, flt, wt)), out.data_ptr(),
+                                                       out.numel() * out.element_size(), torch_stream(stream), C.byref(ms))
+        self.last_kernel_ms = ms.value
+        if err:
+            raise AstcError(err, "astcenc_amd_resize_image_device")
+        return out
 
     def decompress(self, data, width, height, block=(6, 6), profile=PRF_LDR, out_type=np.uint8, depth=None):
         """Decode blocks back to [H, W, 4] ([D, H, W, 4] when depth is given) through

@@ -522,6 +522,87 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_mip_chain_weighted_device
 	void* hip_stream,
 	float* kernel_ms);
 
+/* Resizing a device image to any size with the mip filters.
+ *
+ * The chain calls above make exactly max(1, s >> 1) texels from s.  astcenc_amd_resize_image_device makes any number, with the
+ * same filters (BOX included), edges (CLAMP and WRAP), weighting and arithmetic, so that an image whose level 0 has the wrong
+ * size -- source art above a platform's cap, a scan that is no power of two, an atlas rescaled by an odd factor -- reaches the
+ * size it ships at on the device and with bits that are specified.  Its output is an ordinary device image: pass it as
+ * level 0 to any chain call.
+ *
+ * device_image is dim_x x dim_y x dim_z texels and device_out resize->dim_x x dim_y x dim_z, both tightly packed RGBA slices
+ * back to back, the layout of every other device entry point.  kind ASTCENC_AMD_MIP_ARRAY: dim_z independent layers, every
+ * one resized in x and y; resize->dim_z must equal dim_z (a 2D image is one layer).  ASTCENC_AMD_MIP_VOLUME: all three axes
+ * are resized.  U8 data in an ASTCENC_PRF_LDR_SRGB context is filtered in linear light through the chain's EOTF and threshold
+ * tables (channels 0-2).  The call needs no caller scratch; the taps are built on the host once per call and kept in the
+ * context's own scratch.
+ *
+ * Checks, error codes, logging, stream rules and kernel_ms follow the _filtered_ calls: everything is checked before anything
+ * is launched and an error writes nothing; the log names the argument (the new ones "resize"); the work is queued on
+ * hip_stream (null: the context's own) and is complete on return; kernel_ms (may be null) receives the kernel's time.
+ * ASTCENC_ERR_BAD_PARAM: a null context or `resize`, a zero source or destination dimension, an unknown kind, data type, filter
+ * kind, edge or weight, ASTCENC_AMD_MIP_EDGE_CUBE (not done for resizing), an ARRAY whose layer count changes, texel bytes
+ * beyond size_t, an integer box (U8 data, BOX) whose weight x value sums could leave 64 bits (den_x den_y den_z 65025 >= 2^63,
+ * den below), a buffer or stream of another device.  ASTCENC_ERR_BAD_CONTEXT: a null buffer.  ASTCENC_ERR_OUT_OF_MEM: out_len
+ * is too short, or the taps do not fit the library's 64 MiB scratch bound (a row of taps per destination texel of an axis, a
+ * weight per tap; periodic ratios need one period).  There is no other cap on the ratio.
+ *
+ * The arithmetic, exactly (a numpy model reproduces it bit for bit).  Per axis a source of s texels makes d:
+ *   - pass-through, s == 1 or d == s: destination j has one tap of weight 1.0, on texel 0 or on texel j.  An untouched axis is
+ *     copied exactly and a resize to the same size returns the input's bytes;
+ *   - windowed kinds otherwise: r = (double)s / (double)d; scale = r if d < s, else 1.0 (no widening when enlarging);
+ *     c = (double)((2j + 1) s) / (double)(2d), the product in 64-bit integers; the taps are every integer i with |t| < S,
+ *     t = (((double)i + 0.5) - c) / scale.  The function f, the normalisation by the running sum in increasing i and the CLAMP
+ *     or WRAP mapping of i to a source texel are those of the chain's windowed filters above.  At d = max(1, s >> 1) these are
+ *     the chain's taps, every float equal;
+ *   - BOX otherwise: with g = gcd(s, d), s' = s / g and d' = d / g, destination j covers [j s', (j + 1) s') and source i
+ *     covers [i d', (i + 1) d'); the taps are the sources with a non-empty overlap in increasing i, the weight is the integer
+ *     overlap length and den = s'.  There are no edges.  At d = max(1, s >> 1) these are the chain's box weights.
+ * Sums and results are the chain's, word for word.  Windowed: float64 row (x), acc (y) and vol (z) sums in increasing tap
+ * order, each sum starting at its first product and each operation rounded on its own, then the stored results of the windowed
+ * filters.  Box: the same sums with (double)w, then a division by ((den_x den_y) den_z) in float64; for linear U8 (and the
+ * alpha channel of sRGB data) the exact rational mean rounded to nearest, ties up, in 64-bit integers.
+ * ASTCENC_AMD_MIP_WEIGHT_ALPHA: the definitions of the weighting above with these taps, including the fallback to the plain
+ * colour; channel 3 is byte for byte the plain resize's.  An ARRAY's z axis is the one tap of weight 1.0.
+ *
+ * Not done here: cube edges; the NORMALIZE and ALPHA_COVERAGE post-passes (a caller renormalises through a chain call, whose
+ * options apply to the levels it makes); host-pointer input; per-layer sizes. */
+struct astcenc_amd_resize {
+	unsigned int dim_x, dim_y, dim_z;             /* destination size */
+	struct astcenc_amd_mip_filter filter;         /* kind + edge; BOX allowed, EDGE_CUBE not */
+	struct astcenc_amd_mip_weighting weighting;   /* NONE or ALPHA */
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_resize_image_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_amd_mip_kind kind,
+	enum astcenc_type data_type,
+	const struct astcenc_amd_resize* resize,
+	void* device_out, size_t out_len,
+	void* hip_stream,
+	float* kernel_ms);
+
+/* The destination size of a capped and / or power-of-two texture: integer arithmetic only, no device.  In this order:
+ *   1. cap: if max_dim != 0 and L = max(dim_x, dim_y) > max_dim, the larger axis becomes max_dim and the other
+ *      max(1, (v max_dim + L / 2) / L) (the aspect kept, rounded to nearest);
+ *   2. power of two, per axis: NEXT the smallest power of two >= v; PREVIOUS the largest <= v; NEAREST is PREVIOUS when
+ *      v - prev < 2 prev - v, else 2 prev (ties go up).  If the cap was given and the rounded value exceeds it: PREVIOUS.
+ * ASTCENC_ERR_BAD_PARAM: a zero dimension, a null output, an unknown mode or a result above 2^31 (nothing is written). */
+enum astcenc_amd_resize_pow2 {
+	ASTCENC_AMD_POW2_NONE     = 0,
+	ASTCENC_AMD_POW2_NEAREST  = 1,
+	ASTCENC_AMD_POW2_NEXT     = 2,
+	ASTCENC_AMD_POW2_PREVIOUS = 3
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_resize_dims(
+	unsigned int dim_x, unsigned int dim_y,
+	unsigned int max_dim,
+	enum astcenc_amd_resize_pow2 pow2,
+	unsigned int* out_x, unsigned int* out_y);
+
 /* Error sums of two device-resident images of the same size, the quantities the reference CLI's quality
  * report is made of (ref: compute_error_metrics, Source/astcenccli_error_metrics.cpp:110-300):
  *   PSNR (LDR-RGBA)     = 10 log10(4 texels / (squared_error[0] + .. + [3]))
