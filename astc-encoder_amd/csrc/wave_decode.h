@@ -648,7 +648,10 @@ WV_FN void swizzle_sources(float r, float g, float b, float a, float src[7])
 	float yn = (a * 2.0f) - 1.0f;
 	float zn = 1.0f - xn * xn - yn * yn;
 	if (zn < 0.0f) zn = 0.0f;
-	src[6] = (f_sqrt(zn) * 0.5f) + 0.5f;
+	const float z = (f_sqrt(zn) * 0.5f) + 0.5f;
+	// An error texel's NaN goes through the reference's scalar arithmetic with its sign and payload as they are (every
+	// operation there returns its NaN operand); the device's negated operands need not keep the sign, so it is handed on here.
+	src[6] = r != r ? r : a != a ? a : z;
 }
 
 /* One decoded texel (floats) as an RGBA8 pixel through the swizzle; an error texel (NaN) is opaque magenta. */

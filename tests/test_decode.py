@@ -120,6 +120,12 @@ def test_decode_random_bit_patterns(lib, ref, A, block, profile_name):
             bi = (y // block[1]) * nbx + x // block[0]
             raise AssertionError("%s: first differing texel (y=%d, x=%d) block %s: want %s got %s" %
                                  (out_type.__name__, y, x, blocks[bi].tobytes().hex(), want[y, x], got[y, x]))
+    # an error block's texels are NaN: the normal-map swizzle (z computed from r and a) hands the reference's NaN on bit for bit
+    swz = (A.SWZ_R, A.SWZ_A, A.SWZ_Z, A.SWZ_1)
+    for out_type in (np.float16, np.float32):
+        want = decode(ref, A, data, w, h, block, profile, out_type, swz)
+        assert np.isnan(want).any()
+        assert same(want, decode(lib, A, data, w, h, block, profile, out_type, swz)), ("SWZ_Z", out_type.__name__)
 
 
 def test_decode_matches_independent_oracle_decoder(lib, ref, A):
