@@ -162,6 +162,22 @@ struct CompareJob {
 };
 constexpr int METRIC_SUMS_HOST = 18;
 
+/* Error sums of compressed blocks against their source images (wave_quality.h): an image set whose entries are compared
+ * without a decoded image in memory.  Per entry a DecompressDeviceJob whose device_image is unused and whose data_type is the
+ * type the blocks are decoded to, the original and the optional per-block output. */
+struct QualityEntryJob {
+	DecompressDeviceJob decode;
+	const void* device_original; uint32_t original_type;
+	double* device_block_errors;   // null, or four doubles per block of the entry (squared error r, g, b, a)
+};
+struct QualitySetJob {
+	const QualityEntryJob* entries;
+	uint32_t count;
+	void* stream;
+	double* sums;              // METRIC_SUMS_HOST doubles per entry, laid out as CompareJob::sums
+	int hdr, fstop_lo, fstop_hi;
+};
+
 /* status / return codes: 0 ok, 1 out of memory, 2 no usable device / launch failure, 3 bad argument
  * (a stream of another device than the buffers).
  * backend_create builds one device slot per GPU the context may use: every visible device by default, or the
@@ -179,6 +195,7 @@ int backend_compare(Backend* b, const CompareJob& job);
  * entry points live in astcenc_set.cpp, which the sequential build of oracle/emu does not link.) */
 int backend_compress_set(Backend* b, const CompressSetJob& job);
 int backend_decompress_set(Backend* b, const DecompressSetJob& job);
+int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 int backend_generate_mips(Backend* b, const MipChainJob& job);
 int backend_resize(Backend* b, const ResizeJob& job);
 /* A line for the diagnostics callback (astcenc_amd_set_log_callback), printf-style. */
@@ -267,6 +284,20 @@ int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream);
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();
 void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uint32_t block_z);
+
+/* Block quality launch (kernel_quality.hip): an image set's table as for the decoder (astc_quality_set_bytes(count) bytes),
+ * one QualityLaunch per entry (decode.d_image and decode.stream unused).  astc_quality_set_launch queues the kernels from the
+ * table's host and device copies (d_table: null for a set of one entry, whose record travels with the launch): d_partials = astc_quality_scratch_doubles() doubles, d_sums = METRIC_SUMS_HOST doubles per
+ * entry, which receive the totals. */
+struct QualityLaunch {
+	DecodeLaunch decode;
+	const void* d_original; uint32_t original_type;
+	double* d_block_errors;
+};
+size_t astc_quality_set_bytes(uint32_t count);
+size_t astc_quality_scratch_doubles();
+uint32_t astc_quality_set_build(void* out, const QualityLaunch* entries, uint32_t count);
+int astc_quality_set_launch(const void* h_table, const void* d_table, double* d_partials, double* d_sums, int hdr, int fstop_lo, int fstop_hi, void* stream);
 
 /* Mip chain generation (kernel_mips.hip): queues the launches of `job` on `stream` (job.stream unused), level i made from level
  * i - 1.  d_srgb: the tables of astc_mip_srgb_tables_build in device memory (astc_mip_srgb_table_bytes()), used for RGBA8 when

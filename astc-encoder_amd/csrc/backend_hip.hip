@@ -71,6 +71,8 @@ struct DeviceSlot {
 	unsigned long long* d_prof = nullptr;   // stage timers (ASTC_PROFILE builds) / search trace (ASTC_TRACE builds)
 	size_t trace_cap = 0;         // bytes at d_prof in ASTC_TRACE builds
 	double* d_sums = nullptr;     // totals of the image comparison kernel
+	double* d_quality = nullptr; size_t quality_cap = 0;   // partial sums of the block quality kernel (kernel_quality.hip), a fixed size
+	double* d_quality_sums = nullptr; size_t quality_sums_cap = 0;   // ... and its totals, per entry of the set
 	std::mutex busy;              // one call at a time per slot: the staging buffers and events are shared state
 	std::vector<int> local_cpus;  // host CPUs on the device's NUMA node (Linux sysfs); empty: unknown, no binding
 	SlotWorker* worker = nullptr; // the slot's parked host thread (slots 1.. of a multi-device context), or null
@@ -363,6 +365,8 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_mip_filter) (void)hipFree(s->d_mip_filter);
 	if (s->d_set) (void)hipFree(s->d_set);
 	if (s->d_sums) (void)hipFree(s->d_sums);
+	if (s->d_quality) (void)hipFree(s->d_quality);
+	if (s->d_quality_sums) (void)hipFree(s->d_quality_sums);
 	if (s->d_prof) (void)hipFree(s->d_prof);
 	for (int i = 0; i < 2; i++) { if (s->h_in[i]) (void)hipHostFree(s->h_in[i]); if (s->h_out[i]) (void)hipHostFree(s->h_out[i]); }
 	for (hipEvent_t e : { s->ev_copy[0], s->ev_copy[1], s->ev_band, s->ev_done[0], s->ev_done[1], s->ev_done[2], s->ev_out[0], s->ev_out[1], s->ev0, s->ev1, s->ev_gen })
@@ -1470,6 +1474,49 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 		int lrc = astc_decode_set_launch(s->d_set, runs, stream);
 		if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
 		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		return 0;
+	});
+}
+
+/* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial
+ * sums has a fixed size (rc 1 when it cannot be had, nothing launched), the totals come back once the stream has run. */
+int backend_compare_blocks_set(Backend* b, const QualitySetJob& job)
+{
+	std::vector<const void*> ptrs;
+	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_original); ptrs.push_back(job.entries[e].decode.device_blocks); }
+	return run_on_owner(b, job.entries[0].device_original, ptrs.data(), ptrs.size(), job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		std::vector<QualityLaunch> q(job.count);
+		for (uint32_t e = 0; e < job.count; e++)
+		{
+			const QualityEntryJob& en = job.entries[e];
+			hipPointerAttribute_t attr;
+			memset(&attr, 0, sizeof(attr));
+			if (en.device_block_errors && hipPointerGetAttributes(&attr, en.device_block_errors) == hipSuccess && attr.device != s->device)
+			{
+				log_msg("image set entry %u: the block error buffer is on device %d, entry 0's image on device %d", e, attr.device, s->device);
+				return 3;
+			}
+			(void)hipGetLastError();
+			q[e].decode = decode_launch(b, s, en.decode, en.decode.device_blocks, nullptr, nullptr);
+			q[e].d_original = en.device_original; q[e].original_type = en.original_type;
+			q[e].d_block_errors = en.device_block_errors;
+		}
+		const size_t sums_bytes = (size_t)job.count * METRIC_SUMS_HOST * sizeof(double);
+		if (grow(s->d_quality, s->quality_cap, astc_quality_scratch_doubles() * sizeof(double)) != 0 ||
+		    grow(s->d_quality_sums, s->quality_sums_cap, sums_bytes) != 0) return 1;
+		const size_t bytes = astc_quality_set_bytes(job.count);
+		s->h_set.assign(bytes, 0);
+		astc_quality_set_build(s->h_set.data(), q.data(), job.count);
+		// (a set of one entry -- the single-image calls -- needs no table on the device)
+		const int urc = job.count > 1 ? set_table_upload(s, stream, bytes) : 0;
+		if (urc != 0) return urc;
+		int lrc = astc_quality_set_launch(s->h_set.data(), job.count > 1 ? s->d_set : nullptr, s->d_quality, s->d_quality_sums, job.hdr, job.fstop_lo, job.fstop_hi, stream);
+		if (lrc != 0) { log_msg("block quality kernel launch failed (hip error %d)", lrc); return 2; }
+		std::vector<double> raw((size_t)job.count * METRIC_SUMS_HOST);
+		HIP_TRY(hipMemcpyAsync(raw.data(), s->d_quality_sums, sums_bytes, hipMemcpyDeviceToHost, stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		memcpy(job.sums, raw.data(), sums_bytes);
 		return 0;
 	});
 }

@@ -709,6 +709,17 @@ WV_FN void store_texel(const DecodeImage& img, uint32_t x, uint32_t y, uint32_t 
 	store_texel_at(img, (((size_t)z * img.dim_y + y) * img.dim_x + x) * 4, r, g, b, a);
 }
 
+/* Where the texel phases of decode_row_batch put a decoded texel: the three forms in which one leaves them, each with the
+ * lane it is on and `at`, the index of its first component in the image.  The decoder's own sink stores them; the one of
+ * wave_quality.h compares them with the original image's texel at the same place instead.  trip_end: all 64 lanes have done
+ * their texels of elements [base, base + 64) of the run, `unit` elements to a block (2D: columns, 3D: texels). */
+struct DecodeStore {
+	WV_FN void pixel(const DecodeImage& img, int, size_t at, uint32_t px) { __builtin_memcpy(static_cast<uint8_t*>(img.data) + at, &px, 4); }
+	WV_FN void halves(const DecodeImage& img, int, size_t at, uint64_t px) { __builtin_memcpy(static_cast<uint8_t*>(img.data) + at * 2, &px, 8); }
+	WV_FN void texel(const DecodeImage& img, int, size_t at, float r, float g, float b, float a) { store_texel_at(img, at, r, g, b, a); }
+	WV_FN void trip_end(int, int, int) {}
+};
+
 /* Everything the header of a block says (ref: physical_to_symbolic :291-556 up to the ISE decode). */
 struct BlockHeader {
 	bool error, constant, constant_f16;
@@ -1076,7 +1087,8 @@ WV_FN void group_symbols_split(const GroupLayout& L, uint32_t a, uint32_t b, uin
 /* A texel that does not leave as an RGBA8 pixel built from integers: error and constant-colour blocks, LNS endpoints,
  * FP16 / FP32 output, the Z swizzle.  cv = the four interpolated 16-bit values (blocks with a payload).
  * `at` = index of the texel's first component.  (ref: decode_texel :66, store_image_block :345) */
-WV_FN void store_texel_general(const DecodeImage& img, const DecodeBatch& s, int k, uint32_t flags, int p, const int cv[4], size_t at)
+template <class Sink>
+WV_FN void store_texel_general(const DecodeImage& img, const DecodeBatch& s, int k, uint32_t flags, int p, const int cv[4], size_t at, Sink& sink, int lane)
 {
 	const int profile = (int)img.profile;
 	const bool u8_out = img.data_type == 0 || profile == 0;        // (ref: get_u8_component_mask)
@@ -1107,12 +1119,12 @@ WV_FN void store_texel_general(const DecodeImage& img, const DecodeBatch& s, int
 		{
 			const uint32_t lo = (uint32_t)(hf[0] & 0xFFFF) | ((uint32_t)hf[1] << 16), hi = (uint32_t)(hf[2] & 0xFFFF) | ((uint32_t)hf[3] << 16);
 			const uint64_t px = ((uint64_t)hi << 32) | lo;
-			__builtin_memcpy(static_cast<uint8_t*>(img.data) + at * 2, &px, 8);
+			sink.halves(img, lane, at, px);
 			return;
 		}
 		r = half_to_float((uint16_t)hf[0]); g = half_to_float((uint16_t)hf[1]); bl = half_to_float((uint16_t)hf[2]); a = half_to_float((uint16_t)hf[3]);
 	}
-	store_texel_at(img, at, r, g, bl, a);
+	sink.texel(img, lane, at, r, g, bl, a);
 }
 
 /* The RGBA8 pixel of four interpolation results x[q] = lerp_terms(endpoint word q, weight pair) (byte 2 = the value's top
@@ -1132,8 +1144,8 @@ WV_FN uint32_t pixel_from_lerps(uint32_t sel, const uint32_t x[4])
  * has blocks with more than one partition (1: with two at most, 2: with three or four) / with two weight planes
  * (wave-uniform; a run without them skips the partition hash and reads its endpoints once per column / reads one plane).  kGeneral: some texel of the run does not leave as an
  * integer-built RGBA8 pixel (store_texel_general); the builds without it are the RGBA8 decoder's inner loops. */
-template <int kMulti, bool kDual, bool kGeneral>
-WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s)
+template <int kMulti, bool kDual, bool kGeneral, class Sink>
+WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink)
 {
 	const int block_x = (int)img.block_x, block_y = (int)img.block_y;
 	const bool small_block = block_x * block_y < 31;
@@ -1233,17 +1245,19 @@ WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, 
 					if (fast) px = pixel_from_lerps(swz_sel, x);
 					else for (int q = 0; q < 4; q++) cv[q] = (int)(x[q] >> 8);
 				}
-				if (fast) __builtin_memcpy(static_cast<uint8_t*>(img.data) + at, &px, 4);
-				else store_texel_general(img, s, k, ra, p, cv, at);
+				if (fast) sink.pixel(img, l, at, px);
+				else store_texel_general(img, s, k, ra, p, cv, at, sink, l);
 			}
 		}
+		sink.trip_end(c0, block_x, count);
 	}
 }
 
 /* Decode blocks bx0 .. bx0 + count - 1 (count <= DECODE_BATCH) of block row `by`, layer `bz` of the stream into the image.
  * All 64 lanes call this.  The arithmetic, block by block, is that of the single-block routines above (parse_block_header,
  * unpack_block_payload, infill_texel_weights: what astcenc_get_block_info runs on the host). */
-WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s)
+template <class Sink>
+WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink)
 {
 	const int block_x = (int)img.block_x, block_y = (int)img.block_y, block_z = (int)img.block_z;
 	const int T = block_x * block_y * block_z;
@@ -1470,21 +1484,21 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 	// ---- texels ----
 	if (block_z == 1)
 	{
-		if (any_general) decode_row_texels<2, true, true>(img, bx0, by, bz, count, s);
+		if (any_general) decode_row_texels<2, true, true, Sink>(img, bx0, by, bz, count, s, sink);
 		else if (any_many)
 		{
-			if (any_dual) decode_row_texels<2, true, false>(img, bx0, by, bz, count, s);
-			else decode_row_texels<2, false, false>(img, bx0, by, bz, count, s);
+			if (any_dual) decode_row_texels<2, true, false, Sink>(img, bx0, by, bz, count, s, sink);
+			else decode_row_texels<2, false, false, Sink>(img, bx0, by, bz, count, s, sink);
 		}
 		else if (any_multi)
 		{
-			if (any_dual) decode_row_texels<1, true, false>(img, bx0, by, bz, count, s);
-			else decode_row_texels<1, false, false>(img, bx0, by, bz, count, s);
+			if (any_dual) decode_row_texels<1, true, false, Sink>(img, bx0, by, bz, count, s, sink);
+			else decode_row_texels<1, false, false, Sink>(img, bx0, by, bz, count, s, sink);
 		}
 		else
 		{
-			if (any_dual) decode_row_texels<0, true, false>(img, bx0, by, bz, count, s);
-			else decode_row_texels<0, false, false>(img, bx0, by, bz, count, s);
+			if (any_dual) decode_row_texels<0, true, false, Sink>(img, bx0, by, bz, count, s, sink);
+			else decode_row_texels<0, false, false, Sink>(img, bx0, by, bz, count, s, sink);
 		}
 	}
 	else
@@ -1492,48 +1506,61 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 		// 3D blocks: one lane per (block, texel)
 		const bool small_block = T < 31;
 		const uint32_t swz_sel = swizzle_selector(img.swz);
-		WV_FOR(j, count * T)
+		const int n = count * T;
+		for (int j0 = 0; j0 < n; j0 += 64)
 		{
-			const int k = (int)(((uint32_t)j * img.t_inv24) >> 24);
-			const int t = j - k * T;
-			const int tz = (int)(((uint32_t)t * img.bxy_inv16) >> 16);
-			const int trem = t - tz * (block_x * block_y);
-			const int ty = (int)(((uint32_t)trem * img.bx_inv16) >> 16);
-			const int tx = trem - ty * block_x;
-			const uint32_t xi = (bx0 + (uint32_t)k) * (uint32_t)block_x + (uint32_t)tx;
-			const uint32_t yi = by * (uint32_t)block_y + (uint32_t)ty;
-			const uint32_t zi = bz * (uint32_t)block_z + (uint32_t)tz;
-			if (xi >= img.dim_x || yi >= img.dim_y || zi >= img.dim_z) continue;
-			const size_t at = (((size_t)zi * img.dim_y + yi) * img.dim_x + xi) * 4;
-			const uint32_t ra = s.rec[k][0], rc = s.rec[k][2];
-			const bool fast = img.data_type == 0 && (ra & 8u) != 0u;
-			uint32_t px = s.rec[k][3];
-			int cv[4] = { 0, 0, 0, 0 };
-			int p = 0;
-			if (!(ra & 1u))
+			WV_FOR64(l, i_min(64, n - j0))
 			{
-				const bool dual = (rc & 0x1000u) != 0u;
-				const int parts = (int)((rc >> 13) & 7u);
-				const int plane2 = dual ? (int)((rc >> 16) & 3u) : -1;
-				int wp[2];
-				infill_texel_weights((int)(rc & 15u), (int)((rc >> 4) & 15u), (int)((rc >> 8) & 15u), dual, s.weights[k], s.weights[k] + (dual ? 1 : 0), dual ? 2 : 1,
-				                     (int)img.ds, (int)img.dt, (int)img.dr, block_z, tx, ty, tz, wp);
-				if (parts > 1)
+				const int j = j0 + l;
+				const int k = (int)(((uint32_t)j * img.t_inv24) >> 24);
+				const int t = j - k * T;
+				const int tz = (int)(((uint32_t)t * img.bxy_inv16) >> 16);
+				const int trem = t - tz * (block_x * block_y);
+				const int ty = (int)(((uint32_t)trem * img.bx_inv16) >> 16);
+				const int tx = trem - ty * block_x;
+				const uint32_t xi = (bx0 + (uint32_t)k) * (uint32_t)block_x + (uint32_t)tx;
+				const uint32_t yi = by * (uint32_t)block_y + (uint32_t)ty;
+				const uint32_t zi = bz * (uint32_t)block_z + (uint32_t)tz;
+				if (xi >= img.dim_x || yi >= img.dim_y || zi >= img.dim_z) continue;
+				const size_t at = (((size_t)zi * img.dim_y + yi) * img.dim_x + xi) * 4;
+				const uint32_t ra = s.rec[k][0], rc = s.rec[k][2];
+				const bool fast = img.data_type == 0 && (ra & 8u) != 0u;
+				uint32_t px = s.rec[k][3];
+				int cv[4] = { 0, 0, 0, 0 };
+				int p = 0;
+				if (!(ra & 1u))
 				{
-					PartitionHash ph;
-					for (int q = 0; q < 4; q++) ph.term[q] = s.hash[k][q];
-					p = partition_from_hash(ph, tx, ty, tz, small_block);
+					const bool dual = (rc & 0x1000u) != 0u;
+					const int parts = (int)((rc >> 13) & 7u);
+					const int plane2 = dual ? (int)((rc >> 16) & 3u) : -1;
+					int wp[2];
+					infill_texel_weights((int)(rc & 15u), (int)((rc >> 4) & 15u), (int)((rc >> 8) & 15u), dual, s.weights[k], s.weights[k] + (dual ? 1 : 0), dual ? 2 : 1,
+					                     (int)img.ds, (int)img.dt, (int)img.dr, block_z, tx, ty, tz, wp);
+					if (parts > 1)
+					{
+						PartitionHash ph;
+						for (int q = 0; q < 4; q++) ph.term[q] = s.hash[k][q];
+						p = partition_from_hash(ph, tx, ty, tz, small_block);
+					}
+					uint32_t x[4];
+					for (int q = 0; q < 4; q++) x[q] = lerp_terms(s.ep[k][p * 4 + q], lerp_weight_pair(q == plane2 ? wp[1] : wp[0]));
+					if (fast) px = pixel_from_lerps(swz_sel, x);
+					else for (int q = 0; q < 4; q++) cv[q] = (int)(x[q] >> 8);
 				}
-				uint32_t x[4];
-				for (int q = 0; q < 4; q++) x[q] = lerp_terms(s.ep[k][p * 4 + q], lerp_weight_pair(q == plane2 ? wp[1] : wp[0]));
-				if (fast) px = pixel_from_lerps(swz_sel, x);
-				else for (int q = 0; q < 4; q++) cv[q] = (int)(x[q] >> 8);
+				if (fast) sink.pixel(img, l, at, px);
+				else store_texel_general(img, s, k, ra, p, cv, at, sink, l);
 			}
-			if (fast) __builtin_memcpy(static_cast<uint8_t*>(img.data) + at, &px, 4);
-			else store_texel_general(img, s, k, ra, p, cv, at);
+			sink.trip_end(j0, T, count);
 		}
 	}
 	WV_SYNC();          // the batch scratch is reused by the next call
+}
+
+/* ... into the image: the decoder. */
+WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s)
+{
+	DecodeStore store;
+	decode_row_batch(img, blocks, bx0, by, bz, count, s, store);
 }
 
 #endif // !ASTC_DECODE_NO_LUTS

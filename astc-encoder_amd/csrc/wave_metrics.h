@@ -16,6 +16,13 @@ constexpr int METRIC_HDR_FIRST = 10;   // HDR comparisons add [10..13] squared l
 constexpr int METRIC_SUMS_HDR = 18;
 constexpr int METRIC_STRIDE = 32;      // doubles per workgroup slot in the partials array
 
+/* A half / float component as the comparison takes it: clamp(0, 65504, v), NaN -> 0 as the reference's max/min pair. */
+WV_FN float metric_clamp_operand(float v)
+{
+	v = v > 0.0f ? v : 0.0f;
+	return v < 65504.0f ? v : 65504.0f;
+}
+
 /* `unorm8` is an optional table of (float)i / 255.0f, i = 0..255 (the same correctly rounded quotients,
  * computed once per workgroup instead of eight times per texel). */
 WV_FN void metric_load_texel(const void* img, size_t texel, uint32_t data_type, const float* unorm8, float c[4])
@@ -38,10 +45,7 @@ WV_FN void metric_load_texel(const void* img, size_t texel, uint32_t data_type, 
 		else __builtin_memcpy(f4, static_cast<const float*>(img) + texel * 4, 16);
 		for (int k = 0; k < 4; k++)
 		{
-			float v = data_type == 1 ? half_to_float(h4[k]) : f4[k];
-			v = v > 0.0f ? v : 0.0f;               // clamp(0, 65504, v), NaN -> 0 as the reference's max/min pair
-			v = v < 65504.0f ? v : 65504.0f;
-			c[k] = v;
+			c[k] = metric_clamp_operand(data_type == 1 ? half_to_float(h4[k]) : f4[k]);
 		}
 	}
 }

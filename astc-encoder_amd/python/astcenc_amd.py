@@ -98,7 +98,8 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_generate_mip_chain_ex_device", "astcenc_amd_compress_mip_chain_ex_device",
                "astcenc_amd_generate_mip_chain_filtered_device", "astcenc_amd_compress_mip_chain_filtered_device",
                "astcenc_amd_generate_mip_chain_weighted_device", "astcenc_amd_compress_mip_chain_weighted_device",
-               "astcenc_amd_resize_image_device", "astcenc_amd_resize_dims"]
+               "astcenc_amd_resize_image_device", "astcenc_amd_resize_dims", "astcenc_amd_compare_blocks_device",
+               "astcenc_amd_compare_blocks_hdr_device", "astcenc_amd_compare_image_set_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
@@ -189,6 +190,11 @@ class HdrErrorSums(C.Structure):
         return float(np.sqrt(sum(self.log2_squared_error[k] for k in range(3)) / texels))
 
 
+class BlockError(C.Structure):
+    """struct astcenc_amd_block_error (include/astcenc_amd.h): 32 bytes per block, raster block order."""
+    _fields_ = [("squared_error", C.c_double * 4)]
+
+
 class AstcError(RuntimeError):
     def __init__(self, code, where):
         super().__init__("%s failed with astcenc_error %d" % (where, code))
@@ -264,6 +270,16 @@ class Library:
             L.astcenc_amd_compress_images_device.restype = C.c_int
             L.astcenc_amd_decompress_images_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p]
             L.astcenc_amd_decompress_images_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_compare_blocks_device"):
+            blocks_args = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(Swizzle),
+                           C.c_void_p, C.c_size_t]
+            L.astcenc_amd_compare_blocks_device.argtypes = blocks_args + [C.c_void_p, C.POINTER(ErrorSums)]
+            L.astcenc_amd_compare_blocks_device.restype = C.c_int
+            L.astcenc_amd_compare_blocks_hdr_device.argtypes = blocks_args + [C.c_int, C.c_int, C.c_void_p, C.POINTER(ErrorSums), C.POINTER(HdrErrorSums)]
+            L.astcenc_amd_compare_blocks_hdr_device.restype = C.c_int
+            L.astcenc_amd_compare_image_set_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                               C.POINTER(ErrorSums)]
+            L.astcenc_amd_compare_image_set_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_mip_chain_layout"):
             L.astcenc_amd_mip_chain_layout.argtypes = [C.POINTER(Config), C.c_uint, C.c_uint, C.c_int, C.c_uint, C.POINTER(MipChainLayout)]
             L.astcenc_amd_mip_chain_layout.restype = C.c_int
@@ -417,6 +433,51 @@ class Library:
         """astcenc_amd_decompress_images_device over `entries` (see _set_args): every entry's blocks into its image."""
         arr, n, s = self._set_args(entries, stream)
         return self.lib.astcenc_amd_decompress_images_device(ctx, arr, n, s)
+
+    @staticmethod
+    def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):
+        """The arguments astcenc_amd_compare_blocks_device and its _hdr_ form share, from device tensors: `blocks` uint8, `image`
+        [H, W, 4] or [D, H, W, 4] (the original), `block_errors` None or a float64 tensor of four values per block."""
+        import torch
+        types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
+        assert image.is_contiguous() and blocks.is_contiguous() and image.dim() in (3, 4) and image.shape[-1] == 4
+        assert block_errors is None or (block_errors.is_contiguous() and block_errors.dtype == torch.float64)
+        d = image.shape[0] if image.dim() == 4 else 1
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        image_type = types[image.dtype]
+        return [blocks.data_ptr(), blocks.numel(), image.data_ptr(), image.shape[-2], image.shape[-3], d, image_type,
+                image_type if decode_type is None else decode_type, C.byref(Swizzle(*swizzle)),
+                None if block_errors is None else block_errors.data_ptr(), 0 if block_errors is None else block_errors.numel() * 8], \
+            getattr(stream, "cuda_stream", stream)
+
+    def compare_blocks_device(self, ctx, blocks, image, decode_type=None, swizzle=SWZ_RGBA, block_errors=None, stream=None):
+        """astcenc_amd_compare_blocks_device: the blocks decoded to decode_type (default: the image's type) through `swizzle` against
+        the original `image`, no decoded image in memory.  Returns (error, ErrorSums); block_errors (optional, float64 [blocks, 4])
+        receives the per-block squared errors."""
+        args, s = self._blocks_args(blocks, image, decode_type, swizzle, block_errors, stream)
+        sums = ErrorSums()
+        err = self.lib.astcenc_amd_compare_blocks_device(ctx, *args, s, C.byref(sums))
+        return err, sums
+
+    def compare_blocks_hdr_device(self, ctx, blocks, image, fstop_lo=-10, fstop_hi=10, decode_type=None, swizzle=SWZ_RGBA, block_errors=None,
+                                  stream=None):
+        """astcenc_amd_compare_blocks_hdr_device: as compare_blocks_device, with the HDR sums over the f-stops.  Returns
+        (error, ErrorSums, HdrErrorSums)."""
+        args, s = self._blocks_args(blocks, image, decode_type, swizzle, block_errors, stream)
+        sums, hdr = ErrorSums(), HdrErrorSums()
+        err = self.lib.astcenc_amd_compare_blocks_hdr_device(ctx, *args, fstop_lo, fstop_hi, s, C.byref(sums), C.byref(hdr))
+        return err, sums, hdr
+
+    def compare_image_set_device(self, ctx, entries, block_errors=None, stream=None):
+        """astcenc_amd_compare_image_set_device over `entries` (see _set_args; an entry's image is the original, nothing in an entry
+        is written).  Returns (error, [ErrorSums per entry]); block_errors (optional, float64, four values per block of the whole
+        set) receives every entry's per-block squared errors back to back."""
+        arr, n, s = self._set_args(entries, stream)
+        sums = (ErrorSums * max(n, 1))()
+        err = self.lib.astcenc_amd_compare_image_set_device(ctx, arr, n, None if block_errors is None else block_errors.data_ptr(),
+                                                            0 if block_errors is None else block_errors.numel() * 8, s, sums)
+        return err, list(sums)[:n]
 
     def mip_chain_layout(self, cfg, w, h, dtype, levels=0):
         """astcenc_amd_mip_chain_layout for the footprint of `cfg` (a Config); dtype: TYPE_*.  Returns (error, MipChainLayout)."""

@@ -649,6 +649,80 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compare_images_hdr_device(
 	struct astcenc_amd_error_sums* sums,
 	struct astcenc_amd_hdr_error_sums* hdr_sums);
 
+/* Compressed blocks scored against their source image in one device pass: what a compression cost, without the decoded
+ * image -- a buffer the size of the texture, written once and read once -- that the pair astcenc_amd_decompress_image_device +
+ * astcenc_amd_compare_images_device needs.
+ *
+ * Let D be the image astcenc_amd_decompress_image_device writes for (device_blocks, dim_x, dim_y, dim_z, decode_type,
+ * swizzle).  `sums` (and `hdr_sums`) are what astcenc_amd_compare_images_device (and _hdr_device) return for
+ * (device_image, image_type) as image 1 and (D, decode_type) as image 2: the original is image 1, so the alpha scaling and
+ * rgb_peak come from it.  D is never written: every texel is compared where the decoder would have stored it, as the bits it
+ * would have stored -- the packed RGBA8 pixel, the half, the float -- so every per-texel term is bit for bit the one the two
+ * calls form (an error block is magenta for U8 and NaN, compared as 0, for F16 / F32).  `texels` and `rgb_peak` are exact; the
+ * fp64 sums are added in a fixed order of the kernel's own, without atomics: they agree with the two calls' to fp64 rounding
+ * and are the same doubles on every run.
+ *
+ * device_block_errors (optional: NULL and 0): one record per block, raster block order (x, then y, then z; for a 2D
+ * footprint and dim_z > 1 the blocks of slice z follow those of slice z - 1, as in the stream): the sum of squared_error
+ * term c over the block's texels that lie inside the image.
+ *
+ *   - The context, blocks, data_len, dimensions, swizzle and image pointer are checked as in
+ *     astcenc_amd_decompress_image_device, with its error codes; ASTCENC_ERR_BAD_PARAM also for a null context, swizzle or
+ *     `sums` (`hdr_sums`), an unknown type, f-stops outside -125..125 or reversed; ASTCENC_ERR_OUT_OF_MEM for a non-null
+ *     device_block_errors with block_errors_len below 32 bytes per block.  Everything is checked before anything is launched, and
+ *     an error writes nothing.
+ *   - Nothing but device_block_errors is written on the device; the original and the blocks are only read.
+ *   - The work is queued on hip_stream (NULL: the context's own stream) and has completed on return.
+ *   - The library's scratch for partial sums has a fixed size (9 MiB per device, allocated by the first such call and reused);
+ *     ASTCENC_ERR_OUT_OF_MEM when it cannot be allocated. */
+struct astcenc_amd_block_error {
+	double squared_error[4];               /* per channel, original - decoded, over the block's texels inside the image */
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compare_blocks_device(
+	struct astcenc_context* context,
+	const void* device_blocks, size_t data_len,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_type image_type,
+	enum astcenc_type decode_type,
+	const struct astcenc_swizzle* swizzle,
+	struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	void* hip_stream,
+	struct astcenc_amd_error_sums* sums);
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compare_blocks_hdr_device(
+	struct astcenc_context* context,
+	const void* device_blocks, size_t data_len,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_type image_type,
+	enum astcenc_type decode_type,
+	const struct astcenc_swizzle* swizzle,
+	struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	int fstop_lo, int fstop_hi,
+	void* hip_stream,
+	struct astcenc_amd_error_sums* sums,
+	struct astcenc_amd_hdr_error_sums* hdr_sums);
+
+/* The same for an image set -- the levels of a mip chain, the layers of an array, a batch of textures -- in one call:
+ * entries[i].image is the original (read), entries[i].blocks the stream (read), nothing in an entry is written; the blocks are
+ * decoded to the entry's data_type, which is also the original's type.  sums[i] holds the very doubles
+ * astcenc_amd_compare_blocks_device returns for entry i alone (that call is a set of one entry), and device_block_errors
+ * (optional) receives every entry's block records back to back in entry order, each entry's part as the single call writes
+ * it.  The argument rules of astcenc_amd_decompress_images_device: every entry is checked as the single call checks its image
+ * before anything is launched, and the log callback names a bad entry; the call runs on the device that owns entry 0's image,
+ * a buffer of another device is ASTCENC_ERR_BAD_PARAM; entry_count == 0 succeeds and does nothing; a null `entries` with a
+ * non-zero count, a null context or `sums`, or more than 2^32 - 1 blocks in all are ASTCENC_ERR_BAD_PARAM; a
+ * block_errors_len below 32 bytes per block of the whole set is ASTCENC_ERR_OUT_OF_MEM.
+ * HDR sums for sets are not provided: call astcenc_amd_compare_blocks_hdr_device per image. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compare_image_set_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	void* hip_stream,
+	struct astcenc_amd_error_sums* sums);
+
 /* "hip:gfx950" for the product library. */
 ASTCENC_PUBLIC const char* astcenc_amd_backend_name(void);
 
