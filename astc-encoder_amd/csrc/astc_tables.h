@@ -317,6 +317,8 @@ struct ImageDesc {
 	uint32_t dim_z, blocks_z; // slices of a volume / 2D array image (1 for a plain 2D image)
 	uint32_t fast_load_slice0; // reference behaviour of the RGBA8 fast loader on a multi-slice image: every slice's
 	                           // blocks are read from slice 0 (ref: astcenc_image.cpp:304); 0 = read the block's own slice
+	const uint32_t* list;      // null: the launch's positions are the image's blocks; else positions in this device array of raster
+	                           // block indices (astcenc_amd_compress_block_list_device), an index past the image's blocks is skipped
 };
 
 // One entry of a compressed image set (image_set.h): the image as a single call would hand it to the kernel, and where its

@@ -531,32 +531,7 @@ astcenc_error astcenc_amd_compress_volume_device(astcenc_context* ctx, const voi
 	size_t block_count;
 	astcenc_error status = check_compress_args(ctx, dim_x, dim_y, dim_z, swizzle, data_len, 0, block_count);
 	if (status != ASTCENC_SUCCESS) return status;
-	const bool alpha_scale = ctx->config.a_scale_radius != 0 && ctx->config.block_z <= 1;
-
-	CompressJob job;
-	memset(&job, 0, sizeof(job));
-	job.device_data = device_image;
-	job.dim_x = dim_x;
-	job.dim_y = dim_y;
-	job.dim_z = dim_z;
-	job.data_type = (uint32_t)data_type;
-	job.swz[0] = swizzle->r; job.swz[1] = swizzle->g; job.swz[2] = swizzle->b; job.swz[3] = swizzle->a;
-	job.device_out = static_cast<uint8_t*>(device_out);
-	job.stream = hip_stream;
-	job.kernel_ms = kernel_ms;
-	job.a_scale_radius = alpha_scale ? ctx->config.a_scale_radius : 0u;
-	// default of this entry point (which has no reference counterpart to match): every slice from its own data
-	job.fast_load_slice0 = ctx->per_slice_fast_load == 0 ? 1u : 0u;
-
-	// A device-resident call is a single-caller operation.  On a thread_count == 1 context it starts from a clean
-	// state like astcenc_compress_image does there (a cancel issued before the call is forgotten; one issued while
-	// it runs stops it at the next chunk).  On a multi-thread context a cancel is sticky until
-	// astcenc_compress_reset -- a device call must not swallow the cancel of a concurrent or later
-	// astcenc_compress_image -- so a pending one stops this call as well.  Calls on one context are serialised per
-	// device inside the backend.
-	if (ctx->thread_count == 1) ctx->cancel_flag.store(0);
-	job.cancel_flag = &ctx->cancel_flag;
-	job.progress = ctx->config.progress_callback;
+	const CompressJob job = device_compress_job(ctx, device_image, dim_x, dim_y, dim_z, data_type, swizzle, device_out, hip_stream, kernel_ms);
 	int rc = backend_compress(ctx->backend, job);
 	return rc == 0 ? ASTCENC_SUCCESS : rc == 1 ? ASTCENC_ERR_OUT_OF_MEM : rc == 3 ? ASTCENC_ERR_BAD_PARAM : ASTCENC_ERR_BAD_CONTEXT;
 }

@@ -36,6 +36,11 @@ struct CompressJob {
 	// above the shard's first row and halo_below rows follow its last one (dim_y counts the shard's own rows only).  The
 	// pre-pass runs over all of them, the blocks of the shard's own rows are compressed (backend_compress sets these).
 	uint32_t halo_above, halo_below;
+	// A block list (astcenc_amd_compress_block_list_device, device-resident jobs only; device_list null: every block of the image):
+	// the list_count raster block indices at device_list are compressed into their own slots of device_out, nothing else of it
+	// is written.
+	const uint32_t* device_list;
+	uint32_t list_count;
 };
 
 struct DecompressJob {
@@ -94,6 +99,7 @@ inline ImageDesc image_desc(const TableRoot& root, int32_t profile, const Compre
 	img.fast_load_slice0 = job.fast_load_slice0;
 	img.alpha_avg = nullptr;
 	img.a_scale_radius = job.a_scale_radius;
+	img.list = job.device_list;
 	return img;
 }
 
@@ -196,6 +202,31 @@ int backend_compare(Backend* b, const CompareJob& job);
 int backend_compress_set(Backend* b, const CompressSetJob& job);
 int backend_decompress_set(Backend* b, const DecompressSetJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
+/* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
+ * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
+ * backend_adaptive_refine: everything of astcenc_amd_compress_image_adaptive_device after the base pass, on the strong context. */
+struct SelectJob {
+	const double* device_block_errors;   // four doubles per block
+	uint32_t dim_x, dim_y, dim_z;        // the image; the footprint is the context's
+	uint32_t blocks;                     // ... and its blocks, as the entry point counted them
+	double weight[4], max_mse;
+	uint32_t* device_list;
+	void* stream;
+	uint32_t* count;
+};
+struct AdaptiveJob {
+	CompressJob strong;                  // the strong pass as a device job of the whole image: device_out holds the base stream
+	DecompressDeviceJob decode;          // how the streams are scored (device_image unused, data_type = the image's)
+	double weight[4], max_mse;
+	double* device_block_errors;         // null, or the caller's records
+	uint32_t* selected; uint32_t* replaced;
+	float* kernel_ms_strong; float* kernel_ms_other;   // both null or both set
+};
+int backend_select_blocks(Backend* b, const SelectJob& job);
+/* ... and its scratch on the device that owns the image, allocated (1: out of memory) before the base pass writes anything; the
+ * output and the records (null: the library's own) must live on that device (else 3). */
+int backend_adaptive_reserve(Backend* b, const void* device_image, const void* device_out, const void* device_block_errors, size_t blocks);
+int backend_adaptive_refine(Backend* b, const AdaptiveJob& job);
 int backend_generate_mips(Backend* b, const MipChainJob& job);
 int backend_resize(Backend* b, const ResizeJob& job);
 /* A line for the diagnostics callback (astcenc_amd_set_log_callback), printf-style. */
@@ -215,8 +246,9 @@ struct KernelLaunch {
 	uint32_t first, count;
 	void* stream;                    // hipStream_t
 	unsigned long long* d_prof;      // stage timers (profiling builds) or null
-	const ImageSetTable* d_set;      // null: blocks [first, first + count) of `img` into `d_out`; else an image set's table (image_set.h):
-	                                 // the blocks of all entries back to back, `img` and `d_out` unused
+	const ImageSetTable* d_set;      // null: blocks [first, first + count) of `img` into `d_out` (positions of img.list when that is set: each
+	                                 // listed block goes to its own slot); else an image set's table (image_set.h): the blocks of all entries
+	                                 // back to back, `img` and `d_out` unused
 };
 
 /* Return 0 on success, a hipError_t value otherwise. `prepare` sets the dynamic-LDS attribute and
@@ -298,6 +330,34 @@ size_t astc_quality_set_bytes(uint32_t count);
 size_t astc_quality_scratch_doubles();
 uint32_t astc_quality_set_build(void* out, const QualityLaunch* entries, uint32_t count);
 int astc_quality_set_launch(const void* h_table, const void* d_table, double* d_partials, double* d_sums, int hdr, int fstop_lo, int fstop_hi, void* stream);
+
+/* Block selection (kernel_select.hip, block_select.h).  astc_select_launch queues the count, scan and scatter kernels:
+ * d_list[0 .. n) receives the ascending indices of the selected blocks, d_counts (astc_select_scratch_words(blocks) words) ends in
+ * n at word astc_select_total_word(blocks).  astc_merge_launch: for each of the *d_count listed blocks whose `strong` record is
+ * strictly better than its `base` record, the 16 bytes of d_strong replace those of d_out and the record replaces the base
+ * one (d_base_errors is updated in place); *d_replaced counts them (zeroed by the launch). */
+struct SelectLaunch {
+	const double* d_errors;
+	uint32_t dim_x, dim_y, dim_z, block_x, block_y, block_z, blocks;
+	double weight[4], max_mse;
+	uint32_t* d_list;
+	uint32_t* d_counts;
+	void* stream;
+};
+size_t astc_select_scratch_words(size_t blocks);
+size_t astc_select_total_word(size_t blocks);
+int astc_select_launch(const SelectLaunch& s);
+struct MergeLaunch {
+	const uint32_t* d_list; const uint32_t* d_count;
+	uint32_t blocks;                 // of the image: a list entry past them is skipped
+	uint32_t max_count;              // the grid covers this many list positions (the host's copy of *d_count)
+	const double* d_strong_errors; double* d_base_errors;
+	const uint8_t* d_strong; uint8_t* d_out;
+	double weight[4];
+	uint32_t* d_replaced;
+	void* stream;
+};
+int astc_merge_launch(const MergeLaunch& m);
 
 /* Mip chain generation (kernel_mips.hip): queues the launches of `job` on `stream` (job.stream unused), level i made from level
  * i - 1.  d_srgb: the tables of astc_mip_srgb_tables_build in device memory (astc_mip_srgb_table_bytes()), used for RGBA8 when

@@ -73,6 +73,9 @@ struct DeviceSlot {
 	double* d_sums = nullptr;     // totals of the image comparison kernel
 	double* d_quality = nullptr; size_t quality_cap = 0;   // partial sums of the block quality kernel (kernel_quality.hip), a fixed size
 	double* d_quality_sums = nullptr; size_t quality_sums_cap = 0;   // ... and its totals, per entry of the set
+	uint32_t* d_select = nullptr; size_t select_cap = 0;   // per-tile counts of the selection kernels, then the merge's counter (kernel_select.hip)
+	uint8_t* d_adaptive = nullptr; size_t adaptive_cap = 0;   // the adaptive driver's stream copy, records and list (backend_adaptive_refine)
+	hipEvent_t ev_adapt[2] = {};  // around the adaptive driver's work on the strong context (created on first use)
 	std::mutex busy;              // one call at a time per slot: the staging buffers and events are shared state
 	std::vector<int> local_cpus;  // host CPUs on the device's NUMA node (Linux sysfs); empty: unknown, no binding
 	SlotWorker* worker = nullptr; // the slot's parked host thread (slots 1.. of a multi-device context), or null
@@ -367,6 +370,9 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_sums) (void)hipFree(s->d_sums);
 	if (s->d_quality) (void)hipFree(s->d_quality);
 	if (s->d_quality_sums) (void)hipFree(s->d_quality_sums);
+	if (s->d_select) (void)hipFree(s->d_select);
+	if (s->d_adaptive) (void)hipFree(s->d_adaptive);
+	for (hipEvent_t e : s->ev_adapt) if (e) (void)hipEventDestroy(e);
 	if (s->d_prof) (void)hipFree(s->d_prof);
 	for (int i = 0; i < 2; i++) { if (s->h_in[i]) (void)hipHostFree(s->h_in[i]); if (s->h_out[i]) (void)hipHostFree(s->h_out[i]); }
 	for (hipEvent_t e : { s->ev_copy[0], s->ev_copy[1], s->ev_band, s->ev_done[0], s->ev_done[1], s->ev_done[2], s->ev_out[0], s->ev_out[1], s->ev0, s->ev1, s->ev_gen })
@@ -905,7 +911,8 @@ static int compress_pipeline(Backend* b, DeviceSlot* s, hipStream_t stream, cons
 {
 	const BlockGrid grid = block_grid(b->root, job);
 	const uint32_t bsy = b->root.dim_y, dim_z = grid.dim_z, blocks_x = grid.x, blocks_y = grid.y;
-	const size_t nblocks = grid.count();
+	// (a block list: the launches cover the positions of the list, everything else is the whole image's)
+	const size_t nblocks = job.device_list ? (size_t)job.list_count : grid.count();
 	jit_count_blocks(b, s, nblocks);
 	const size_t row_bytes = (size_t)job.dim_x * texel_bytes(job.data_type);
 	// (a shard of the alpha-scale split carries halo rows around its own: they are uploaded and averaged, not compressed)
@@ -914,7 +921,7 @@ static int compress_pipeline(Backend* b, DeviceSlot* s, hipStream_t stream, cons
 	const uint32_t rows_with_halo = job.dim_y + halo_above + halo_below;
 	const size_t slice_bytes = rows_with_halo * row_bytes;
 	const size_t image_bytes = slice_bytes * dim_z;
-	const size_t out_bytes = nblocks * 16;
+	const size_t out_bytes = grid.count() * 16;
 
 	const void* d_image = job.device_data;
 	uint8_t* d_out = job.device_out;
@@ -997,7 +1004,7 @@ static int compress_pipeline(Backend* b, DeviceSlot* s, hipStream_t stream, cons
 #if defined(ASTC_TRACE)
 	{
 		// debug build: one trace slice per block, dumped to $ASTCENC_AMD_TRACE_FILE after the call (wave_ctx.h: TRACE_PUT)
-		const size_t need = nblocks * TRACE_WORDS_PER_BLOCK_HOST * sizeof(uint32_t);
+		const size_t need = grid.count() * TRACE_WORDS_PER_BLOCK_HOST * sizeof(uint32_t);
 		if (grow(s->d_prof, s->trace_cap, need) != 0) return 1;
 		HIP_TRY(hipMemsetAsync(s->d_prof, 0, need, stream), return 2);
 	}
@@ -1049,7 +1056,7 @@ static int compress_pipeline(Backend* b, DeviceSlot* s, hipStream_t stream, cons
 #if defined(ASTC_TRACE)
 	if (const char* path = getenv("ASTCENC_AMD_TRACE_FILE"))
 	{
-		std::vector<uint32_t> host(nblocks * TRACE_WORDS_PER_BLOCK_HOST);
+		std::vector<uint32_t> host(grid.count() * TRACE_WORDS_PER_BLOCK_HOST);
 		HIP_TRY(hipMemcpy(host.data(), s->d_prof, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), return 2);
 		if (FILE* f = fopen(path, "wb")) { fwrite(host.data(), sizeof(uint32_t), host.size(), f); fclose(f); }
 	}
@@ -1196,11 +1203,12 @@ int backend_compress(Backend* b, const CompressJob& job)
 {
 	const BlockGrid grid = block_grid(b->root, job);
 	Progress progress;
-	progress.done = 0; progress.callback = job.progress; progress.total = grid.count();
+	progress.done = 0; progress.callback = job.progress; progress.total = job.device_list ? job.list_count : grid.count();
 
-	// Buffers that already live on a device are compressed there.
+	// Buffers that already live on a device are compressed there (a block list must live there as well).
+	const void* list_ptr[1] = { job.device_list };
 	if (!job.host_slices)
-		return run_on_owner(b, job.device_data, nullptr, 0, job.stream, [&](DeviceSlot* s, hipStream_t stream) { return compress_on_slot(b, s, stream, job, &progress); });
+		return run_on_owner(b, job.device_data, list_ptr, 1, job.stream, [&](DeviceSlot* s, hipStream_t stream) { return compress_on_slot(b, s, stream, job, &progress); });
 
 	// Host images: contiguous ranges of block rows (2D) or of block layers (volumes, stacks of slices), one per device,
 	// each running its own pipeline on its own streams from its own host thread; the caller's thread takes the first
@@ -1480,43 +1488,191 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial
  * sums has a fixed size (rc 1 when it cannot be had, nothing launched), the totals come back once the stream has run. */
+static int compare_blocks_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const QualitySetJob& job)
+{
+	std::vector<QualityLaunch> q(job.count);
+	for (uint32_t e = 0; e < job.count; e++)
+	{
+		const QualityEntryJob& en = job.entries[e];
+		hipPointerAttribute_t attr;
+		memset(&attr, 0, sizeof(attr));
+		if (en.device_block_errors && hipPointerGetAttributes(&attr, en.device_block_errors) == hipSuccess && attr.device != s->device)
+		{
+			log_msg("image set entry %u: the block error buffer is on device %d, entry 0's image on device %d", e, attr.device, s->device);
+			return 3;
+		}
+		(void)hipGetLastError();
+		q[e].decode = decode_launch(b, s, en.decode, en.decode.device_blocks, nullptr, nullptr);
+		q[e].d_original = en.device_original; q[e].original_type = en.original_type;
+		q[e].d_block_errors = en.device_block_errors;
+	}
+	const size_t sums_bytes = (size_t)job.count * METRIC_SUMS_HOST * sizeof(double);
+	if (grow(s->d_quality, s->quality_cap, astc_quality_scratch_doubles() * sizeof(double)) != 0 ||
+	    grow(s->d_quality_sums, s->quality_sums_cap, sums_bytes) != 0) return 1;
+	const size_t bytes = astc_quality_set_bytes(job.count);
+	s->h_set.assign(bytes, 0);
+	astc_quality_set_build(s->h_set.data(), q.data(), job.count);
+	// (a set of one entry -- the single-image calls -- needs no table on the device)
+	const int urc = job.count > 1 ? set_table_upload(s, stream, bytes) : 0;
+	if (urc != 0) return urc;
+	int lrc = astc_quality_set_launch(s->h_set.data(), job.count > 1 ? s->d_set : nullptr, s->d_quality, s->d_quality_sums, job.hdr, job.fstop_lo, job.fstop_hi, stream);
+	if (lrc != 0) { log_msg("block quality kernel launch failed (hip error %d)", lrc); return 2; }
+	std::vector<double> raw((size_t)job.count * METRIC_SUMS_HOST);
+	HIP_TRY(hipMemcpyAsync(raw.data(), s->d_quality_sums, sums_bytes, hipMemcpyDeviceToHost, stream), return 2);
+	HIP_TRY(hipStreamSynchronize(stream), return 2);
+	memcpy(job.sums, raw.data(), sums_bytes);
+	return 0;
+}
+
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job)
 {
 	std::vector<const void*> ptrs;
 	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_original); ptrs.push_back(job.entries[e].decode.device_blocks); }
 	return run_on_owner(b, job.entries[0].device_original, ptrs.data(), ptrs.size(), job.stream, [&](DeviceSlot* s, hipStream_t stream)
 	{
-		std::vector<QualityLaunch> q(job.count);
-		for (uint32_t e = 0; e < job.count; e++)
-		{
-			const QualityEntryJob& en = job.entries[e];
-			hipPointerAttribute_t attr;
-			memset(&attr, 0, sizeof(attr));
-			if (en.device_block_errors && hipPointerGetAttributes(&attr, en.device_block_errors) == hipSuccess && attr.device != s->device)
-			{
-				log_msg("image set entry %u: the block error buffer is on device %d, entry 0's image on device %d", e, attr.device, s->device);
-				return 3;
-			}
-			(void)hipGetLastError();
-			q[e].decode = decode_launch(b, s, en.decode, en.decode.device_blocks, nullptr, nullptr);
-			q[e].d_original = en.device_original; q[e].original_type = en.original_type;
-			q[e].d_block_errors = en.device_block_errors;
-		}
-		const size_t sums_bytes = (size_t)job.count * METRIC_SUMS_HOST * sizeof(double);
-		if (grow(s->d_quality, s->quality_cap, astc_quality_scratch_doubles() * sizeof(double)) != 0 ||
-		    grow(s->d_quality_sums, s->quality_sums_cap, sums_bytes) != 0) return 1;
-		const size_t bytes = astc_quality_set_bytes(job.count);
-		s->h_set.assign(bytes, 0);
-		astc_quality_set_build(s->h_set.data(), q.data(), job.count);
-		// (a set of one entry -- the single-image calls -- needs no table on the device)
-		const int urc = job.count > 1 ? set_table_upload(s, stream, bytes) : 0;
-		if (urc != 0) return urc;
-		int lrc = astc_quality_set_launch(s->h_set.data(), job.count > 1 ? s->d_set : nullptr, s->d_quality, s->d_quality_sums, job.hdr, job.fstop_lo, job.fstop_hi, stream);
-		if (lrc != 0) { log_msg("block quality kernel launch failed (hip error %d)", lrc); return 2; }
-		std::vector<double> raw((size_t)job.count * METRIC_SUMS_HOST);
-		HIP_TRY(hipMemcpyAsync(raw.data(), s->d_quality_sums, sums_bytes, hipMemcpyDeviceToHost, stream), return 2);
+		return compare_blocks_on_slot(b, s, stream, job);
+	});
+}
+
+/* The selection launches of `job` on slot `s` (list: where the indices go); the count stays on the device, at *d_count. */
+static int select_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const SelectJob& job, uint32_t* d_list, const uint32_t** d_count)
+{
+	const size_t blocks = job.blocks;
+	// (one word past the counts: the merge kernel's counter)
+	if (grow(s->d_select, s->select_cap, (astc_select_scratch_words(blocks) + 1) * sizeof(uint32_t)) != 0) return 1;
+	SelectLaunch l;
+	l.d_errors = job.device_block_errors;
+	l.dim_x = job.dim_x; l.dim_y = job.dim_y; l.dim_z = job.dim_z;
+	l.block_x = b->root.dim_x; l.block_y = b->root.dim_y; l.block_z = b->root.dim_z; l.blocks = job.blocks;
+	for (int i = 0; i < 4; i++) l.weight[i] = job.weight[i];
+	l.max_mse = job.max_mse;
+	l.d_list = d_list; l.d_counts = s->d_select; l.stream = stream;
+	const int lrc = astc_select_launch(l);
+	if (lrc != 0) { log_msg("block selection kernel launch failed (hip error %d)", lrc); return 2; }
+	*d_count = s->d_select + astc_select_total_word(blocks);
+	return 0;
+}
+
+int backend_select_blocks(Backend* b, const SelectJob& job)
+{
+	const void* ptrs[1] = { job.device_list };
+	return run_on_owner(b, job.device_block_errors, ptrs, 1, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		const uint32_t* d_count = nullptr;
+		const int rc = select_on_slot(b, s, stream, job, job.device_list, &d_count);
+		if (rc != 0) return rc;
+		uint32_t count = 0;
+		HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, stream), return 2);
 		HIP_TRY(hipStreamSynchronize(stream), return 2);
-		memcpy(job.sums, raw.data(), sums_bytes);
+		*job.count = count;
+		return 0;
+	});
+}
+
+/* astcenc_amd_compress_image_adaptive_device after its base pass (job.strong.device_out holds the base stream B0), all of it on
+ * the strong context's slot of the device that owns the image and on one stream:
+ *   score B0 -> E0 (the caller's records, or scratch) | select E0 -> list, count | with no block selected, done
+ *   copy B0 -> S (scratch) | strong pass over the list into S | score S -> E1 (scratch) | merge: S and E1 over B0 and E0 where better
+ * Scratch: S, E1, E0 unless the caller's, the list: 16 + 32 (+ 32) + 4 bytes per block, sized before anything is launched. */
+static size_t adaptive_scratch_bytes(size_t blocks, bool own_records) { return blocks * (16 + 32 + (own_records ? 32 : 0) + 4); }
+
+int backend_adaptive_reserve(Backend* b, const void* device_image, const void* device_out, const void* device_block_errors, size_t blocks)
+{
+	const void* ptrs[2] = { device_out, device_block_errors };
+	const bool own_records = device_block_errors == nullptr;
+	return run_on_owner(b, device_image, ptrs, 2, nullptr, [&](DeviceSlot* s, hipStream_t)
+	{
+		if (grow(s->d_adaptive, s->adaptive_cap, adaptive_scratch_bytes(blocks, own_records)) != 0 ||
+		    grow(s->d_select, s->select_cap, (astc_select_scratch_words(blocks) + 1) * sizeof(uint32_t)) != 0 ||
+		    grow(s->d_quality, s->quality_cap, astc_quality_scratch_doubles() * sizeof(double)) != 0 ||
+		    grow(s->d_quality_sums, s->quality_sums_cap, METRIC_SUMS_HOST * sizeof(double)) != 0) return 1;
+		return 0;
+	});
+}
+
+int backend_adaptive_refine(Backend* b, const AdaptiveJob& job)
+{
+	const CompressJob& cj = job.strong;
+	const void* ptrs[2] = { cj.device_out, job.device_block_errors };
+	return run_on_owner(b, cj.device_data, ptrs, 2, cj.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		const size_t blocks = block_grid(b->root, cj).count();
+		const size_t at_e1 = blocks * 16, at_e0 = at_e1 + blocks * 32, at_list = at_e0 + (job.device_block_errors ? 0 : blocks * 32);
+		if (grow(s->d_adaptive, s->adaptive_cap, adaptive_scratch_bytes(blocks, !job.device_block_errors)) != 0) return 1;
+		uint8_t* d_stream = s->d_adaptive;
+		double* d_e1 = reinterpret_cast<double*>(s->d_adaptive + at_e1);
+		double* d_e0 = job.device_block_errors ? job.device_block_errors : reinterpret_cast<double*>(s->d_adaptive + at_e0);
+		uint32_t* d_list = reinterpret_cast<uint32_t*>(s->d_adaptive + at_list);
+		const bool timed = job.kernel_ms_other != nullptr;
+		if (timed)
+		{
+			for (hipEvent_t& e : s->ev_adapt) if (!e) HIP_TRY(hipEventCreate(&e), return 2);
+			HIP_TRY(hipEventRecord(s->ev_adapt[0], stream), return 2);
+		}
+		double sums[METRIC_SUMS_HOST];
+		QualityEntryJob q;
+		memset(&q, 0, sizeof(q));
+		q.decode = job.decode;
+		q.decode.device_blocks = cj.device_out;
+		q.device_original = cj.device_data; q.original_type = cj.data_type;
+		q.device_block_errors = d_e0;
+		QualitySetJob qs;
+		memset(&qs, 0, sizeof(qs));
+		qs.entries = &q; qs.count = 1; qs.stream = stream; qs.sums = sums;
+		int rc = compare_blocks_on_slot(b, s, stream, qs);
+		if (rc != 0) return rc;
+
+		SelectJob sj;
+		memset(&sj, 0, sizeof(sj));
+		sj.device_block_errors = d_e0;
+		sj.dim_x = cj.dim_x; sj.dim_y = cj.dim_y; sj.dim_z = cj.dim_z ? cj.dim_z : 1u;
+		sj.blocks = (uint32_t)blocks;
+		for (int i = 0; i < 4; i++) sj.weight[i] = job.weight[i];
+		sj.max_mse = job.max_mse;
+		const uint32_t* d_count = nullptr;
+		rc = select_on_slot(b, s, stream, sj, d_list, &d_count);
+		if (rc != 0) return rc;
+		uint32_t count = 0;
+		HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		*job.selected = count;
+		*job.replaced = 0;
+		float strong_ms = 0.0f;
+		if (count != 0)
+		{
+			HIP_TRY(hipMemcpyAsync(d_stream, cj.device_out, blocks * 16, hipMemcpyDeviceToDevice, stream), return 2);
+			CompressJob lj = cj;
+			lj.device_out = d_stream;
+			lj.device_list = d_list; lj.list_count = count;
+			lj.kernel_ms = timed ? &strong_ms : nullptr;
+			Progress progress;
+			progress.done = 0; progress.callback = lj.progress; progress.total = count;
+			rc = compress_on_slot(b, s, stream, lj, &progress);
+			if (rc != 0) return rc;
+			q.decode.device_blocks = d_stream;
+			q.device_block_errors = d_e1;
+			rc = compare_blocks_on_slot(b, s, stream, qs);
+			if (rc != 0) return rc;
+			uint32_t* d_replaced = s->d_select + astc_select_scratch_words(blocks);
+			MergeLaunch m;
+			m.d_list = d_list; m.d_count = d_count; m.blocks = (uint32_t)blocks; m.max_count = count;
+			m.d_strong_errors = d_e1; m.d_base_errors = d_e0;
+			m.d_strong = d_stream; m.d_out = cj.device_out;
+			for (int i = 0; i < 4; i++) m.weight[i] = job.weight[i];
+			m.d_replaced = d_replaced; m.stream = stream;
+			const int mrc = astc_merge_launch(m);
+			if (mrc != 0) { log_msg("block merge kernel launch failed (hip error %d)", mrc); return 2; }
+			HIP_TRY(hipMemcpyAsync(job.replaced, d_replaced, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), return 2);
+		}
+		if (timed) HIP_TRY(hipEventRecord(s->ev_adapt[1], stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		if (timed)
+		{
+			float all_ms = 0.0f;
+			HIP_TRY(hipEventElapsedTime(&all_ms, s->ev_adapt[0], s->ev_adapt[1]), return 2);
+			*job.kernel_ms_strong = strong_ms;
+			*job.kernel_ms_other = all_ms > strong_ms ? all_ms - strong_ms : 0.0f;
+		}
 		return 0;
 	});
 }

@@ -9,6 +9,7 @@
 
 #include <atomic>
 #include <condition_variable>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -100,6 +101,37 @@ inline astcenc_error check_decompress_device_args(astcenc_context* ctx, const vo
 	if (overflow || block_count == 0) return ASTCENC_ERR_BAD_PARAM;
 	if (data_len < block_count * 16) return ASTCENC_ERR_OUT_OF_MEM;
 	return ASTCENC_SUCCESS;
+}
+
+/* The job of astcenc_amd_compress_volume_device for arguments that check_compress_args has passed: every device-resident
+ * compression of one image is this job (astcenc_amd_compress_block_list_device adds its list).
+ * A device-resident call is a single-caller operation.  On a thread_count == 1 context it starts from a clean state like
+ * astcenc_compress_image does there (a cancel issued before the call is forgotten; one issued while it runs stops it at the
+ * next chunk).  On a multi-thread context a cancel is sticky until astcenc_compress_reset -- a device call must not swallow
+ * the cancel of a concurrent or later astcenc_compress_image -- so a pending one stops this call as well.  Calls on one
+ * context are serialised per device inside the backend. */
+inline CompressJob device_compress_job(astcenc_context* ctx, const void* device_image, unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+                                       astcenc_type data_type, const astcenc_swizzle* swizzle, void* device_out, void* hip_stream, float* kernel_ms)
+{
+	const bool alpha_scale = ctx->config.a_scale_radius != 0 && ctx->config.block_z <= 1;
+	CompressJob job;
+	memset(&job, 0, sizeof(job));
+	job.device_data = device_image;
+	job.dim_x = dim_x;
+	job.dim_y = dim_y;
+	job.dim_z = dim_z;
+	job.data_type = (uint32_t)data_type;
+	job.swz[0] = swizzle->r; job.swz[1] = swizzle->g; job.swz[2] = swizzle->b; job.swz[3] = swizzle->a;
+	job.device_out = static_cast<uint8_t*>(device_out);
+	job.stream = hip_stream;
+	job.kernel_ms = kernel_ms;
+	job.a_scale_radius = alpha_scale ? ctx->config.a_scale_radius : 0u;
+	// default of the device entry points (which have no reference counterpart to match): every slice from its own data
+	job.fast_load_slice0 = ctx->per_slice_fast_load == 0 ? 1u : 0u;
+	if (ctx->thread_count == 1) ctx->cancel_flag.store(0);
+	job.cancel_flag = &ctx->cancel_flag;
+	job.progress = ctx->config.progress_callback;
+	return job;
 }
 
 } // namespace astcd

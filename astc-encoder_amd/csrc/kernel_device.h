@@ -51,10 +51,18 @@ ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
                  uint8_t* __restrict__ out, uint32_t first_block, uint32_t num_blocks, unsigned long long* prof,
                  const ImageSetTable* __restrict__ set)
 {
-	uint8_t* lds = lds_base();
-
 	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
 	uint32_t b = (set ? xcd_block_remap_runs(blockIdx.x, num_blocks) : xcd_block_remap(blockIdx.x, num_blocks)) + first_block;
+	// A block list (astcenc_amd_compress_block_list_device: img.list, never with a set): `b` is so far a position in the list, the
+	// XCD remap included; the block is the one named there, compressed into its own raster slot.  One scalar load through a
+	// constant pointer, as for `tab` below.  An index that is no block of the image (a stale list) ends the wavefront before it
+	// touches anything.
+	if (img.list)
+	{
+		b = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(reinterpret_cast<uintptr_t>(img.list))[b];
+		if (b >= img.blocks_x * img.blocks_y * img.blocks_z) return;
+	}
+	uint8_t* lds = lds_base();
 #if defined(ASTC_TRACE)
 	const uint32_t trace_slot = b;
 #endif

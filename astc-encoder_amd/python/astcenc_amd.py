@@ -99,7 +99,9 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_generate_mip_chain_filtered_device", "astcenc_amd_compress_mip_chain_filtered_device",
                "astcenc_amd_generate_mip_chain_weighted_device", "astcenc_amd_compress_mip_chain_weighted_device",
                "astcenc_amd_resize_image_device", "astcenc_amd_resize_dims", "astcenc_amd_compare_blocks_device",
-               "astcenc_amd_compare_blocks_hdr_device", "astcenc_amd_compare_image_set_device"]
+               "astcenc_amd_compare_blocks_hdr_device", "astcenc_amd_compare_image_set_device",
+               "astcenc_amd_compress_block_list_device", "astcenc_amd_select_blocks_device",
+               "astcenc_amd_compress_image_adaptive_device"]
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
@@ -195,6 +197,21 @@ class BlockError(C.Structure):
     _fields_ = [("squared_error", C.c_double * 4)]
 
 
+class BlockCriterion(C.Structure):
+    """struct astcenc_amd_block_criterion: selected iff ((w0 s0 + w1 s1) + w2 s2) + w3 s3 > max_mean_squared_error * texels."""
+    _fields_ = [("channel_weight", C.c_double * 4), ("max_mean_squared_error", C.c_double)]
+
+
+def block_criterion(max_mean_squared_error, channel_weight=(1.0, 1.0, 1.0, 1.0)):
+    return BlockCriterion((C.c_double * 4)(*channel_weight), max_mean_squared_error)
+
+
+class AdaptiveStats(C.Structure):
+    """struct astcenc_amd_adaptive_stats."""
+    _fields_ = [("blocks", C.c_uint), ("selected", C.c_uint), ("replaced", C.c_uint),
+                ("kernel_ms_base", C.c_float), ("kernel_ms_strong", C.c_float), ("kernel_ms_other", C.c_float)]
+
+
 class AstcError(RuntimeError):
     def __init__(self, code, where):
         super().__init__("%s failed with astcenc_error %d" % (where, code))
@@ -280,6 +297,19 @@ class Library:
             L.astcenc_amd_compare_image_set_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p,
                                                                C.POINTER(ErrorSums)]
             L.astcenc_amd_compare_image_set_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_compress_block_list_device"):
+            L.astcenc_amd_compress_block_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int,
+                                                                 C.POINTER(Swizzle), C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t,
+                                                                 C.c_void_p, C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_block_list_device.restype = C.c_int
+            L.astcenc_amd_select_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint,
+                                                           C.POINTER(BlockCriterion), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint)]
+            L.astcenc_amd_select_blocks_device.restype = C.c_int
+            L.astcenc_amd_compress_image_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int,
+                                                                     C.POINTER(Swizzle), C.POINTER(Swizzle), C.POINTER(BlockCriterion),
+                                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                     C.POINTER(AdaptiveStats)]
+            L.astcenc_amd_compress_image_adaptive_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_mip_chain_layout"):
             L.astcenc_amd_mip_chain_layout.argtypes = [C.POINTER(Config), C.c_uint, C.c_uint, C.c_int, C.c_uint, C.POINTER(MipChainLayout)]
             L.astcenc_amd_mip_chain_layout.restype = C.c_int
@@ -468,6 +498,57 @@ class Library:
         sums, hdr = ErrorSums(), HdrErrorSums()
         err = self.lib.astcenc_amd_compare_blocks_hdr_device(ctx, *args, fstop_lo, fstop_hi, s, C.byref(sums), C.byref(hdr))
         return err, sums, hdr
+
+    @staticmethod
+    def _image_args(image, stream):
+        """(data pointer, dim_x, dim_y, dim_z, astcenc_type) of a contiguous device tensor [H, W, 4] or [D, H, W, 4], and the stream."""
+        import torch
+        types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
+        assert image.is_contiguous() and image.dim() in (3, 4) and image.shape[-1] == 4
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        d = image.shape[0] if image.dim() == 4 else 1
+        return [image.data_ptr(), image.shape[-2], image.shape[-3], d, types[image.dtype]], getattr(stream, "cuda_stream", stream)
+
+    def compress_block_list_device(self, ctx, image, block_list, out, swizzle=SWZ_RGBA, list_count=None, data_len=None, stream=None):
+        """astcenc_amd_compress_block_list_device: the blocks of `image` named in `block_list` (a device tensor of 32-bit raster block
+        indices, or None) into their slots of `out` (device uint8, 16 bytes per block of the whole image).  list_count / data_len
+        override what the tensors say.  Returns the astcenc_error, the kernel time (ms) in self.last_kernel_ms."""
+        args, s = self._image_args(image, stream)
+        assert block_list is None or (block_list.is_contiguous() and block_list.element_size() == 4)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_block_list_device(
+            ctx, *args, C.byref(Swizzle(*swizzle)), None if block_list is None else block_list.data_ptr(),
+            (0 if block_list is None else block_list.numel()) if list_count is None else list_count,
+            out.data_ptr(), out.numel() if data_len is None else data_len, s, C.byref(ms))
+        self.last_kernel_ms = ms.value
+        return err
+
+    def select_blocks_device(self, ctx, block_errors, dims, criterion, block_list, stream=None):
+        """astcenc_amd_select_blocks_device: `block_errors` float64 [blocks, 4] on the device, dims (x, y, z) of the image,
+        `criterion` a BlockCriterion, `block_list` a device tensor of 32-bit words, one per block.  Returns (error, count): the
+        ascending indices of the selected blocks are block_list[:count]."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream()
+        count = C.c_uint(0)
+        err = self.lib.astcenc_amd_select_blocks_device(ctx, block_errors.data_ptr(), block_errors.numel() * 8, dims[0], dims[1], dims[2],
+                                                        C.byref(criterion), block_list.data_ptr(), block_list.numel() * 4,
+                                                        getattr(stream, "cuda_stream", stream), C.byref(count))
+        return err, count.value
+
+    def compress_image_adaptive_device(self, base_ctx, strong_ctx, image, criterion, out, swizzle=SWZ_RGBA, decode_swizzle=SWZ_RGBA,
+                                       block_errors=None, stream=None):
+        """astcenc_amd_compress_image_adaptive_device: `image` compressed with base_ctx into `out`, the blocks that miss `criterion`
+        re-encoded with strong_ctx and kept where better; block_errors (optional, float64 [blocks, 4]) receives the final stream's
+        records.  Returns (error, AdaptiveStats)."""
+        args, s = self._image_args(image, stream)
+        stats = AdaptiveStats()
+        err = self.lib.astcenc_amd_compress_image_adaptive_device(
+            base_ctx, strong_ctx, *args, C.byref(Swizzle(*swizzle)), C.byref(Swizzle(*decode_swizzle)), C.byref(criterion),
+            out.data_ptr(), out.numel(), None if block_errors is None else block_errors.data_ptr(),
+            0 if block_errors is None else block_errors.numel() * 8, s, C.byref(stats))
+        return err, stats
 
     def compare_image_set_device(self, ctx, entries, block_errors=None, stream=None):
         """astcenc_amd_compare_image_set_device over `entries` (see _set_args; an entry's image is the original, nothing in an entry

@@ -723,6 +723,103 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compare_image_set_device(
 	void* hip_stream,
 	struct astcenc_amd_error_sums* sums);
 
+/* Adaptive effort: re-encode only the blocks that miss a quality target.  Three calls, each usable on its own: a launch of
+ * the compression kernel over a list of blocks, the selection of blocks by their error records, and a driver that chains
+ * base compression -> scoring -> selection -> strong compression of the selected blocks -> scoring -> keep-the-better merge,
+ * everything in device memory.
+ *   Not done: image sets and mip chains; host-pointer input; an HDR (log2 / mPSNR) criterion; a budget such as "the worst N
+ *   blocks"; more than two tiers.
+ *
+ * astcenc_amd_compress_block_list_device: device_list[i], i < list_count, is a raster block index of the image (the order
+ * of astcenc_amd_compress_volume_device, whose per-slice loading default and ASTCENC_AMD_OPT_PER_SLICE_FAST_LOAD apply).  For
+ * every i with device_list[i] < blocks the 16 bytes at device_out + 16 * device_list[i] become exactly the bytes
+ * astcenc_amd_compress_volume_device writes there for the same arguments; no other byte of device_out is written.
+ *   - Indices >= blocks are skipped (a stale list never writes outside the buffer); duplicates rewrite the same bytes; any
+ *     order; list_count == 0 succeeds, launches nothing and writes nothing.
+ *   - Checks and error codes of astcenc_amd_compress_volume_device; data_len is checked against the whole image's blocks.
+ *     Also: a null device_list with a non-zero count is ASTCENC_ERR_BAD_CONTEXT, as the other null buffers are; a list on
+ *     another device than the image, or an image of more than 2^32 - 1 blocks, is ASTCENC_ERR_BAD_PARAM.  Everything is checked
+ *     before anything is launched, and an error writes nothing.
+ *   - A context with a_scale_radius != 0 runs the alpha-average pre-pass over the whole image, as the full call does.
+ *   - The call launches the build the context launches (astcenc_amd_context_kernel_name); progress counts listed blocks,
+ *     cancel works as in the full call. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_block_list_device(
+	struct astcenc_context* context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	const unsigned int* device_list, unsigned int list_count,
+	void* device_out, size_t data_len,
+	void* hip_stream,
+	float* kernel_ms);
+
+/* The criterion a block's record (struct astcenc_amd_block_error, s = squared_error) is held against:
+ *   e = ((w0*s0 + w1*s1) + w2*s2) + w3*s3        every operation a separately rounded fp64 operation in that order, none fused
+ *   n = the block's texels inside the image      the footprint clipped on every axis; a 2D footprint over slices counts one slice
+ *   selected  iff  e > max_mean_squared_error * (double)n      one rounded multiply; a NaN e is never selected
+ * The units are those of the records: U8 as value / 255, floats clamped to 0..65504.  For equal RGBA weights a PSNR target of
+ * p dB corresponds to max_mean_squared_error = 4 * 10^(-p/10). */
+struct astcenc_amd_block_criterion {
+	double channel_weight[4];              /* each finite and >= 0 */
+	double max_mean_squared_error;         /* >= 0 or +inf; per texel, over the weighted channels */
+};
+
+/* device_list[0 .. count) receives the indices of the selected blocks of a dim_x * dim_y * dim_z image in the context's
+ * footprint (the context is used for nothing else) in ascending order; nothing past `count` is written; *selected_count (a
+ * host pointer, required) receives count.  The same list comes out on every run.  The work is queued on hip_stream (NULL: the
+ * context's own) and has completed on return.
+ *   - ASTCENC_ERR_BAD_PARAM: a null context, criterion or count pointer, a zero dimension, more than 2^32 - 1 blocks, a bad
+ *     criterion (a NaN, negative or non-finite weight, a NaN or negative threshold), a buffer or stream of another device than
+ *     the records'.  ASTCENC_ERR_BAD_CONTEXT: a null buffer.  ASTCENC_ERR_OUT_OF_MEM: block_errors_len < 32 bytes per block,
+ *     list_len < 4 bytes per block, or no memory for the library's scratch (one word per 2048 blocks).  Nothing is written on
+ *     an error. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_select_blocks_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	const struct astcenc_amd_block_criterion* criterion,
+	unsigned int* device_list, size_t list_len,
+	void* hip_stream,
+	unsigned int* selected_count);
+
+/* The driver.  Let B0 and B1 be what astcenc_amd_compress_volume_device writes with base_context and strong_context, and E0
+ * and E1 the per-block records astcenc_amd_compare_blocks_device returns for B0 and B1 against the image with decode_type ==
+ * data_type and decode_swizzle.  Block i of device_out is B1[i] if block i is selected by E0[i] and e(E1[i]) < e(E0[i]), else
+ * B0[i]; device_block_errors[i] (optional: NULL and 0) is the matching record, bit for bit what
+ * astcenc_amd_compare_blocks_device returns for the final stream.  B1 is only ever computed for the selected blocks; with no
+ * block selected the strong context launches nothing.
+ *   - The two contexts must agree in footprint, profile and flags (else ASTCENC_ERR_BAD_PARAM); neither may be
+ *     ASTCENC_FLG_DECOMPRESS_ONLY (ASTCENC_ERR_BAD_CONTEXT, as in compression).  The same context twice is legal and replaces
+ *     nothing.  All other checks are those of the calls the driver is made of (`swizzle`: compression, both passes;
+ *     `decode_swizzle`: scoring), plus ASTCENC_ERR_BAD_PARAM for a null argument other than the optional ones, a bad
+ *     criterion or an unknown data_type.  They are made before anything is launched, and an error writes nothing.
+ *   - Scratch: a copy of the stream, the records of the mixed stream, the base records unless device_block_errors is given,
+ *     and the list: at most 16 + 64 + 4 bytes per block (and the selection's word per 2048 blocks).  It is kept with the strong
+ *     context and reused; ASTCENC_ERR_OUT_OF_MEM, with nothing written, when it cannot be allocated.
+ *   - Cancel and progress: each pass behaves as astcenc_amd_compress_volume_device does on its own context (the strong pass
+ *     reports its listed blocks); after a cancelled base pass nothing is refined.
+ *   - stats (optional): the block counts, and the elapsed kernel time of the base pass, of the strong pass, and of everything
+ *     else on the stream (scoring, selection, copies, merge). */
+struct astcenc_amd_adaptive_stats {
+	unsigned int blocks, selected, replaced;
+	float kernel_ms_base, kernel_ms_strong, kernel_ms_other;
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_image_adaptive_device(
+	struct astcenc_context* base_context,
+	struct astcenc_context* strong_context,
+	const void* device_image,
+	unsigned int dim_x, unsigned int dim_y, unsigned int dim_z,
+	enum astcenc_type data_type,
+	const struct astcenc_swizzle* swizzle,
+	const struct astcenc_swizzle* decode_swizzle,
+	const struct astcenc_amd_block_criterion* criterion,
+	void* device_out, size_t data_len,
+	struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	void* hip_stream,
+	struct astcenc_amd_adaptive_stats* stats);
+
 /* "hip:gfx950" for the product library. */
 ASTCENC_PUBLIC const char* astcenc_amd_backend_name(void);
 
