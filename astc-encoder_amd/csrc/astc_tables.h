@@ -319,6 +319,9 @@ struct ImageDesc {
 	                           // blocks are read from slice 0 (ref: astcenc_image.cpp:304); 0 = read the block's own slice
 	const uint32_t* list;      // null: the launch's positions are the image's blocks; else positions in this device array of raster
 	                           // block indices (astcenc_amd_compress_block_list_device), an index past the image's blocks is skipped
+	uint32_t* tickets;         // of the launch, not of the image (it travels here: the kernel's argument list stays what it is): null, one
+	                           // workgroup per block; else the eight zeroed heads the launch's workgroups draw their blocks from
+	                           // (block_tickets.h).  Unused in the records of an image set.
 };
 
 // One entry of a compressed image set (image_set.h): the image as a single call would hand it to the kernel, and where its

@@ -100,6 +100,7 @@ inline ImageDesc image_desc(const TableRoot& root, int32_t profile, const Compre
 	img.alpha_avg = nullptr;
 	img.a_scale_radius = job.a_scale_radius;
 	img.list = job.device_list;
+	img.tickets = nullptr;
 	return img;
 }
 
@@ -249,26 +250,34 @@ struct KernelLaunch {
 	const ImageSetTable* d_set;      // null: blocks [first, first + count) of `img` into `d_out` (positions of img.list when that is set: each
 	                                 // listed block goes to its own slot); else an image set's table (image_set.h): the blocks of all entries
 	                                 // back to back, `img` and `d_out` unused
+	uint32_t grid = 0;               // img.tickets null: `count` workgroups, one per block; else the workgroups that draw the `count`
+	                                 // blocks from those heads (block_tickets.h)
 };
 
 /* Return 0 on success, a hipError_t value otherwise. `prepare` sets the dynamic-LDS attribute and
  * reports the per-workgroup LDS bytes and the LdsLayout record (<= 256 bytes) that the backend
- * appends to the device copy of the table blob together with the DeviceConfig. */
+ * appends to the device copy of the table blob together with the DeviceConfig.  `occupancy`: the workgroups of the
+ * build that one CU of the current device holds at `lds_bytes` of dynamic LDS. */
 int astc_kernel_prepare_ldr(const TableRoot& root, const DeviceConfig& cfg, uint32_t* lds_bytes, void* layout_out, uint32_t* layout_bytes);
 int astc_kernel_prepare_hdr(const TableRoot& root, const DeviceConfig& cfg, uint32_t* lds_bytes, void* layout_out, uint32_t* layout_bytes);
 int astc_kernel_launch_ldr(const KernelLaunch& k);
 int astc_kernel_launch_hdr(const KernelLaunch& k);
+int astc_kernel_occupancy_ldr(uint32_t lds_bytes, int* workgroups_per_cu);
+int astc_kernel_occupancy_hdr(uint32_t lds_bytes, int* workgroups_per_cu);
 // ... and the builds for footprints of at most 64 texels (kernel_ldr64.hip / kernel_hdr64.hip)
 int astc_kernel_prepare_ldr64(const TableRoot& root, const DeviceConfig& cfg, uint32_t* lds_bytes, void* layout_out, uint32_t* layout_bytes);
 int astc_kernel_prepare_hdr64(const TableRoot& root, const DeviceConfig& cfg, uint32_t* lds_bytes, void* layout_out, uint32_t* layout_bytes);
 int astc_kernel_launch_ldr64(const KernelLaunch& k);
 int astc_kernel_launch_hdr64(const KernelLaunch& k);
+int astc_kernel_occupancy_ldr64(uint32_t lds_bytes, int* workgroups_per_cu);
+int astc_kernel_occupancy_hdr64(uint32_t lds_bytes, int* workgroups_per_cu);
 // ... and the fixed-context builds (kernel_ldr_6x6m.hip, kernel_ldr_8x8t.hip, kernel_hdr_6x6m.hip): `prepare` returns
 // ASTC_PREPARE_NOT_THIS_CONTEXT when the context is not the one the build was compiled for
 constexpr int ASTC_PREPARE_NOT_THIS_CONTEXT = -1;
 #define ASTC_DECLARE_KERNEL_VARIANT(tag) \
 	int astc_kernel_prepare_##tag(const TableRoot& root, const DeviceConfig& cfg, uint32_t* lds_bytes, void* layout_out, uint32_t* layout_bytes); \
-	int astc_kernel_launch_##tag(const KernelLaunch& k);
+	int astc_kernel_launch_##tag(const KernelLaunch& k); \
+	int astc_kernel_occupancy_##tag(uint32_t lds_bytes, int* workgroups_per_cu);
 ASTC_DECLARE_KERNEL_VARIANT(ldr_6x6m)
 ASTC_DECLARE_KERNEL_VARIANT(ldr_8x8t)
 ASTC_DECLARE_KERNEL_VARIANT(hdr_6x6m)

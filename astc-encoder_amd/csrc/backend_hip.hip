@@ -7,6 +7,7 @@
 // instead of threads pulling 16-block tickets from an atomic counter, the block range of a chunk
 // is one kernel launch; chunks give the host cancel/progress points.
 #include "backend.h"
+#include "block_tickets.h"
 #include "kernel_jit.h"
 #include "mip_resample.h"
 
@@ -84,6 +85,12 @@ struct DeviceSlot {
 	hipModule_t jit_module = nullptr;
 	hipFunction_t jit_fn = nullptr;
 	bool jit_tried = false;
+	// block tickets (block_tickets.h): the heads of the launch in flight, the workgroups the device holds of the library's build
+	// and of the run-time build (0: not asked yet, RESIDENT_UNKNOWN: the runtime did not say; compress_grid), and the end of the
+	// last ticket launch (every ticket launch waits for it: the heads are one buffer)
+	uint32_t* d_tickets = nullptr;
+	uint32_t resident_lib = 0, resident_jit = 0;
+	hipEvent_t ev_tickets = nullptr;
 };
 
 struct Backend {
@@ -195,15 +202,16 @@ struct KernelVariant {
 	bool fixed, hdr, small;
 	int (*prepare)(const TableRoot&, const DeviceConfig&, uint32_t*, void*, uint32_t*);
 	int (*launch)(const KernelLaunch&);
+	int (*occupancy)(uint32_t, int*);
 };
 const KernelVariant kernel_variants[] = {
-	{ "astc_compress_blocks_ldr_6x6m", true, false, true, astc_kernel_prepare_ldr_6x6m, astc_kernel_launch_ldr_6x6m },
-	{ "astc_compress_blocks_ldr_8x8t", true, false, true, astc_kernel_prepare_ldr_8x8t, astc_kernel_launch_ldr_8x8t },
-	{ "astc_compress_blocks_hdr_6x6m", true, true, true, astc_kernel_prepare_hdr_6x6m, astc_kernel_launch_hdr_6x6m },
-	{ "astc_compress_blocks_ldr64", false, false, true, astc_kernel_prepare_ldr64, astc_kernel_launch_ldr64 },
-	{ "astc_compress_blocks_hdr64", false, true, true, astc_kernel_prepare_hdr64, astc_kernel_launch_hdr64 },
-	{ "astc_compress_blocks_ldr", false, false, false, astc_kernel_prepare_ldr, astc_kernel_launch_ldr },
-	{ "astc_compress_blocks_hdr", false, true, false, astc_kernel_prepare_hdr, astc_kernel_launch_hdr },
+	{ "astc_compress_blocks_ldr_6x6m", true, false, true, astc_kernel_prepare_ldr_6x6m, astc_kernel_launch_ldr_6x6m, astc_kernel_occupancy_ldr_6x6m },
+	{ "astc_compress_blocks_ldr_8x8t", true, false, true, astc_kernel_prepare_ldr_8x8t, astc_kernel_launch_ldr_8x8t, astc_kernel_occupancy_ldr_8x8t },
+	{ "astc_compress_blocks_hdr_6x6m", true, true, true, astc_kernel_prepare_hdr_6x6m, astc_kernel_launch_hdr_6x6m, astc_kernel_occupancy_hdr_6x6m },
+	{ "astc_compress_blocks_ldr64", false, false, true, astc_kernel_prepare_ldr64, astc_kernel_launch_ldr64, astc_kernel_occupancy_ldr64 },
+	{ "astc_compress_blocks_hdr64", false, true, true, astc_kernel_prepare_hdr64, astc_kernel_launch_hdr64, astc_kernel_occupancy_hdr64 },
+	{ "astc_compress_blocks_ldr", false, false, false, astc_kernel_prepare_ldr, astc_kernel_launch_ldr, astc_kernel_occupancy_ldr },
+	{ "astc_compress_blocks_hdr", false, true, false, astc_kernel_prepare_hdr, astc_kernel_launch_hdr, astc_kernel_occupancy_hdr },
 };
 /* Picks the context's variant (b->variant < 0: not chosen yet) and prepares it on the current device. */
 int kernel_prepare(Backend* b, uint32_t* lds_bytes, void* layout_out, uint32_t* layout_bytes)
@@ -230,9 +238,69 @@ int kernel_launch(const Backend* b, const DeviceSlot* s, const KernelLaunch& k)
 		// the run-time build: same parameters as the library's builds (kernel_device.h), launched through the module API
 		KernelLaunch a = k;
 		void* args[] = { &a.d_tab, &a.img, &a.d_out, &a.first, &a.count, &a.d_prof, &a.d_set };
-		return (int)hipModuleLaunchKernel(s->jit_fn, k.count, 1, 1, 64, 1, 1, k.lds_bytes, static_cast<hipStream_t>(k.stream), args, nullptr);
+		return (int)hipModuleLaunchKernel(s->jit_fn, k.img.tickets ? k.grid : k.count, 1, 1, 64, 1, 1, k.lds_bytes, static_cast<hipStream_t>(k.stream), args, nullptr);
 	}
 	return kernel_variants[b->variant].launch(k);
+}
+
+/* ASTCENC_AMD_COMPRESS_GRID, read once per process: unset (-1) a launch of more blocks than the device holds workgroups draws
+ * its blocks from tickets (block_tickets.h); 0 never; N > 0 every launch does, with min(N, blocks) workgroups (the tests'
+ * handle on the ticket path: tests/test_persistent_grid.py). */
+long compress_grid_from_env()
+{
+	static const long v = []() {
+		const char* e = getenv("ASTCENC_AMD_COMPRESS_GRID");
+		if (!e || !*e) return -1L;
+		char* end = nullptr;
+		const long n = strtol(e, &end, 10);
+		return end != e && n >= 0 && n <= 0x7fffffffL ? n : -1L;
+	}();
+	return v;
+}
+
+/* The workgroups of the build the slot launches that its device holds at once: CUs x workgroups per CU at the context's LDS
+ * size, asked once per build (current device = the slot's) and reported once to the diagnostics callback.  0: the runtime
+ * does not say; launches then stay one workgroup per block. */
+constexpr uint32_t RESIDENT_UNKNOWN = 0xFFFFFFFFu;
+uint32_t compress_grid(const Backend* b, DeviceSlot* s)
+{
+	uint32_t& resident = s->jit_fn ? s->resident_jit : s->resident_lib;
+	if (resident) return resident == RESIDENT_UNKNOWN ? 0 : resident;
+	int cus = 0, per_cu = 0;
+	hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
+	if (e == hipSuccess)
+		e = s->jit_fn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s->jit_fn, 64, b->lds_bytes)
+		              : (hipError_t)kernel_variants[b->variant].occupancy(b->lds_bytes, &per_cu);
+	if (e != hipSuccess || cus <= 0 || per_cu <= 0)
+	{
+		(void)hipGetLastError();
+		log_msg("occupancy of %s on device %d unknown: one workgroup per block", s->jit_fn ? "the run-time build" : kernel_variants[b->variant].name, s->device);
+		resident = RESIDENT_UNKNOWN;
+		return 0;
+	}
+	resident = (uint32_t)cus * (uint32_t)per_cu;
+	log_msg("%s on device %d: %u workgroups resident (%d CUs x %d); a launch of more blocks draws them from tickets",
+	        s->jit_fn ? "the run-time build" : kernel_variants[b->variant].name, s->device, resident, cus, per_cu);
+	return resident;
+}
+
+/* Turns `k` into a ticket launch of `grid` workgroups: the heads are zeroed on the launch's stream in front of it.  The slot
+ * has one ticket buffer, so the launch first waits for the end of the last ticket launch, whichever stream that was on (no
+ * wait at all on the same stream, or before the event was ever recorded). */
+int tickets_arm(DeviceSlot* s, KernelLaunch& k, uint32_t grid)
+{
+	const hipStream_t stream = static_cast<hipStream_t>(k.stream);
+	HIP_TRY(hipStreamWaitEvent(stream, s->ev_tickets, 0), return 2);
+	HIP_TRY(hipMemsetAsync(s->d_tickets, 0, TICKET_BUFFER_BYTES, stream), return 2);
+	k.img.tickets = s->d_tickets;
+	k.grid = grid;
+	return 0;
+}
+int tickets_launched(DeviceSlot* s, const KernelLaunch& k)
+{
+	const hipStream_t stream = static_cast<hipStream_t>(k.stream);
+	HIP_TRY(hipEventRecord(s->ev_tickets, stream), return 2);
+	return 0;
 }
 
 /* The self-check of slot_adopt_jit: 48 x 48 blocks (volumes: 16 x 16 x 8) of deterministic RGBA8 content through `fn` and
@@ -240,6 +308,7 @@ int kernel_launch(const Backend* b, const DeviceSlot* s, const KernelLaunch& k)
  * classes: a build compiled with floating-point contraction differs from the generic build on one block in a hundred of
  * grey content and one in four hundred of lightly noisy ramps, and passed the 256 blocks of six classes this check once was
  * -- tests/test_jit_matrix.py keeps such builds and expects them to be turned away here.) */
+constexpr uint32_t JIT_SELF_CHECK_GRID = 288;
 bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 {
 	const uint32_t bsx = b->root.dim_x, bsy = b->root.dim_y, bsz = b->root.dim_z;
@@ -296,8 +365,12 @@ bool jit_self_check(Backend* b, DeviceSlot* s, hipFunction_t fn)
 		k.d_out = d_out;
 		ok = ok && kernel_variants[b->variant].launch(k) == 0;
 		k.d_out = d_out + nblocks * 16;
+		// (the candidate through the ticket path, 288 workgroups over the 2304 blocks: every workgroup compresses several blocks of
+		//  different classes one after the other, so a build that carries state from one block into the next is turned away too)
+		ok = ok && tickets_arm(s, k, JIT_SELF_CHECK_GRID) == 0;
 		void* args[] = { &k.d_tab, &k.img, &k.d_out, &k.first, &k.count, &k.d_prof, &k.d_set };
-		ok = ok && hipModuleLaunchKernel(fn, k.count, 1, 1, 64, 1, 1, k.lds_bytes, s->stream, args, nullptr) == hipSuccess;
+		ok = ok && hipModuleLaunchKernel(fn, k.grid, 1, 1, 64, 1, 1, k.lds_bytes, s->stream, args, nullptr) == hipSuccess;
+		ok = ok && tickets_launched(s, k) == 0;
 		ok = ok && hipMemcpyAsync(out.data(), d_out, out.size(), hipMemcpyDeviceToHost, s->stream) == hipSuccess;
 		ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
 		if (!ok) (void)hipGetLastError();
@@ -374,6 +447,8 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_adaptive) (void)hipFree(s->d_adaptive);
 	for (hipEvent_t e : s->ev_adapt) if (e) (void)hipEventDestroy(e);
 	if (s->d_prof) (void)hipFree(s->d_prof);
+	if (s->d_tickets) (void)hipFree(s->d_tickets);
+	if (s->ev_tickets) (void)hipEventDestroy(s->ev_tickets);
 	for (int i = 0; i < 2; i++) { if (s->h_in[i]) (void)hipHostFree(s->h_in[i]); if (s->h_out[i]) (void)hipHostFree(s->h_out[i]); }
 	for (hipEvent_t e : { s->ev_copy[0], s->ev_copy[1], s->ev_band, s->ev_done[0], s->ev_done[1], s->ev_done[2], s->ev_out[0], s->ev_out[1], s->ev0, s->ev1, s->ev_gen })
 		if (e) (void)hipEventDestroy(e);
@@ -518,6 +593,8 @@ DeviceSlot* slot_create(Backend* b, int device, int* status)
 	SLOT_TRY(hipEventCreate(&s->ev0), 2);
 	SLOT_TRY(hipEventCreate(&s->ev1), 2);
 	SLOT_TRY(hipEventCreate(&s->ev_gen), 2);
+	SLOT_TRY(hipEventCreateWithFlags(&s->ev_tickets, hipEventDisableTiming), 2);
+	SLOT_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_tickets), TICKET_BUFFER_BYTES), 1);
 #if defined(ASTC_PROFILE)
 	enum { PS_COUNT = 40 };
 	SLOT_TRY(hipMalloc(&s->d_prof, 2 * PS_COUNT * sizeof(unsigned long long)), 1);
@@ -868,8 +945,15 @@ static int run_chunks(const Backend* b, DeviceSlot* s, ChunkLoop& L)
 		if (L.before_launch && L.before_launch(first, n) != 0) return 2;
 		KernelLaunch k = L.k;
 		k.first = (uint32_t)first; k.count = (uint32_t)n;
+		// more blocks than the device holds workgroups: that many workgroups draw the blocks from tickets (block_tickets.h)
+		const long forced = compress_grid_from_env();
+		uint32_t grid = 0;
+		if (forced > 0) grid = (uint32_t)((size_t)forced < n ? (size_t)forced : n);
+		else if (forced < 0) { const uint32_t resident = compress_grid(b, s); if (resident && n > resident) grid = resident; }
+		if (grid && tickets_arm(s, k, grid) != 0) return 2;
 		int lrc = kernel_launch(b, s, k);
 		if (lrc != 0) { log_msg("kernel launch failed (hip error %d)", lrc); return 2; }
+		if (grid && tickets_launched(s, k) != 0) return 2;
 		L.launched = first + n;
 		if (L.after_launch)
 		{

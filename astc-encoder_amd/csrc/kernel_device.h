@@ -9,6 +9,7 @@
 #pragma once
 #include "wave_block.h"
 #include "image_set.h"
+#include "block_tickets.h"
 
 #ifndef ASTC_KERNEL_LINKAGE
 #define ASTC_KERNEL_LINKAGE
@@ -44,18 +45,46 @@ __device__ inline uint32_t xcd_block_remap_runs(uint32_t b, uint32_t n)
 	return g * group + (r % 8u) * XCD_SET_RUN + r / 8u;
 }
 
-// (the occupancy bound twice: __launch_bounds__ is a macro of the HIP headers, and the run-time compiler of ROCm 7.0 drops its
-//  second argument -- 160 VGPRs, three waves per SIMD -- where hipcc and the ROCm 7.2 run-time compiler honour it)
-ASTC_KERNEL_LINKAGE __global__ void __launch_bounds__(64, ASTC_WAVES_PER_EU) __attribute__((amdgpu_waves_per_eu(ASTC_WAVES_PER_EU)))
-ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
-                 uint8_t* __restrict__ out, uint32_t first_block, uint32_t num_blocks, unsigned long long* prof,
-                 const ImageSetTable* __restrict__ set)
+/* The kernel's arguments as they lie in its argument segment (the declaration below, member for member).  The ticket heads of
+ * the launch travel in `img` (astc_tables.h): the argument list is the same for every build, the run-time ones included. */
+struct CompressKernelArgs {
+	const uint8_t* tab;
+	ImageDesc img;
+	uint8_t* out;
+	uint32_t first_block, num_blocks;
+	unsigned long long* prof;
+	const ImageSetTable* set;
+};
+
+/* One block of a launch: `index` is its launch index -- blockIdx.x in a launch of one workgroup per block, a ticket's index
+ * (block_tickets.h) otherwise.  What a block needs of the kernel's arguments it reads from the argument segment itself (scalar
+ * loads), so no register of one block reaches the next one.  What a block leaves behind in LDS is dead when the next one starts,
+ * exactly as for the workgroup that follows another on a CU (LDS is not cleared between workgroups): load_block writes the
+ * whole BlkInfo and the texel rows, search_block resets the best encoding and the trial caches, and a constant-colour block,
+ * which skips the search, writes every Scb field its 16 bytes are made from. */
+/* ... read from the segment now: scalar loads through a pointer the optimiser cannot see through, so that what is read lives
+ * from here to its last use and is not loaded once in front of the ticket loop and carried across every search. */
+__attribute__((always_inline)) __device__ inline CompressKernelArgs compress_kernel_args()
 {
+	uintptr_t args_bits = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr());
+	asm volatile("" : "+s"(args_bits));
+	return image_set_record<CompressKernelArgs>((const __attribute__((address_space(4))) uint32_t*)args_bits);
+}
+
+__attribute__((always_inline)) __device__ inline void compress_launch_index(uint32_t index)
+{
+	WV_LANE_SCOPE;
 	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
-	uint32_t b = (set ? xcd_block_remap_runs(blockIdx.x, num_blocks) : xcd_block_remap(blockIdx.x, num_blocks)) + first_block;
+	const CompressKernelArgs a = compress_kernel_args();
+	ImageDesc img = a.img;
+	uint8_t* __restrict__ out = a.out;
+	const uint8_t* __restrict__ tab = a.tab;
+	unsigned long long* prof = a.prof;
+	const ImageSetTable* __restrict__ set = a.set;
+	uint32_t b = (set ? xcd_block_remap_runs(index, a.num_blocks) : xcd_block_remap(index, a.num_blocks)) + a.first_block;
 	// A block list (astcenc_amd_compress_block_list_device: img.list, never with a set): `b` is so far a position in the list, the
 	// XCD remap included; the block is the one named there, compressed into its own raster slot.  One scalar load through a
-	// constant pointer, as for `tab` below.  An index that is no block of the image (a stale list) ends the wavefront before it
+	// constant pointer, as for `tab` below.  An index that is no block of the image (a stale list) ends the block before it
 	// touches anything.
 	if (img.list)
 	{
@@ -145,5 +174,69 @@ ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
 	}
 	compress_block(c, out);
 }
+
+/* The XCD the wavefront runs on (0 .. 7): where a workgroup starts to draw tickets.  Placement only: any value gives the same bytes. */
+__device__ inline uint32_t home_xcd()
+{
+	uint32_t x;
+	asm("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(x));
+	return x % TICKET_HEADS;
+}
+
+// (the occupancy bound twice: __launch_bounds__ is a macro of the HIP headers, and the run-time compiler of ROCm 7.0 drops its
+//  second argument -- 160 VGPRs, three waves per SIMD -- where hipcc and the ROCm 7.2 run-time compiler honour it)
+// img.tickets null: one workgroup per block, blockIdx.x is the launch index.  Else the eight zeroed heads of block_tickets.h: the
+// grid is smaller than num_blocks and every workgroup compresses blocks until the heads are exhausted.
+// (the arguments are read by compress_launch_index and the loop below from the argument segment: CompressKernelArgs)
+ASTC_KERNEL_LINKAGE __global__ void __launch_bounds__(64, ASTC_WAVES_PER_EU) __attribute__((amdgpu_waves_per_eu(ASTC_WAVES_PER_EU)))
+ASTC_KERNEL_NAME(const uint8_t* __restrict__ tab, ImageDesc img,
+                 uint8_t* __restrict__ out, uint32_t first_block, uint32_t num_blocks, unsigned long long* prof,
+                 const ImageSetTable* __restrict__ set)
+{
+	// The ticket loop: heads home, home + 1, ... each until it is exhausted.  Lane 0 draws, with a relaxed device-scope atomic
+	// (the heads are shared by every XCD; a ticket orders nothing but itself), and the wave takes its value.  Without tickets
+	// the loop makes its one trip with blockIdx.x.  Two scalars live from one trip to the next: `home` and `dry`.
+	typedef __attribute__((address_space(1))) uint32_t* global_words;
+	const uint32_t home = img.tickets ? home_xcd() : 0u;
+	uint32_t dry = 0;
+	for (;;)
+	{
+		const CompressKernelArgs a = compress_kernel_args();
+		uint32_t index = blockIdx.x;
+		if (a.img.tickets)
+		{
+			const global_words heads = (global_words)reinterpret_cast<uintptr_t>(a.img.tickets);
+			for (;;)
+			{
+				if (dry == TICKET_HEADS) return;
+				const uint32_t x = ticket_head_after(home, dry);
+				uint32_t t = 0;
+				WV_ONE t = __hip_atomic_fetch_add(heads + ticket_head_word(x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				t = wv_uniform(t);
+				if (t < ticket_head_count(a.num_blocks, x)) { index = ticket_index(t, x); break; }
+				dry++;
+			}
+		}
+		compress_launch_index(index);
+		if (!compress_kernel_args().img.tickets) return;
+		// (the next block's first LDS writes stay behind this block's last LDS reads)
+		WV_SYNC();
+	}
+}
+
+// CompressKernelArgs against the declaration above: the members have the parameters' types in the parameters' order, nothing
+// lies between or behind them, and an argument segment lays its arguments out as a C struct lays out its members.
+template <class A, class B> struct same_type { static constexpr bool value = false; };
+template <class A> struct same_type<A, A> { static constexpr bool value = true; };
+static_assert(same_type<decltype(&ASTC_KERNEL_NAME),
+                        void (*)(decltype(CompressKernelArgs::tab), decltype(CompressKernelArgs::img), decltype(CompressKernelArgs::out),
+                                 decltype(CompressKernelArgs::first_block), decltype(CompressKernelArgs::num_blocks),
+                                 decltype(CompressKernelArgs::prof), decltype(CompressKernelArgs::set))>::value,
+              "CompressKernelArgs does not mirror the kernel's parameter list");
+static_assert(sizeof(ImageDesc) % 8 == 0 && __builtin_offsetof(CompressKernelArgs, tab) == 0 && __builtin_offsetof(CompressKernelArgs, img) == 8 &&
+              __builtin_offsetof(CompressKernelArgs, out) == 8 + sizeof(ImageDesc) && __builtin_offsetof(CompressKernelArgs, first_block) == 16 + sizeof(ImageDesc) &&
+              __builtin_offsetof(CompressKernelArgs, num_blocks) == 20 + sizeof(ImageDesc) && __builtin_offsetof(CompressKernelArgs, prof) == 24 + sizeof(ImageDesc) &&
+              __builtin_offsetof(CompressKernelArgs, set) == 32 + sizeof(ImageDesc) && sizeof(CompressKernelArgs) == 40 + sizeof(ImageDesc),
+              "CompressKernelArgs has members, padding or an order that the kernel's argument segment does not");
 
 } // namespace astcd

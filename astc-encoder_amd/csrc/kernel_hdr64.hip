@@ -6,4 +6,5 @@
 #define ASTC_KERNEL_NAME astc_compress_blocks_hdr64
 #define ASTC_PREPARE_NAME astc_kernel_prepare_hdr64
 #define ASTC_LAUNCH_NAME astc_kernel_launch_hdr64
+#define ASTC_OCCUPANCY_NAME astc_kernel_occupancy_hdr64
 #include "kernel_impl.h"

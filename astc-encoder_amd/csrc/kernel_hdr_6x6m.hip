@@ -9,4 +9,5 @@
 #define ASTC_KERNEL_NAME astc_compress_blocks_hdr_6x6m
 #define ASTC_PREPARE_NAME astc_kernel_prepare_hdr_6x6m
 #define ASTC_LAUNCH_NAME astc_kernel_launch_hdr_6x6m
+#define ASTC_OCCUPANCY_NAME astc_kernel_occupancy_hdr_6x6m
 #include "kernel_impl.h"

@@ -2,7 +2,7 @@
 // The compression kernel.  Included by kernel_ldr.hip and kernel_hdr.hip, which set
 //   ASTC_VARIANT     inline-namespace tag of this build of the wave_*.h code
 //   ASTC_ENABLE_HDR  0: LDR/sRGB profiles only (HDR endpoint coders compiled out), 1: everything
-//   ASTC_KERNEL_NAME / ASTC_PREPARE_NAME / ASTC_LAUNCH_NAME
+//   ASTC_KERNEL_NAME / ASTC_PREPARE_NAME / ASTC_LAUNCH_NAME / ASTC_OCCUPANCY_NAME
 // One 64-lane wavefront (= one workgroup) compresses one ASTC block; its working set is a
 // dynamic-LDS region laid out by make_lds_layout().
 #include "backend.h"
@@ -41,13 +41,23 @@ int ASTC_LAUNCH_NAME(const KernelLaunch& k)
 	// (occupancy experiment builds only: extra dynamic LDS per workgroup from the environment)
 	static const unsigned pad = getenv("ASTC_LDS_PAD") ? (unsigned)atoi(getenv("ASTC_LDS_PAD")) : 0u;
 	if (pad) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ASTC_KERNEL_NAME), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(k.lds_bytes + pad));
-	hipLaunchKernelGGL(ASTC_KERNEL_NAME, dim3(k.count), dim3(64), k.lds_bytes + pad, static_cast<hipStream_t>(k.stream),
+	hipLaunchKernelGGL(ASTC_KERNEL_NAME, dim3(k.img.tickets ? k.grid : k.count), dim3(64), k.lds_bytes + pad, static_cast<hipStream_t>(k.stream),
 	                   k.d_tab, k.img, k.d_out, k.first, k.count, k.d_prof, k.d_set);
 	return (int)hipGetLastError();
 #endif
-	hipLaunchKernelGGL(ASTC_KERNEL_NAME, dim3(k.count), dim3(64), k.lds_bytes, static_cast<hipStream_t>(k.stream),
+	// (k.img.tickets: the workgroups draw their blocks, block_tickets.h)
+	hipLaunchKernelGGL(ASTC_KERNEL_NAME, dim3(k.img.tickets ? k.grid : k.count), dim3(64), k.lds_bytes, static_cast<hipStream_t>(k.stream),
 	                   k.d_tab, k.img, k.d_out, k.first, k.count, k.d_prof, k.d_set);
 	return (int)hipGetLastError();
+}
+
+int ASTC_OCCUPANCY_NAME(uint32_t lds_bytes, int* workgroups_per_cu)
+{
+#if defined(ASTC_LDS_PAD_ENV)
+	// (occupancy experiment builds: the launch's LDS size, pad included, so that the grid is what such a build holds)
+	if (getenv("ASTC_LDS_PAD")) lds_bytes += (unsigned)atoi(getenv("ASTC_LDS_PAD"));
+#endif
+	return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, reinterpret_cast<const void*>(ASTC_KERNEL_NAME), 64, lds_bytes);
 }
 
 } // namespace astcd

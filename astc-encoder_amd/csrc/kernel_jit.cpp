@@ -48,6 +48,7 @@ ASTC_EMBED(astc_src_wave_batch, "wave_batch.h")
 ASTC_EMBED(astc_src_wave_partition, "wave_partition.h")
 ASTC_EMBED(astc_src_wave_pack, "wave_pack.h")
 ASTC_EMBED(astc_src_image_set, "image_set.h")
+ASTC_EMBED(astc_src_block_tickets, "block_tickets.h")
 
 extern char** environ;
 
@@ -64,7 +65,7 @@ const EmbeddedHeader kHeaders[] = {
 	{ "wave_color.h", astc_src_wave_color, astc_src_wave_color_end }, { "wave_color_hdr.h", astc_src_wave_color_hdr, astc_src_wave_color_hdr_end },
 	{ "wave_refine.h", astc_src_wave_refine, astc_src_wave_refine_end }, { "wave_batch.h", astc_src_wave_batch, astc_src_wave_batch_end },
 	{ "wave_partition.h", astc_src_wave_partition, astc_src_wave_partition_end }, { "wave_pack.h", astc_src_wave_pack, astc_src_wave_pack_end },
-	{ "image_set.h", astc_src_image_set, astc_src_image_set_end },
+	{ "image_set.h", astc_src_image_set, astc_src_image_set_end }, { "block_tickets.h", astc_src_block_tickets, astc_src_block_tickets_end },
 };
 constexpr int kHeaderCount = (int)(sizeof(kHeaders) / sizeof(kHeaders[0]));
 constexpr long JIT_MAX_SCRATCH_BYTES = 32;
@@ -546,7 +547,9 @@ JitKernel* jit_acquire(const void* layout, size_t layout_bytes, const DeviceConf
 	std::string a = arch && *arch ? arch : "gfx950";
 	a = a.substr(0, a.find(':'));
 	k->options = { "--offload-arch=" + a, "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-math-errno",
-	               "-fno-slp-vectorize", "-Wno-unused-function" };
+	               "-fno-slp-vectorize", "-Wno-unused-function",
+	               // (as the Makefile's SINK: the loop invariants of the search stages are not carried across the ticket loop)
+	               "-mllvm", "-sink-insts-to-avoid-spills" };
 	// (ASTCENC_AMD_JIT_OPTIONS: further compiler options, space separated -- a debugging aid: the kernel of a context rebuilt
 	//  with another optimisation level or a -D switch of the source without rebuilding the library; part of the cache key)
 	if (const char* more = getenv("ASTCENC_AMD_JIT_OPTIONS"))

@@ -5,4 +5,5 @@
 #define ASTC_KERNEL_NAME astc_compress_blocks_ldr
 #define ASTC_PREPARE_NAME astc_kernel_prepare_ldr
 #define ASTC_LAUNCH_NAME astc_kernel_launch_ldr
+#define ASTC_OCCUPANCY_NAME astc_kernel_occupancy_ldr
 #include "kernel_impl.h"

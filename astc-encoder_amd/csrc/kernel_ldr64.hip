@@ -7,4 +7,5 @@
 #define ASTC_KERNEL_NAME astc_compress_blocks_ldr64
 #define ASTC_PREPARE_NAME astc_kernel_prepare_ldr64
 #define ASTC_LAUNCH_NAME astc_kernel_launch_ldr64
+#define ASTC_OCCUPANCY_NAME astc_kernel_occupancy_ldr64
 #include "kernel_impl.h"

@@ -9,4 +9,5 @@
 #define ASTC_KERNEL_NAME astc_compress_blocks_ldr_8x8t
 #define ASTC_PREPARE_NAME astc_kernel_prepare_ldr_8x8t
 #define ASTC_LAUNCH_NAME astc_kernel_launch_ldr_8x8t
+#define ASTC_OCCUPANCY_NAME astc_kernel_occupancy_ldr_8x8t
 #include "kernel_impl.h"

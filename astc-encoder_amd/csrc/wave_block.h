@@ -1296,6 +1296,7 @@ __attribute__((always_inline)) WV_FN void search_block(const Ctx& c)
  * register pair across the whole search). */
 WV_FN void compress_block(const Ctx& c, uint8_t* out)
 {
+	WV_LANE_SCOPE;
 	bool constant_color;
 	{
 		const BlkInfo& blk = c.blk();
@@ -1312,6 +1313,9 @@ WV_FN void compress_block(const Ctx& c, uint8_t* out)
 		const Ctx ce = ctx_make();
 		Scb& scb = ce.scb();
 		const BlkInfo& blk = ce.blk();
+		// (asked again rather than kept in a register across the whole search)
+		constant_color = blk.data_min[0] == blk.data_max[0] && blk.data_min[1] == blk.data_max[1] &&
+		                 blk.data_min[2] == blk.data_max[2] && blk.data_min[3] == blk.data_max[3];
 		if (constant_color)
 		{
 			// constant colour -> void extent (ref: :1216-1245)

@@ -62,6 +62,7 @@ WV_FN int lns_to_sf16(int p)
 /* Load block (bx, by, bz) of the image into LDS and compute the block statistics. */
 WV_FN void load_block(const Ctx& c, const ImageDesc& img, unsigned int bx, unsigned int by, unsigned int bz)
 {
+	WV_LANE_SCOPE;
 	const int T = c.T;
 	const int dim_x = c.root->dim_x;
 	const unsigned int plane_texels = (unsigned)dim_x * (unsigned)c.root->dim_y;
@@ -197,6 +198,7 @@ WV_FN void load_block(const Ctx& c, const ImageDesc& img, unsigned int bx, unsig
  * reach of non-transparent content?  If not the block is encoded as constant zero without being read. */
 WV_FN bool block_has_visible_alpha(const Ctx& c, const ImageDesc& img, unsigned int bx, unsigned int by)
 {
+	WV_LANE_SCOPE;
 	const int dim_x = c.root->dim_x, dim_y = c.root->dim_y;
 	const unsigned int r = img.a_scale_radius;
 	const float footprint = (float)((size_t)(dim_x + 2 * (r - 1)) * (size_t)(dim_y + 2 * (r - 1)));
@@ -216,6 +218,7 @@ WV_FN bool block_has_visible_alpha(const Ctx& c, const ImageDesc& img, unsigned 
  * (ref: astcenc_entry.cpp:1027-1034). */
 WV_FN void load_transparent_block(const Ctx& c)
 {
+	WV_LANE_SCOPE;
 	BlkInfo& blk = c.blk();
 	WV_ONE
 	{

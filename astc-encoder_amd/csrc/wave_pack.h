@@ -59,6 +59,7 @@ WV_FN void bits_or(uint32_t* words, uint32_t value, uint32_t count, uint32_t off
  * sym: the `count` symbols in LDS; words: the destination bit string; base: its first bit. */
 WV_FN void encode_ise_lanes(const Ctx& c, int quant, int count, const uint8_t* sym, uint32_t* words, uint32_t base)
 {
+	WV_LANE_SCOPE;
 	const Btq b = btq_of(quant);
 	const uint32_t bits = b.bits, low_mask = (1u << bits) - 1u;
 	const uint8_t* trit_tab = c.table(c.root->off_integer_of_trits);
@@ -112,6 +113,7 @@ WV_FN uint32_t bit_reverse32(uint32_t v)
  * behind the header, the header fields from lane 0. */
 WV_FN void symbolic_to_physical(const Ctx& c, const Scb& scb, uint8_t* pcb_out)
 {
+	WV_LANE_SCOPE;
 	// scratch in LDS (the search regions are idle by now)
 	uint32_t* block = reinterpret_cast<uint32_t*>(c.lds + c.L->uni);            // [4] + 1 word of slack
 	uint32_t* stream = block + 8;                                                // [4] + 1: the weight bit stream

@@ -4,14 +4,16 @@ SGPR spills (v_writelane / v_readlane), and the kernel descriptor's private segm
 
 Compiles csrc/kernel_<which>.hip to gfx950 assembly with the product's flags and reads the assembler's own function /
 kernel info comments and metadata.  usage: kernel_stats.py [ldr|hdr|ldr64|hdr64] [--json out.json]
-(ldr64 / hdr64: the builds for footprints of at most 64 texels, i.e. what BASELINE configs 2-4 run)"""
+(ldr64 / hdr64: the builds for footprints of at most 64 texels, i.e. what BASELINE configs 2-4 run)
+KS_SINK in the environment replaces the Makefile's SINK flags (empty: a tree from before the ticket loop); KS_EXTRA goes in front."""
 import json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "astc-encoder_amd")
 which = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else "ldr"
 out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
 FLAGS = os.environ.get("KS_EXTRA", "") + " --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-math-errno -fno-slp-vectorize " \
-        "-fvisibility=hidden -DASTCENC_DYNAMIC_LIBRARY=1 -Icsrc -Wno-unused-function --cuda-device-only -S"
+        "-fvisibility=hidden -DASTCENC_DYNAMIC_LIBRARY=1 -Icsrc -Wno-unused-function --cuda-device-only -S " + \
+        os.environ.get("KS_SINK", "-mllvm -sink-insts-to-avoid-spills")
 with tempfile.TemporaryDirectory() as tmp:
     asm = os.path.join(tmp, "k.s")
     subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS.split() + ["-o", asm, "csrc/kernel_%s.hip" % which], cwd=PKG, check=True,

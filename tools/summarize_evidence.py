@@ -10,7 +10,10 @@ from collections import defaultdict
 d, configs = sys.argv[1], sys.argv[2:]
 out = {"configs": {}, "method": "rocprofv3 --pmc over `bench.py --config <c> --steps 1 --warmup 0` (one launch of the compression kernel at the "
                                "config's full size); FETCH_SIZE and WRITE_SIZE in separate passes, KiB -> bytes, FETCH_SIZE doubled "
-                               "(gfx950 counts 128 B requests as 64 B); per block = per wavefront (one wave per block)"}
+                               "(gfx950 counts 128 B requests as 64 B); per block = per wavefront where the launch is one wave per block, else "
+                               "(a ticket launch: `waves` wavefronts draw the blocks) per block of the config's image"}
+# blocks of the BASELINE configs' images (bench.py CONFIGS): a ticket launch has fewer wavefronts than blocks
+BLOCKS = {"c2": 1366 * 1366, "c3": 1024 * 1024, "c4": 683 * 683}
 for c in configs:
     tot, n = defaultdict(float), defaultdict(int)
     kernel = None
@@ -29,6 +32,9 @@ for c in configs:
         e["write_bytes_per_launch"] = per("WRITE_SIZE") * 1024.0
         e["hbm_bytes_per_launch"] = e["read_bytes_per_launch"] + e["write_bytes_per_launch"]
     waves = per("SQ_WAVES")
+    if waves and waves < BLOCKS.get(c, 0):
+        e["waves"] = waves
+        waves = float(BLOCKS[c])
     if waves:
         e["blocks"] = waves
         for key, counter in (("valu_insts_per_block", "SQ_INSTS_VALU"), ("salu_insts_per_block", "SQ_INSTS_SALU"), ("lds_insts_per_block", "SQ_INSTS_LDS"),
