@@ -35,13 +35,12 @@ static bool set_fits_32_bits(const std::vector<size_t>& blocks)
 	return true;
 }
 
-/* Checks every entry of a compression set and fills its job; the generation of a mip chain (`generate`, may be null) is queued
- * ahead of the set's launches on the same stream.  Nothing is launched unless every check passes. */
-static astcenc_error compress_set(astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
-                                  void* hip_stream, float* kernel_ms, const MipChainJob* generate)
+/* Checks every entry of a compression set and fills its job (entry_internal.h). */
+astcenc_error astcd::check_compress_set(astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                        std::vector<CompressJob>& jobs, size_t& total)
 {
 	const bool alpha_scale = ctx->config.a_scale_radius != 0 && ctx->config.block_z <= 1;
-	std::vector<CompressJob> jobs(entry_count);
+	jobs.resize(entry_count);
 	std::vector<size_t> blocks(entry_count);
 	for (unsigned int e = 0; e < entry_count; e++)
 	{
@@ -70,6 +69,20 @@ static astcenc_error compress_set(astcenc_context* ctx, const astcenc_amd_image_
 		backend_log("image set of %u entries: more than 2^32 - 1 blocks", entry_count);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
+	total = 0;
+	for (size_t n : blocks) total += n;
+	return ASTCENC_SUCCESS;
+}
+
+/* Checks every entry of a compression set and launches it; the generation of a mip chain (`generate`, may be null) is queued
+ * ahead of the set's launches on the same stream.  Nothing is launched unless every check passes. */
+static astcenc_error compress_set(astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                  void* hip_stream, float* kernel_ms, const MipChainJob* generate)
+{
+	std::vector<CompressJob> jobs;
+	size_t total;
+	const astcenc_error status = check_compress_set(ctx, entries, entry_count, jobs, total);
+	if (status != ASTCENC_SUCCESS) return status;
 
 	// cancel: the rules of astcenc_amd_compress_volume_device (a thread_count == 1 context starts clean, a multi-thread
 	// context's cancel is sticky until astcenc_compress_reset)

@@ -115,6 +115,11 @@ struct CompressSetJob {
 	const std::atomic<int>* cancel_flag;
 	void (*progress)(float);
 	const struct MipChainJob* generate;   // non-null: generate this mip chain first, on the same stream (the entries are its levels)
+	// A block list (astcenc_amd_compress_block_list_set_device; device_list null: every block of the set): the list_count global
+	// block indices at device_list -- the blocks of all entries counted back to back -- are compressed into their own slots of
+	// their entries' outputs, nothing else is written.
+	const uint32_t* device_list;
+	uint32_t list_count;
 };
 
 /* Levels 1 .. level_count - 1 of a device image (astcenc_amd_generate_mip_chain_device and its _volume_ form, mip_filter.h):
@@ -228,6 +233,33 @@ int backend_select_blocks(Backend* b, const SelectJob& job);
  * output and the records (null: the library's own) must live on that device (else 3). */
 int backend_adaptive_reserve(Backend* b, const void* device_image, const void* device_out, const void* device_block_errors, size_t blocks);
 int backend_adaptive_refine(Backend* b, const AdaptiveJob& job);
+/* The same over an image set, with a block budget (block_budget.h).  backend_select_blocks_set: runs on the device that owns the
+ * records; *candidates may be null.  backend_adaptive_set_reserve / _refine: the set forms of the two calls above; the refine job's
+ * strong pass is a CompressSetJob whose entries' device_out hold the base streams. */
+struct BudgetSetEntry;
+struct SelectSetJob {
+	const double* device_block_errors;   // four doubles per block of the set
+	const BudgetSetEntry* entries;
+	uint32_t count;
+	uint32_t blocks;                     // of all entries, as the entry point counted them
+	double weight[4], max_mse;
+	uint32_t max_blocks;
+	uint32_t* device_list;
+	void* stream;
+	uint32_t* candidates; uint32_t* selected;
+};
+struct AdaptiveSetJob {
+	CompressSetJob strong;
+	const QualityEntryJob* score;        // per entry: how its stream is scored (decode.device_blocks = the entry's output)
+	double weight[4], max_mse;
+	uint32_t max_blocks;
+	double* device_block_errors;         // null, or the caller's records
+	uint32_t* candidates; uint32_t* selected; uint32_t* replaced;
+	float* kernel_ms_strong; float* kernel_ms_other;   // both null or both set
+};
+int backend_select_blocks_set(Backend* b, const SelectSetJob& job);
+int backend_adaptive_set_reserve(Backend* b, const CompressSetJob& set, const void* device_block_errors, size_t blocks);
+int backend_adaptive_set_refine(Backend* b, const AdaptiveSetJob& job);
 int backend_generate_mips(Backend* b, const MipChainJob& job);
 int backend_resize(Backend* b, const ResizeJob& job);
 /* A line for the diagnostics callback (astcenc_amd_set_log_callback), printf-style. */
@@ -367,6 +399,48 @@ struct MergeLaunch {
 	void* stream;
 };
 int astc_merge_launch(const MergeLaunch& m);
+
+/* Block selection over an image set with a block budget, and the merge over a set (kernel_select_set.hip, block_budget.h).
+ * astc_budget_table_build writes the set's table (astc_budget_table_bytes(count) bytes: ImageSetTable, first[], one BudgetEntry per
+ * entry) on the host.  astc_budget_select_launch queues the selection from the table's device copy: d_list[0 .. n) receives the
+ * ascending global indices of the selected blocks; d_keys: 8 bytes per block; d_counts: astc_budget_count_words(blocks) words;
+ * d_fixed: astc_budget_fixed_bytes() bytes (the state and the histograms), in which astc_budget_counts() points at two words,
+ * the candidate count and n.  astc_merge_set_launch: astc_merge_launch over the set, d_strong and both record arrays indexed by
+ * the global block, the bytes stored into the entries' own buffers (the table's `out`); the list's length is read from d_fixed. */
+struct BudgetSetEntry {
+	uint32_t dim_x, dim_y, dim_z;
+	uint8_t* device_out;             // the merge only
+};
+struct BudgetSelectLaunch {
+	const double* d_errors;
+	const uint8_t* d_table;
+	uint32_t block_x, block_y, block_z, blocks;
+	double weight[4], max_mse;
+	uint32_t max_blocks;             // 0xFFFFFFFF: no budget
+	unsigned long long* d_keys;
+	uint32_t* d_counts;
+	uint8_t* d_fixed;
+	uint32_t* d_list;
+	void* stream;
+};
+size_t astc_budget_table_bytes(uint32_t count);
+void astc_budget_table_build(void* out, const BudgetSetEntry* entries, uint32_t count, uint32_t block_x, uint32_t block_y, uint32_t block_z);
+size_t astc_budget_count_words(size_t blocks);
+size_t astc_budget_fixed_bytes();
+const uint32_t* astc_budget_counts(const uint8_t* d_fixed);
+int astc_budget_select_launch(const BudgetSelectLaunch& s);
+struct MergeSetLaunch {
+	const uint32_t* d_list;
+	const uint8_t* d_fixed;
+	uint32_t max_count;              // the grid covers this many list positions (the host's copy of the list's length)
+	const double* d_strong_errors; double* d_base_errors;
+	const uint8_t* d_strong;
+	const uint8_t* d_table;
+	double weight[4];
+	uint32_t* d_replaced;
+	void* stream;
+};
+int astc_merge_set_launch(const MergeSetLaunch& m);
 
 /* Mip chain generation (kernel_mips.hip): queues the launches of `job` on `stream` (job.stream unused), level i made from level
  * i - 1.  d_srgb: the tables of astc_mip_srgb_tables_build in device memory (astc_mip_srgb_table_bytes()), used for RGBA8 when

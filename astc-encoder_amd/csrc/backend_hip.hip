@@ -76,6 +76,11 @@ struct DeviceSlot {
 	double* d_quality_sums = nullptr; size_t quality_sums_cap = 0;   // ... and its totals, per entry of the set
 	uint32_t* d_select = nullptr; size_t select_cap = 0;   // per-tile counts of the selection kernels, then the merge's counter (kernel_select.hip)
 	uint8_t* d_adaptive = nullptr; size_t adaptive_cap = 0;   // the adaptive driver's stream copy, records and list (backend_adaptive_refine)
+	// selection with a block budget (kernel_select_set.hip): the keys, the state and histograms, the set's table and its host copy
+	unsigned long long* d_keys = nullptr; size_t keys_cap = 0;
+	uint8_t* d_budget_fixed = nullptr; size_t budget_fixed_cap = 0;
+	uint8_t* d_budget_tab = nullptr; size_t budget_tab_cap = 0;
+	std::vector<uint8_t> h_budget_tab;
 	hipEvent_t ev_adapt[2] = {};  // around the adaptive driver's work on the strong context (created on first use)
 	std::mutex busy;              // one call at a time per slot: the staging buffers and events are shared state
 	std::vector<int> local_cpus;  // host CPUs on the device's NUMA node (Linux sysfs); empty: unknown, no binding
@@ -445,6 +450,9 @@ void slot_destroy(DeviceSlot* s)
 	if (s->d_quality_sums) (void)hipFree(s->d_quality_sums);
 	if (s->d_select) (void)hipFree(s->d_select);
 	if (s->d_adaptive) (void)hipFree(s->d_adaptive);
+	if (s->d_keys) (void)hipFree(s->d_keys);
+	if (s->d_budget_fixed) (void)hipFree(s->d_budget_fixed);
+	if (s->d_budget_tab) (void)hipFree(s->d_budget_tab);
 	for (hipEvent_t e : s->ev_adapt) if (e) (void)hipEventDestroy(e);
 	if (s->d_prof) (void)hipFree(s->d_prof);
 	if (s->d_tickets) (void)hipFree(s->d_tickets);
@@ -1504,7 +1512,9 @@ static int compress_set_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, c
 	ImageSetTable* t = reinterpret_cast<ImageSetTable*>(s->h_set.data());
 	t->count = count;
 	t->total = (uint32_t)nblocks;
-	jit_count_blocks(b, s, nblocks);
+	// (a block list: the launches cover the positions of the list, everything else is the whole set's)
+	const size_t launch_blocks = job.device_list ? (size_t)job.list_count : nblocks;
+	jit_count_blocks(b, s, launch_blocks);
 
 	if (alpha_floats)
 	{
@@ -1525,11 +1535,18 @@ static int compress_set_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, c
 	ChunkLoop L;
 	L.k.d_tab = s->d_tab; L.k.lds_bytes = b->lds_bytes; L.k.img = rec[0].img; L.k.d_out = rec[0].out;
 	L.k.stream = stream; L.k.d_prof = s->d_prof; L.k.d_set = reinterpret_cast<const ImageSetTable*>(s->d_set);
+	if (job.device_list)
+	{
+		// the by-value record of a set launch carries the list, and as its block count the set's total: the kernel head bounds a
+		// listed index by it before the index goes through the set's table (kernel_device.h)
+		L.k.img.list = job.device_list;
+		L.k.img.blocks_x = (uint32_t)nblocks; L.k.img.blocks_y = 1; L.k.img.blocks_z = 1;
+	}
 #if defined(ASTC_TRACE)
 	L.k.d_prof = nullptr;      // (the search trace is a single-image debug aid: compress_on_slot_locked sizes its buffer)
 #endif
 	L.chunked = progress && progress->callback;
-	L.nblocks = nblocks; L.chunk = L.chunked ? (size_t)1 << 18 : nblocks;
+	L.nblocks = launch_blocks; L.chunk = L.chunked ? (size_t)1 << 18 : launch_blocks;
 	L.timed = job.kernel_ms != nullptr;
 	L.cancel_flag = job.cancel_flag; L.progress = progress;
 	if (run_chunks(b, s, L) != 0) return 2;
@@ -1544,9 +1561,11 @@ int backend_compress_set(Backend* b, const CompressSetJob& job)
 	if (job.generate && job.generate->device_image != job.entries[0].device_data) return 3;
 	std::vector<const void*> ptrs;
 	for (uint32_t e = 0; e < job.count; e++) { ptrs.push_back(job.entries[e].device_data); ptrs.push_back(job.entries[e].device_out); }
+	ptrs.push_back(job.device_list); ptrs.push_back(nullptr);
 	Progress progress;
 	progress.done = 0; progress.callback = job.progress; progress.total = 0;
 	for (uint32_t e = 0; e < job.count; e++) progress.total += block_grid(b->root, job.entries[e]).count();
+	if (job.device_list) progress.total = job.list_count;
 	return run_on_owner(b, job.entries[0].device_data, ptrs.data(), ptrs.size(), job.stream, [&](DeviceSlot* s, hipStream_t stream) { return compress_set_on_slot(b, s, stream, job, &progress); });
 }
 
@@ -1745,6 +1764,185 @@ int backend_adaptive_refine(Backend* b, const AdaptiveJob& job)
 			for (int i = 0; i < 4; i++) m.weight[i] = job.weight[i];
 			m.d_replaced = d_replaced; m.stream = stream;
 			const int mrc = astc_merge_launch(m);
+			if (mrc != 0) { log_msg("block merge kernel launch failed (hip error %d)", mrc); return 2; }
+			HIP_TRY(hipMemcpyAsync(job.replaced, d_replaced, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), return 2);
+		}
+		if (timed) HIP_TRY(hipEventRecord(s->ev_adapt[1], stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		if (timed)
+		{
+			float all_ms = 0.0f;
+			HIP_TRY(hipEventElapsedTime(&all_ms, s->ev_adapt[0], s->ev_adapt[1]), return 2);
+			*job.kernel_ms_strong = strong_ms;
+			*job.kernel_ms_other = all_ms > strong_ms ? all_ms - strong_ms : 0.0f;
+		}
+		return 0;
+	});
+}
+
+/* The selection launches of `job` over its set on slot `s` (d_list: where the indices go).  The candidate count and the list's
+ * length stay on the device, at astc_budget_counts(s->d_budget_fixed); the table stays at s->d_budget_tab for the merge. */
+static int select_set_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const SelectSetJob& job, uint32_t* d_list)
+{
+	const size_t blocks = job.blocks;
+	const size_t table_bytes = astc_budget_table_bytes(job.count);
+	// (one word past the counts: the merge kernel's counter)
+	if (grow(s->d_select, s->select_cap, (astc_budget_count_words(blocks) + 1) * sizeof(uint32_t)) != 0 ||
+	    grow(s->d_keys, s->keys_cap, blocks * sizeof(unsigned long long)) != 0 ||
+	    grow(s->d_budget_fixed, s->budget_fixed_cap, astc_budget_fixed_bytes()) != 0 ||
+	    grow(s->d_budget_tab, s->budget_tab_cap, table_bytes) != 0) return 1;
+	s->h_budget_tab.assign(table_bytes, 0);
+	astc_budget_table_build(s->h_budget_tab.data(), job.entries, job.count, b->root.dim_x, b->root.dim_y, b->root.dim_z);
+	HIP_TRY(hipMemcpyAsync(s->d_budget_tab, s->h_budget_tab.data(), table_bytes, hipMemcpyHostToDevice, stream), return 2);
+	BudgetSelectLaunch l;
+	l.d_errors = job.device_block_errors; l.d_table = s->d_budget_tab;
+	l.block_x = b->root.dim_x; l.block_y = b->root.dim_y; l.block_z = b->root.dim_z; l.blocks = job.blocks;
+	for (int i = 0; i < 4; i++) l.weight[i] = job.weight[i];
+	l.max_mse = job.max_mse; l.max_blocks = job.max_blocks;
+	l.d_keys = s->d_keys; l.d_counts = s->d_select; l.d_fixed = s->d_budget_fixed; l.d_list = d_list; l.stream = stream;
+	const int lrc = astc_budget_select_launch(l);
+	if (lrc != 0) { log_msg("block selection kernel launch failed (hip error %d)", lrc); return 2; }
+	return 0;
+}
+
+int backend_select_blocks_set(Backend* b, const SelectSetJob& job)
+{
+	const void* ptrs[1] = { job.device_list };
+	return run_on_owner(b, job.device_block_errors, ptrs, 1, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		const int rc = select_set_on_slot(b, s, stream, job, job.device_list);
+		if (rc != 0) return rc;
+		uint32_t counts[2] = { 0, 0 };
+		HIP_TRY(hipMemcpyAsync(counts, astc_budget_counts(s->d_budget_fixed), sizeof(counts), hipMemcpyDeviceToHost, stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		if (job.candidates) *job.candidates = counts[0];
+		*job.selected = counts[1];
+		return 0;
+	});
+}
+
+/* astcenc_amd_compress_images_adaptive_device after its base pass: backend_adaptive_refine over a set.  The strong stream S and the
+ * records E0, E1 are laid out by the global block index, entry after entry; the strong pass is a block-list launch of the set
+ * whose entries write into their parts of S, and the merge stores into the entries' own buffers through the selection's table.
+ * Scratch: S, E1, E0 unless the caller's, the list, the keys: 16 + 32 (+ 32) + 4 + 8 bytes per block, sized before anything is
+ * launched. */
+static size_t set_blocks(const Backend* b, const CompressSetJob& set, std::vector<size_t>* first)
+{
+	size_t total = 0;
+	for (uint32_t e = 0; e < set.count; e++)
+	{
+		if (first) first->push_back(total);
+		total += block_grid(b->root, set.entries[e]).count();
+	}
+	return total;
+}
+
+static std::vector<const void*> set_pointers(const CompressSetJob& set, const void* device_block_errors)
+{
+	std::vector<const void*> ptrs;
+	for (uint32_t e = 0; e < set.count; e++) { ptrs.push_back(set.entries[e].device_data); ptrs.push_back(set.entries[e].device_out); }
+	ptrs.push_back(device_block_errors); ptrs.push_back(nullptr);
+	return ptrs;
+}
+
+int backend_adaptive_set_reserve(Backend* b, const CompressSetJob& set, const void* device_block_errors, size_t blocks)
+{
+	const std::vector<const void*> ptrs = set_pointers(set, device_block_errors);
+	const bool own_records = device_block_errors == nullptr;
+	return run_on_owner(b, set.entries[0].device_data, ptrs.data(), ptrs.size(), nullptr, [&](DeviceSlot* s, hipStream_t)
+	{
+		if (grow(s->d_adaptive, s->adaptive_cap, adaptive_scratch_bytes(blocks, own_records)) != 0 ||
+		    grow(s->d_select, s->select_cap, (astc_budget_count_words(blocks) + 1) * sizeof(uint32_t)) != 0 ||
+		    grow(s->d_keys, s->keys_cap, blocks * sizeof(unsigned long long)) != 0 ||
+		    grow(s->d_budget_fixed, s->budget_fixed_cap, astc_budget_fixed_bytes()) != 0 ||
+		    grow(s->d_budget_tab, s->budget_tab_cap, astc_budget_table_bytes(set.count)) != 0 ||
+		    grow(s->d_quality, s->quality_cap, astc_quality_scratch_doubles() * sizeof(double)) != 0 ||
+		    grow(s->d_quality_sums, s->quality_sums_cap, (size_t)set.count * METRIC_SUMS_HOST * sizeof(double)) != 0) return 1;
+		return 0;
+	});
+}
+
+int backend_adaptive_set_refine(Backend* b, const AdaptiveSetJob& job)
+{
+	const CompressSetJob& cs = job.strong;
+	const std::vector<const void*> ptrs = set_pointers(cs, job.device_block_errors);
+	return run_on_owner(b, cs.entries[0].device_data, ptrs.data(), ptrs.size(), cs.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		std::vector<size_t> first;
+		const size_t blocks = set_blocks(b, cs, &first);
+		const size_t at_e1 = blocks * 16, at_e0 = at_e1 + blocks * 32, at_list = at_e0 + (job.device_block_errors ? 0 : blocks * 32);
+		if (grow(s->d_adaptive, s->adaptive_cap, adaptive_scratch_bytes(blocks, !job.device_block_errors)) != 0) return 1;
+		uint8_t* d_stream = s->d_adaptive;
+		double* d_e1 = reinterpret_cast<double*>(s->d_adaptive + at_e1);
+		double* d_e0 = job.device_block_errors ? job.device_block_errors : reinterpret_cast<double*>(s->d_adaptive + at_e0);
+		uint32_t* d_list = reinterpret_cast<uint32_t*>(s->d_adaptive + at_list);
+		const bool timed = job.kernel_ms_other != nullptr;
+		if (timed)
+		{
+			for (hipEvent_t& e : s->ev_adapt) if (!e) HIP_TRY(hipEventCreate(&e), return 2);
+			HIP_TRY(hipEventRecord(s->ev_adapt[0], stream), return 2);
+		}
+		std::vector<double> sums((size_t)cs.count * METRIC_SUMS_HOST);
+		std::vector<QualityEntryJob> q(job.score, job.score + cs.count);
+		for (uint32_t e = 0; e < cs.count; e++) q[e].device_block_errors = d_e0 + first[e] * 4;
+		QualitySetJob qs;
+		memset(&qs, 0, sizeof(qs));
+		qs.entries = q.data(); qs.count = cs.count; qs.stream = stream; qs.sums = sums.data();
+		int rc = compare_blocks_on_slot(b, s, stream, qs);
+		if (rc != 0) return rc;
+
+		std::vector<BudgetSetEntry> dims(cs.count);
+		for (uint32_t e = 0; e < cs.count; e++)
+			dims[e] = { cs.entries[e].dim_x, cs.entries[e].dim_y, cs.entries[e].dim_z ? cs.entries[e].dim_z : 1u, cs.entries[e].device_out };
+		SelectSetJob sj;
+		memset(&sj, 0, sizeof(sj));
+		sj.device_block_errors = d_e0;
+		sj.entries = dims.data(); sj.count = cs.count; sj.blocks = (uint32_t)blocks;
+		for (int i = 0; i < 4; i++) sj.weight[i] = job.weight[i];
+		sj.max_mse = job.max_mse; sj.max_blocks = job.max_blocks;
+		rc = select_set_on_slot(b, s, stream, sj, d_list);
+		if (rc != 0) return rc;
+		uint32_t counts[2] = { 0, 0 };
+		HIP_TRY(hipMemcpyAsync(counts, astc_budget_counts(s->d_budget_fixed), sizeof(counts), hipMemcpyDeviceToHost, stream), return 2);
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		*job.candidates = counts[0];
+		*job.selected = counts[1];
+		*job.replaced = 0;
+		const uint32_t count = counts[1];
+		float strong_ms = 0.0f;
+		if (count != 0)
+		{
+			std::vector<CompressJob> entries(cs.entries, cs.entries + cs.count);
+			for (uint32_t e = 0; e < cs.count; e++)
+			{
+				const size_t bytes = (e + 1 < cs.count ? first[e + 1] - first[e] : blocks - first[e]) * 16;
+				HIP_TRY(hipMemcpyAsync(d_stream + first[e] * 16, cs.entries[e].device_out, bytes, hipMemcpyDeviceToDevice, stream), return 2);
+				entries[e].device_out = d_stream + first[e] * 16;
+			}
+			CompressSetJob lj = cs;
+			lj.entries = entries.data();
+			lj.device_list = d_list; lj.list_count = count;
+			lj.kernel_ms = timed ? &strong_ms : nullptr;
+			lj.generate = nullptr;
+			Progress progress;
+			progress.done = 0; progress.callback = lj.progress; progress.total = count;
+			rc = compress_set_on_slot(b, s, stream, lj, &progress);
+			if (rc != 0) return rc;
+			for (uint32_t e = 0; e < cs.count; e++)
+			{
+				q[e].decode.device_blocks = d_stream + first[e] * 16;
+				q[e].device_block_errors = d_e1 + first[e] * 4;
+			}
+			rc = compare_blocks_on_slot(b, s, stream, qs);
+			if (rc != 0) return rc;
+			uint32_t* d_replaced = s->d_select + astc_budget_count_words(blocks);
+			MergeSetLaunch m;
+			m.d_list = d_list; m.d_fixed = s->d_budget_fixed; m.max_count = count;
+			m.d_strong_errors = d_e1; m.d_base_errors = d_e0;
+			m.d_strong = d_stream; m.d_table = s->d_budget_tab;
+			for (int i = 0; i < 4; i++) m.weight[i] = job.weight[i];
+			m.d_replaced = d_replaced; m.stream = stream;
+			const int mrc = astc_merge_set_launch(m);
 			if (mrc != 0) { log_msg("block merge kernel launch failed (hip error %d)", mrc); return 2; }
 			HIP_TRY(hipMemcpyAsync(job.replaced, d_replaced, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), return 2);
 		}

@@ -36,6 +36,8 @@ struct astcenc_context {
 	int per_slice_fast_load;          // ASTCENC_AMD_OPT_PER_SLICE_FAST_LOAD: -1 not set (each entry point's default), 0, 1
 };
 
+struct astcenc_amd_image_set_entry;   // (include/astcenc_amd.h)
+
 namespace astcd {
 
 inline bool swz_ok(astcenc_swz s, bool allow_z)
@@ -133,5 +135,11 @@ inline CompressJob device_compress_job(astcenc_context* ctx, const void* device_
 	job.progress = ctx->config.progress_callback;
 	return job;
 }
+
+/* The checks of astcenc_amd_compress_images_device (astcenc_set.cpp) for a set of entry_count >= 1 entries: every entry as
+ * astcenc_amd_compress_volume_device checks its image (the log callback names a bad one), and at most 2^32 - 1 blocks in all.
+ * jobs[e]: the device-resident fields of entry e's job; total: the blocks of the set. */
+astcenc_error check_compress_set(astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                 std::vector<CompressJob>& jobs, size_t& total);
 
 } // namespace astcd

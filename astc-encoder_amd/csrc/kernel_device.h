@@ -82,10 +82,12 @@ __attribute__((always_inline)) __device__ inline void compress_launch_index(uint
 	unsigned long long* prof = a.prof;
 	const ImageSetTable* __restrict__ set = a.set;
 	uint32_t b = (set ? xcd_block_remap_runs(index, a.num_blocks) : xcd_block_remap(index, a.num_blocks)) + a.first_block;
-	// A block list (astcenc_amd_compress_block_list_device: img.list, never with a set): `b` is so far a position in the list, the
-	// XCD remap included; the block is the one named there, compressed into its own raster slot.  One scalar load through a
-	// constant pointer, as for `tab` below.  An index that is no block of the image (a stale list) ends the block before it
-	// touches anything.
+	// A block list (astcenc_amd_compress_block_list_device: img.list): `b` is so far a position in the list, the XCD remap
+	// included; the block is the one named there, compressed into its own raster slot.  One scalar load through a constant
+	// pointer, as for `tab` below.  An index that is no block of the image (a stale list) ends the block before it touches
+	// anything.  With a set (astcenc_amd_compress_block_list_set_device) the list names global indices, which then go through the
+	// set's lookup below; the by-value record, otherwise unused in a set launch, carries the list and, as blocks_x * 1 * 1, the set's
+	// total, so the bound is the same line.
 	if (img.list)
 	{
 		b = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(reinterpret_cast<uintptr_t>(img.list))[b];

@@ -101,7 +101,9 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_resize_image_device", "astcenc_amd_resize_dims", "astcenc_amd_compare_blocks_device",
                "astcenc_amd_compare_blocks_hdr_device", "astcenc_amd_compare_image_set_device",
                "astcenc_amd_compress_block_list_device", "astcenc_amd_select_blocks_device",
-               "astcenc_amd_compress_image_adaptive_device"]
+               "astcenc_amd_compress_image_adaptive_device", "astcenc_amd_select_blocks_set_device",
+               "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device"]
+NO_BLOCK_BUDGET = 0xFFFFFFFF
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
 MIP_ARRAY, MIP_VOLUME = 0, 1
@@ -212,6 +214,12 @@ class AdaptiveStats(C.Structure):
                 ("kernel_ms_base", C.c_float), ("kernel_ms_strong", C.c_float), ("kernel_ms_other", C.c_float)]
 
 
+class AdaptiveSetStats(C.Structure):
+    """struct astcenc_amd_adaptive_set_stats."""
+    _fields_ = [("blocks", C.c_uint), ("candidates", C.c_uint), ("selected", C.c_uint), ("replaced", C.c_uint),
+                ("kernel_ms_base", C.c_float), ("kernel_ms_strong", C.c_float), ("kernel_ms_other", C.c_float)]
+
+
 class AstcError(RuntimeError):
     def __init__(self, code, where):
         super().__init__("%s failed with astcenc_error %d" % (where, code))
@@ -310,6 +318,18 @@ class Library:
                                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                                                      C.POINTER(AdaptiveStats)]
             L.astcenc_amd_compress_image_adaptive_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_select_blocks_set_device"):
+            L.astcenc_amd_select_blocks_set_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p, C.c_size_t,
+                                                               C.POINTER(BlockCriterion), C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                               C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+            L.astcenc_amd_select_blocks_set_device.restype = C.c_int
+            L.astcenc_amd_compress_block_list_set_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p, C.c_uint,
+                                                                     C.c_void_p, C.POINTER(C.c_float)]
+            L.astcenc_amd_compress_block_list_set_device.restype = C.c_int
+            L.astcenc_amd_compress_images_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint,
+                                                                      C.POINTER(Swizzle), C.POINTER(BlockCriterion), C.c_uint, C.c_void_p,
+                                                                      C.c_size_t, C.c_void_p, C.POINTER(AdaptiveSetStats)]
+            L.astcenc_amd_compress_images_adaptive_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_mip_chain_layout"):
             L.astcenc_amd_mip_chain_layout.argtypes = [C.POINTER(Config), C.c_uint, C.c_uint, C.c_int, C.c_uint, C.POINTER(MipChainLayout)]
             L.astcenc_amd_mip_chain_layout.restype = C.c_int
@@ -550,6 +570,47 @@ class Library:
             0 if block_errors is None else block_errors.numel() * 8, s, C.byref(stats))
         return err, stats
 
+    def select_blocks_set_device(self, ctx, dims, block_errors, criterion, block_list, max_blocks=NO_BLOCK_BUDGET, stream=None):
+        """astcenc_amd_select_blocks_set_device: `dims` the (x, y, z) of every entry of the set, `block_errors` float64 [blocks of the
+        set, 4] on the device, `block_list` a device tensor of 32-bit words.  Returns (error, candidates, selected): the ascending
+        global indices of the selected blocks are block_list[:selected]."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream()
+        entries = (ImageSetEntry * max(len(dims), 1))(*[ImageSetEntry(None, None, 0, d[0], d[1], d[2], TYPE_U8, Swizzle(*SWZ_RGBA)) for d in dims])
+        candidates, selected = C.c_uint(0), C.c_uint(0)
+        err = self.lib.astcenc_amd_select_blocks_set_device(ctx, entries, len(dims), block_errors.data_ptr(), block_errors.numel() * 8,
+                                                            C.byref(criterion), max_blocks, block_list.data_ptr(), block_list.numel() * 4,
+                                                            getattr(stream, "cuda_stream", stream), C.byref(candidates), C.byref(selected))
+        return err, candidates.value, selected.value
+
+    def compress_block_list_set_device(self, ctx, entries, block_list, list_count=None, stream=None):
+        """astcenc_amd_compress_block_list_set_device over `entries` (see _set_args): the blocks named in `block_list` (a device
+        tensor of 32-bit global block indices, or None) into their slots of their entries' blocks.  Returns the astcenc_error, the
+        kernel time (ms) in self.last_kernel_ms."""
+        arr, n, s = self._set_args(entries, stream)
+        assert block_list is None or (block_list.is_contiguous() and block_list.element_size() == 4)
+        ms = C.c_float(0.0)
+        err = self.lib.astcenc_amd_compress_block_list_set_device(
+            ctx, arr, n, None if block_list is None else block_list.data_ptr(),
+            (0 if block_list is None else block_list.numel()) if list_count is None else list_count, s, C.byref(ms))
+        self.last_kernel_ms = ms.value
+        return err
+
+    def compress_images_adaptive_device(self, base_ctx, strong_ctx, entries, criterion, max_blocks=NO_BLOCK_BUDGET, decode_swizzle=SWZ_RGBA,
+                                        block_errors=None, stream=None):
+        """astcenc_amd_compress_images_adaptive_device over `entries` (see _set_args): every entry compressed with base_ctx into its
+        blocks, the at most max_blocks worst blocks that miss `criterion` re-encoded with strong_ctx and kept where better;
+        block_errors (optional, float64, four values per block of the set) receives the final streams' records.  Returns
+        (error, AdaptiveSetStats)."""
+        arr, n, s = self._set_args(entries, stream)
+        stats = AdaptiveSetStats()
+        err = self.lib.astcenc_amd_compress_images_adaptive_device(
+            base_ctx, strong_ctx, arr, n, C.byref(Swizzle(*decode_swizzle)), C.byref(criterion), max_blocks,
+            None if block_errors is None else block_errors.data_ptr(), 0 if block_errors is None else block_errors.numel() * 8, s,
+            C.byref(stats))
+        return err, stats
+
     def compare_image_set_device(self, ctx, entries, block_errors=None, stream=None):
         """astcenc_amd_compare_image_set_device over `entries` (see _set_args; an entry's image is the original, nothing in an entry
         is written).  Returns (error, [ErrorSums per entry]); block_errors (optional, float64, four values per block of the whole
@@ -761,6 +822,30 @@ class Library:
         n = layout.level_count
         ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
         return tensors, [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+
+    def compress_mip_chain_adaptive(self, base_ctx, strong_ctx, image, criterion, max_blocks=NO_BLOCK_BUDGET, kind=MIP_VOLUME, levels=0,
+                                    options=None, mip_filter=None, weighting=None, swizzle=SWZ_RGBA, decode_swizzle=SWZ_RGBA,
+                                    block_errors=None, stream=None):
+        """The adaptive driver over the mip chain of the [Z, H, W, 4] device tensor `image`: the levels are generated with
+        astcenc_amd_generate_mip_chain_weighted_device (base_ctx), one set entry per level is built from the layout, and
+        astcenc_amd_compress_images_adaptive_device compresses the set.  Returns (level tensors, per-level block tensors,
+        AdaptiveSetStats)."""
+        (w, h, d), dtype, layout, store, tensors, out = self._mip_chain_volume_buffers(base_ctx, image, kind, levels, True)
+        err = self.lib.astcenc_amd_generate_mip_chain_weighted_device(base_ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
+                                                                      self._mip_options(options), self._mip_filter(mip_filter),
+                                                                      self._mip_weighting(weighting), store.data_ptr(), layout.texels_len,
+                                                                      torch_stream(stream))
+        if err:
+            raise AstcError(err, "astcenc_amd_generate_mip_chain_weighted_device")
+        n = layout.level_count
+        ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
+        blocks = [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
+        entries = [image_set_entry(tensors[i], blocks[i], swizzle) for i in range(n)]
+        err, stats = self.compress_images_adaptive_device(base_ctx, strong_ctx, entries, criterion, max_blocks, decode_swizzle, block_errors,
+                                                          torch_stream(stream))
+        if err:
+            raise AstcError(err, "astcenc_amd_compress_images_adaptive_device")
+        return tensors, blocks, stats
 
     def resize_dims(self, w, h, max_dim=0, pow2=POW2_NONE):
         """astcenc_amd_resize_dims: returns (error, (out_w, out_h))."""

@@ -727,8 +727,9 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compare_image_set_device(
  * the compression kernel over a list of blocks, the selection of blocks by their error records, and a driver that chains
  * base compression -> scoring -> selection -> strong compression of the selected blocks -> scoring -> keep-the-better merge,
  * everything in device memory.
- *   Not done: image sets and mip chains; host-pointer input; an HDR (log2 / mPSNR) criterion; a budget such as "the worst N
- *   blocks"; more than two tiers.
+ * Each of the three has a form over an image set (below: astcenc_amd_select_blocks_set_device and its kin), which also takes a
+ * block budget: "the worst N blocks of this asset, wherever they are".
+ *   Not done: an HDR (log2 / mPSNR) criterion; host-pointer input; more than two tiers.
  *
  * astcenc_amd_compress_block_list_device: device_list[i], i < list_count, is a raster block index of the image (the order
  * of astcenc_amd_compress_volume_device, whose per-slice loading default and ASTCENC_AMD_OPT_PER_SLICE_FAST_LOAD apply).  For
@@ -819,6 +820,88 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_image_adaptive_device(
 	struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
 	void* hip_stream,
 	struct astcenc_amd_adaptive_stats* stats);
+
+/* Adaptive effort over an image set -- the levels of a mip chain, the layers of an array, a batch of textures -- with a block
+ * budget.  A set is entries[0 .. entry_count) as in astcenc_amd_compress_images_device.
+ *
+ *   Global index.  Block g of the set counts the blocks of all entries back to back in entry order, raster order within an entry:
+ *     the order in which astcenc_amd_compare_image_set_device writes device_block_errors.  At most 2^32 - 1 blocks in all.  A
+ *     single image is the set of one entry, and then g is its raster block index.
+ *   Candidate.  For block g in entry i, e and n are those of struct astcenc_amd_block_criterion, n taken from entry i's own
+ *     dimensions and the context's footprint.  Block g is a candidate iff e > max_mean_squared_error * (double)n; a NaN e never is.
+ *   Key.  k = e / (double)n, one rounded fp64 division.  A candidate has e > 0, so k is positive or +inf and never a NaN, and keys
+ *     order as their 64 bit patterns do.  The mean, not e: the threshold is per texel, and a partial edge block, or the 1 x 1 level
+ *     of a chain, must not rank below a full block merely for holding fewer texels.
+ *   Budget.  max_blocks, or ASTCENC_AMD_NO_BLOCK_BUDGET.  With c candidates and c <= max_blocks every candidate is selected.
+ *     Otherwise the selected blocks are the first max_blocks candidates in the order (key descending, global index ascending):
+ *     among bit-equal keys the lowest indices win.  max_blocks == 0 selects nothing.  The list holds the selected global indices
+ *     in ascending order, and it is the same list on every run.
+ *
+ * Common rules: everything is checked before anything is launched, an error writes nothing, the log callback names the bad
+ * argument or entry index; the work is queued on hip_stream (NULL: the context's own) and has completed on return; a call runs
+ * on the device that owns entry 0's image (the selection: the records), a buffer of another device is ASTCENC_ERR_BAD_PARAM.
+ *
+ * astcenc_amd_select_blocks_set_device: only dim_x/y/z of the entries are read, their pointers may be null.  device_list[0 ..
+ * *selected_count) receives the list, nothing past it is written; *candidate_count (optional) receives c.  For one entry and no
+ * budget it writes exactly the list of astcenc_amd_select_blocks_device.
+ *   - Errors as astcenc_amd_select_blocks_device, per entry.  Also: entry_count == 0 succeeds with both counts 0; a null `entries`
+ *     with a non-zero count, or more than 2^32 - 1 blocks in all, is ASTCENC_ERR_BAD_PARAM.  list_len must hold min(blocks of the
+ *     set, max_blocks) words (ASTCENC_ERR_OUT_OF_MEM).
+ *   - Scratch: 8 bytes per block (the keys), a word per 2048 blocks, and a fixed 8.2 KB (the state and the digit histograms);
+ *     ASTCENC_ERR_OUT_OF_MEM when it cannot be allocated.
+ *
+ * astcenc_amd_compress_block_list_set_device: for every listed g below the set's total, the 16 bytes of that block in its
+ * entry's `blocks` buffer become exactly what astcenc_amd_compress_images_device writes there; no other byte of any entry is
+ * written.  Indices at or above the total are skipped; duplicates and any order are allowed; list_count == 0 launches nothing.
+ * Entry checks as astcenc_amd_compress_images_device, list rules as astcenc_amd_compress_block_list_device.  The alpha-scale
+ * pre-pass runs per entry over the whole entry; progress counts listed blocks, cancel works as in the list call.
+ *
+ * astcenc_amd_compress_images_adaptive_device: the driver over a set.  entries[i].blocks receives the result, entries[i].swizzle is
+ * the compression swizzle, one decode_swizzle scores all entries.  Let B0 / B1 be what astcenc_amd_compress_images_device writes
+ * with the base / strong context, E0 / E1 the records astcenc_amd_compare_image_set_device gives for them (entry swizzle =
+ * decode_swizzle), and S the selection above on E0.  Block g of the output is B1 if g is in S and e(E1[g]) < e(E0[g]), else B0;
+ * device_block_errors (optional) receives the matching records, bit for bit those of the set scoring call on the final streams.
+ * B1 is computed for S only; with S empty the strong context launches nothing; after a cancelled base pass nothing is refined.
+ *   - Context agreement rules and error codes of astcenc_amd_compress_image_adaptive_device.  With one entry and
+ *     ASTCENC_AMD_NO_BLOCK_BUDGET the bytes, records and counts equal those of that call.
+ *   - Scratch: at most 16 + 64 + 4 + 8 bytes per block of the set plus the selection's fixed part, kept with the strong context;
+ *     ASTCENC_ERR_OUT_OF_MEM, with nothing written, when it cannot be allocated.
+ * A mip chain needs no call of its own: the levels of any chain call are an image set. */
+#define ASTCENC_AMD_NO_BLOCK_BUDGET 0xFFFFFFFFu
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_select_blocks_set_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	const struct astcenc_amd_block_criterion* criterion,
+	unsigned int max_blocks,
+	unsigned int* device_list, size_t list_len,
+	void* hip_stream,
+	unsigned int* candidate_count,
+	unsigned int* selected_count);
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_block_list_set_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const unsigned int* device_list, unsigned int list_count,
+	void* hip_stream,
+	float* kernel_ms);
+
+struct astcenc_amd_adaptive_set_stats {
+	unsigned int blocks, candidates, selected, replaced;
+	float kernel_ms_base, kernel_ms_strong, kernel_ms_other;
+};
+
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_compress_images_adaptive_device(
+	struct astcenc_context* base_context,
+	struct astcenc_context* strong_context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_swizzle* decode_swizzle,
+	const struct astcenc_amd_block_criterion* criterion,
+	unsigned int max_blocks,
+	struct astcenc_amd_block_error* device_block_errors, size_t block_errors_len,
+	void* hip_stream,
+	struct astcenc_amd_adaptive_set_stats* stats);
 
 /* "hip:gfx950" for the product library. */
 ASTCENC_PUBLIC const char* astcenc_amd_backend_name(void);

@@ -12,7 +12,15 @@ tiled to 8192^2; skipped when the corpus is not there).  Base -fast, strong -tho
               launch (kernel_ms_strong / selected against the -thorough baseline's kernel_ms / blocks)
 
 After a warm-up of every call: best and worst of `reps` (default 5) passes.  One JSON line per row.
-usage: time_adaptive.py [reps] [--size N] [--json out.json]"""
+
+--set: the image-set driver with a block budget (astcenc_amd_compress_images_adaptive_device) on the full mip chain of the mosaic
+(of the bench image when the corpus is not there), threshold 0, so that every block with an error is a candidate:
+  baselines   astcenc_amd_compress_images_device with each context: kernel_ms, wall time, PSNR over the whole chain
+  budgets     5, 10, 25 and 50 % of the chain's blocks: the three kernel times of the stats, wall time, dB gained over the base
+              streams, selected and replaced counts
+  selection   astcenc_amd_select_blocks_set_device on the base records with a budget of a third of the candidates and without
+              one, against astcenc_amd_compare_image_set_device on the same set (wall time of the synchronous calls)
+usage: time_adaptive.py [reps] [--size N] [--json out.json] [--set]"""
 import ctypes as C
 import json
 import os
@@ -70,6 +78,90 @@ def images():
     else:
         print(json.dumps({"image": "photographic mosaic", "skipped": why}), flush=True)
 
+
+def set_mode():
+    rows = []
+    base, strong = context(A.PRE_FAST), context(A.PRE_THOROUGH)
+    name, image = list(images())[-1]
+    d_img = torch.from_numpy(np.ascontiguousarray(image)).cuda()
+    levels = lib.generate_mip_chain_weighted_device(base, d_img[None])
+    counts = [(-(-t.shape[2] // B)) * (-(-t.shape[1] // B)) for t in levels]
+    nblocks, texels = sum(counts), sum(t.shape[1] * t.shape[2] for t in levels)
+    outs = [torch.zeros(c * 16, dtype=torch.uint8, device="cuda") for c in counts]
+    entries = list(zip(levels, outs))
+    d_err = torch.zeros(nblocks * 4, dtype=torch.float64, device="cuda")
+    d_list = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
+
+    def full(ctx):
+        assert lib.compress_images_device(ctx, entries) == 0
+        return lib.last_kernel_ms
+
+    def score(records=None):
+        err, sums = lib.compare_image_set_device(base, entries, block_errors=records)
+        assert err == 0
+        return sums
+
+    def psnr():
+        num = sum(sum(s.squared_error[k] for k in range(4)) for s in score())
+        return 999.0 if num == 0 else 10.0 * float(np.log10(texels * 4 / num))
+
+    common = {"image": name + ", mip chain", "size": size, "block": B, "levels": len(levels), "blocks": nblocks, "reps": reps}
+    psnr_of = {}
+    for what, ctx in (("base -fast alone", base), ("strong -thorough alone", strong)):
+        full(ctx)
+        wall, kernel = zip(*[walled(lambda: full(ctx)) for _ in range(reps)])
+        psnr_of[what] = psnr()
+        row = dict(common, run=what, kernel_ms=spread(kernel), wall_ms=spread(wall), psnr_db=round(psnr_of[what], 4),
+                   db_over_base=round(psnr_of[what] - psnr_of["base -fast alone"], 4))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+
+    criterion = A.block_criterion(0.0)
+    for percent in (5, 10, 25, 50):
+        budget = nblocks * percent // 100
+
+        def adaptive():
+            err, stats = lib.compress_images_adaptive_device(base, strong, entries, criterion, budget, block_errors=d_err)
+            assert err == 0
+            return stats
+
+        adaptive()
+        wall, stats = zip(*[walled(adaptive) for _ in range(reps)])
+        s = stats[0]
+        total = [x.kernel_ms_base + x.kernel_ms_strong + x.kernel_ms_other for x in stats]
+        row = dict(common, run="adaptive set, budget %d %% of the blocks" % percent, max_blocks=budget, candidates=s.candidates, selected=s.selected,
+                   replaced=s.replaced, kernel_ms_base=spread([x.kernel_ms_base for x in stats]), kernel_ms_strong=spread([x.kernel_ms_strong for x in stats]),
+                   kernel_ms_other=spread([x.kernel_ms_other for x in stats]), kernel_ms_total=spread(total), wall_ms=spread(wall))
+        final = psnr()
+        row.update(psnr_db=round(final, 4), db_over_base=round(final - psnr_of["base -fast alone"], 4))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+
+    # the selection alone against one scoring pass of the same set
+    full(base)
+    score(d_err)
+    dims = [(t.shape[2], t.shape[1], 1) for t in levels]
+    err, candidates, _ = lib.select_blocks_set_device(base, dims, d_err, criterion, d_list)
+    assert err == 0
+    timings = {"scoring pass (astcenc_amd_compare_image_set_device, with records)": lambda: score(d_err),
+               "selection, budget of a third of the candidates": lambda: lib.select_blocks_set_device(base, dims, d_err, criterion, d_list, candidates // 3),
+               "selection, no budget": lambda: lib.select_blocks_set_device(base, dims, d_err, criterion, d_list)}
+    for what, call in timings.items():
+        call()
+        wall, _ = zip(*[walled(call) for _ in range(max(reps, 5))])
+        row = dict(common, run=what, candidates=candidates, wall_ms=spread(wall))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    lib.context_free(base)
+    lib.context_free(strong)
+    if out_json:
+        with open(out_json, "w") as f:
+            json.dump({"rows": rows}, f, indent=1)
+
+
+if "--set" in sys.argv:
+    set_mode()
+    sys.exit(0)
 
 rows = []
 base, strong = context(A.PRE_FAST), context(A.PRE_THOROUGH)
