@@ -207,6 +207,17 @@ int backend_compare(Backend* b, const CompareJob& job);
  * entry points live in astcenc_set.cpp, which the sequential build of oracle/emu does not link.) */
 int backend_compress_set(Backend* b, const CompressSetJob& job);
 int backend_decompress_set(Backend* b, const DecompressSetJob& job);
+/* astcenc_amd_decompress_regions_device: the entries as DecompressDeviceJobs (device_image and stream unused), the regions as the
+ * kernel's launch records (DecodeRegionLaunch below).  Runs on the device that owns entry 0's blocks. */
+struct DecodeRegionLaunch;
+struct DecompressRegionsJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeRegionLaunch* regions;
+	uint32_t region_count;
+	void*    stream;
+};
+int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -353,6 +364,21 @@ int astc_decode_launch(const DecodeLaunch& d);
 size_t astc_decode_set_bytes(uint32_t count);
 uint32_t astc_decode_set_build(void* out, const DecodeLaunch* entries, uint32_t count);
 int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream);
+/* Windows of compressed images (astcenc_amd_decompress_regions_device; decode_regions.h): one DecodeLaunch per entry (d_image and
+ * stream unused) and one DecodeRegionLaunch per region, checked by the entry point: the window lies inside image `entry`, the
+ * pitches are whole texels, at least a window row / slice.  astc_decode_region_runs: the work items of one region, for the entry
+ * point's bound on their sum; astc_decode_regions_build writes the table (astc_decode_regions_bytes(count) bytes) and returns the
+ * runs of all regions; astc_decode_regions_launch covers them from the table's device copy, as astc_decode_set_launch does. */
+struct DecodeRegionLaunch {
+	uint32_t entry;
+	uint32_t x, y, z, size_x, size_y, size_z;
+	void*    d_out;                   // the window's texel (0, 0, 0)
+	size_t   row_pitch, slice_pitch;  // bytes, not 0
+};
+unsigned long long astc_decode_region_runs(const DecodeRegionLaunch& r, uint32_t block_x, uint32_t block_y, uint32_t block_z);
+size_t astc_decode_regions_bytes(uint32_t count);
+uint32_t astc_decode_regions_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeRegionLaunch* regions, uint32_t count);
+int astc_decode_regions_launch(const void* d_table, uint32_t runs, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -1589,6 +1589,47 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 	});
 }
 
+/* astcenc_amd_decompress_regions_device: as backend_decompress_set, with the regions' table (decode_regions.h) in place of the
+ * set's.  Only the entries a region names are looked at; their streams and every region's buffer must be on the owner's device. */
+int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job)
+{
+	std::vector<uint8_t> used(job.entry_count, 0);
+	for (uint32_t i = 0; i < job.region_count; i++) used[job.regions[i].entry] = 1;
+	return run_on_owner(b, job.entries[0].device_blocks, nullptr, 0, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	{
+		auto foreign = [s](const void* p)
+		{
+			hipPointerAttribute_t attr;
+			memset(&attr, 0, sizeof(attr));
+			if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+			return attr.device != s->device;
+		};
+		for (uint32_t e = 0; e < job.entry_count; e++)
+			if (used[e] && foreign(job.entries[e].device_blocks))
+			{
+				log_msg("decode regions: the blocks of entry %u are not on device %d, which owns entry 0's", e, s->device);
+				return 3;
+			}
+		for (uint32_t i = 0; i < job.region_count; i++)
+			if (foreign(job.regions[i].d_out))
+			{
+				log_msg("decode regions: the buffer of region %u is not on device %d, which owns entry 0's blocks", i, s->device);
+				return 3;
+			}
+		std::vector<DecodeLaunch> d(job.entry_count);
+		for (uint32_t e = 0; e < job.entry_count; e++) d[e] = decode_launch(b, s, job.entries[e], job.entries[e].device_blocks, nullptr, nullptr);
+		const size_t bytes = astc_decode_regions_bytes(job.region_count);
+		s->h_set.assign(bytes, 0);
+		const uint32_t runs = astc_decode_regions_build(s->h_set.data(), d.data(), job.entry_count, job.regions, job.region_count);
+		const int urc = set_table_upload(s, stream, bytes);
+		if (urc != 0) return urc;
+		int lrc = astc_decode_regions_launch(s->d_set, runs, stream);
+		if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
+		HIP_TRY(hipStreamSynchronize(stream), return 2);
+		return 0;
+	});
+}
+
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial
  * sums has a fixed size (rc 1 when it cannot be had, nothing launched), the totals come back once the stream has run. */
 static int compare_blocks_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const QualitySetJob& job)

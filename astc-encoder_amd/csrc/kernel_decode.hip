@@ -5,9 +5,11 @@
 #define ASTC_ENABLE_HDR 1
 #include "backend.h"
 #include "wave_decode.h"
+#include "decode_regions.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 namespace astcd {
 
@@ -53,6 +55,25 @@ astc_decompress_set(const ImageSetTable* __restrict__ set, uint32_t run0)
 	const uint32_t bx0 = (in_layer - by * rec.runs_x) * (uint32_t)DECODE_BATCH;
 	const uint32_t left = rec.img.blocks_x - bx0;
 	decode_row_batch(rec.img, rec.blocks, bx0, by, bz, (int)(left < (uint32_t)DECODE_BATCH ? left : (uint32_t)DECODE_BATCH), batch);
+}
+
+/* Windows of compressed images (astcenc_amd_decompress_regions_device): the runs of every region back to back on a 1D grid, a
+ * run's region found in the table, its window decoded into the region's own buffer (decode_regions.h).  `run0`: the launch
+ * covers runs [run0, run0 + gridDim.x) of the call (astc_decode_regions_launch). */
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
+astc_decode_regions(const ImageSetTable* __restrict__ set, uint32_t run0)
+{
+	__shared__ DecodeBatch batch;
+	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
+	const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
+	const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
+	const __attribute__((address_space(4))) uint32_t* first = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
+	const uint32_t r = run0 + blockIdx.x;
+	const uint32_t g = image_set_find(first, count, r);
+	const DecodeRegionRecord rec = image_set_record<DecodeRegionRecord>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
+		t + image_set_records_offset(count) + (size_t)g * sizeof(DecodeRegionRecord)));
+	DecodeStore store;
+	decode_region_run(rec, r - first[g], batch, store);
 }
 
 size_t astc_decode_tables_bytes() { return sizeof(DecodeTables); }
@@ -143,6 +164,38 @@ int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream)
 	{
 		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
 		hipLaunchKernelGGL(astc_decompress_set, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
+	}
+	return (int)hipGetLastError();
+}
+
+unsigned long long astc_decode_region_runs(const DecodeRegionLaunch& r, uint32_t block_x, uint32_t block_y, uint32_t block_z)
+{
+	return decode_region_runs(r.x, r.y, r.z, r.size_x, r.size_y, r.size_z, block_x, block_y, block_z);
+}
+
+size_t astc_decode_regions_bytes(uint32_t count) { return decode_regions_bytes(count); }
+
+uint32_t astc_decode_regions_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeRegionLaunch* regions, uint32_t count)
+{
+	std::vector<DecodeImage> images(entry_count);
+	std::vector<const uint8_t*> streams(entry_count);
+	for (uint32_t e = 0; e < entry_count; e++)
+	{
+		images[e] = decode_image(entries[e]);
+		streams[e] = entries[e].d_blocks;
+	}
+	return decode_regions_build(out, images.data(), streams.data(), regions, count);
+}
+
+int astc_decode_regions_launch(const void* d_table, uint32_t runs, void* stream)
+{
+	// (the grid of astc_decode_set_launch, and its test limit)
+	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 0xFFFFFFFFu / 64u; }();
+	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);
+	for (uint32_t run0 = 0; run0 < runs; run0 += limit)
+	{
+		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
+		hipLaunchKernelGGL(astc_decode_regions, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
 	}
 	return (int)hipGetLastError();
 }

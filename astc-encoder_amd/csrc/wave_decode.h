@@ -1140,12 +1140,52 @@ WV_FN uint32_t pixel_from_lerps(uint32_t sel, const uint32_t x[4])
 	return byte_perm(ba, rg, sel);
 }
 
+/* Which texels of a run's blocks the texel phases produce and where they go: a compile-time policy next to `Sink`.
+ *   cols_begin / cols_end   2D: the run's columns [begin, end) the lanes are dealt to, counted from the run's first column
+ *                           (row_len = the columns of the run's blocks)
+ *   rows_begin / rows_end   2D: the rows [begin, end) of the block row that are walked (rows = those inside the image)
+ *   has                     3D: the texel (a lane per block-texel) is produced
+ *   at                      index of the first component of texel (x, y, z) of the image, counted from img.data
+ *   row_step                ... and what one row further down adds to it
+ * DecodeWhole is the decoder's: everything the blocks cover, clipped to the image, at its place in the tightly packed image --
+ * every member is the expression decode_row_batch had in its place, so its instantiations compile to what they were. */
+struct DecodeWhole {
+	static constexpr bool whole = true;
+	WV_FN int cols_begin(uint32_t, int) const { return 0; }
+	WV_FN int cols_end(uint32_t, int row_len) const { return row_len; }
+	WV_FN int rows_begin(uint32_t, int) const { return 0; }
+	WV_FN int rows_end(uint32_t, int rows) const { return rows; }
+	WV_FN bool has(uint32_t, uint32_t, uint32_t) const { return true; }
+	WV_FN size_t at(const DecodeImage& img, uint32_t x, uint32_t y, uint32_t z) const { return (((size_t)z * img.dim_y + y) * img.dim_x + x) * 4; }
+	WV_FN size_t row_step(const DecodeImage& img) const { return (size_t)img.dim_x * 4; }
+};
+
+/* A window of the image (astcenc_amd_decompress_regions_device): texels [x, end_x) x [y, end_y) x [z, end_z), wholly inside the
+ * image, written to a buffer of its own -- img.data is the address of the window's first texel, rows and slices are
+ * row_texels / slice_texels texels apart.  Columns, rows and texels outside the window are not visited at all. */
+struct DecodeWindow {
+	uint32_t x, y, z;
+	uint32_t end_x, end_y, end_z;
+	size_t   row_texels, slice_texels;
+	static constexpr bool whole = false;
+	WV_FN int cols_begin(uint32_t x0, int) const { return x > x0 ? (int)(x - x0) : 0; }
+	WV_FN int cols_end(uint32_t x0, int row_len) const { return end_x - x0 < (uint32_t)row_len ? (int)(end_x - x0) : row_len; }
+	WV_FN int rows_begin(uint32_t y0, int) const { return y > y0 ? (int)(y - y0) : 0; }
+	WV_FN int rows_end(uint32_t y0, int rows) const { return end_y - y0 < (uint32_t)rows ? (int)(end_y - y0) : rows; }
+	WV_FN bool has(uint32_t xi, uint32_t yi, uint32_t zi) const { return xi >= x && xi < end_x && yi >= y && yi < end_y && zi >= z && zi < end_z; }
+	WV_FN size_t at(const DecodeImage&, uint32_t xi, uint32_t yi, uint32_t zi) const
+	{
+		return ((size_t)(zi - z) * slice_texels + (size_t)(yi - y) * row_texels + (size_t)(xi - x)) * 4;
+	}
+	WV_FN size_t row_step(const DecodeImage&) const { return row_texels * 4; }
+};
+
 /* The texel phase of a run of 2D blocks: the image rows the run covers, one after the other.  kMulti / kDual: the run
  * has blocks with more than one partition (1: with two at most, 2: with three or four) / with two weight planes
  * (wave-uniform; a run without them skips the partition hash and reads its endpoints once per column / reads one plane).  kGeneral: some texel of the run does not leave as an
  * integer-built RGBA8 pixel (store_texel_general); the builds without it are the RGBA8 decoder's inner loops. */
-template <int kMulti, bool kDual, bool kGeneral, class Sink>
-WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink)
+template <int kMulti, bool kDual, bool kGeneral, class Sink, class Window>
+WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink, const Window win)
 {
 	const int block_x = (int)img.block_x, block_y = (int)img.block_y;
 	const bool small_block = block_x * block_y < 31;
@@ -1155,9 +1195,12 @@ WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, 
 	const int rows = (int)(img.dim_y - y0 < (uint32_t)block_y ? img.dim_y - y0 : (uint32_t)block_y);
 	const int row_len = count * block_x;
 	const uint32_t x0 = bx0 * (uint32_t)block_x;
-	for (int c0 = 0; c0 < row_len; c0 += 64)
+	// (a window: the lanes are dealt to its columns inside the run and its rows inside the block row)
+	const int col_end = win.cols_end(x0, row_len);
+	const int row0 = win.rows_begin(y0, rows), row1 = win.rows_end(y0, rows);
+	for (int c0 = win.cols_begin(x0, row_len); c0 < col_end; c0 += 64)
 	{
-		WV_FOR64(l, i_min(64, row_len - c0))
+		WV_FOR64(l, i_min(64, col_end - c0))
 		{
 			const int col = c0 + l;
 			const int k = (int)(umul24((uint32_t)col, img.bx_inv16) >> 16);
@@ -1196,9 +1239,9 @@ WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, 
 			const uint32_t* epk = s.ep[k];
 			U32x4 e = { 0u, 0u, 0u, 0u };
 			if (!kMulti) e = load_u32x4_aligned(epk);
-			size_t at = (((size_t)bz * img.dim_y + y0) * img.dim_x + xi) * 4;      // (2D blocks: layer bz of the stream is slice bz of the image)
-			int gt64 = 32;                                                          // dt * ty * (wy - 1) + 32, row by row
-			for (int ty = 0; ty < rows; ty++, at += (size_t)img.dim_x * 4, gt64 += dty)
+			size_t at = win.at(img, xi, y0 + (uint32_t)row0, bz);                   // (2D blocks: layer bz of the stream is slice bz of the image)
+			int gt64 = 32 + row0 * dty;                                             // dt * ty * (wy - 1) + 32, row by row
+			for (int ty = row0; ty < row1; ty++, at += win.row_step(img), gt64 += dty)
 			{
 				int cv[4] = { 0, 0, 0, 0 };
 				uint32_t px = cpx;
@@ -1253,11 +1296,12 @@ WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, 
 	}
 }
 
-/* Decode blocks bx0 .. bx0 + count - 1 (count <= DECODE_BATCH) of block row `by`, layer `bz` of the stream into the image.
+/* Decode blocks bx0 .. bx0 + count - 1 (count <= DECODE_BATCH) of block row `by`, layer `bz` of the stream into the image
+ * -- with a window (`win`, see DecodeWhole / DecodeWindow above) the texels of those blocks that lie inside it, into its buffer.
  * All 64 lanes call this.  The arithmetic, block by block, is that of the single-block routines above (parse_block_header,
  * unpack_block_payload, infill_texel_weights: what astcenc_get_block_info runs on the host). */
-template <class Sink>
-WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink)
+template <class Sink, class Window = DecodeWhole>
+WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink, const Window win = Window())
 {
 	const int block_x = (int)img.block_x, block_y = (int)img.block_y, block_z = (int)img.block_z;
 	const int T = block_x * block_y * block_z;
@@ -1484,21 +1528,21 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 	// ---- texels ----
 	if (block_z == 1)
 	{
-		if (any_general) decode_row_texels<2, true, true, Sink>(img, bx0, by, bz, count, s, sink);
+		if (any_general) decode_row_texels<2, true, true, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
 		else if (any_many)
 		{
-			if (any_dual) decode_row_texels<2, true, false, Sink>(img, bx0, by, bz, count, s, sink);
-			else decode_row_texels<2, false, false, Sink>(img, bx0, by, bz, count, s, sink);
+			if (any_dual) decode_row_texels<2, true, false, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
+			else decode_row_texels<2, false, false, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
 		}
 		else if (any_multi)
 		{
-			if (any_dual) decode_row_texels<1, true, false, Sink>(img, bx0, by, bz, count, s, sink);
-			else decode_row_texels<1, false, false, Sink>(img, bx0, by, bz, count, s, sink);
+			if (any_dual) decode_row_texels<1, true, false, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
+			else decode_row_texels<1, false, false, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
 		}
 		else
 		{
-			if (any_dual) decode_row_texels<0, true, false, Sink>(img, bx0, by, bz, count, s, sink);
-			else decode_row_texels<0, false, false, Sink>(img, bx0, by, bz, count, s, sink);
+			if (any_dual) decode_row_texels<0, true, false, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
+			else decode_row_texels<0, false, false, Sink, Window>(img, bx0, by, bz, count, s, sink, win);
 		}
 	}
 	else
@@ -1521,8 +1565,9 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 				const uint32_t xi = (bx0 + (uint32_t)k) * (uint32_t)block_x + (uint32_t)tx;
 				const uint32_t yi = by * (uint32_t)block_y + (uint32_t)ty;
 				const uint32_t zi = bz * (uint32_t)block_z + (uint32_t)tz;
-				if (xi >= img.dim_x || yi >= img.dim_y || zi >= img.dim_z) continue;
-				const size_t at = (((size_t)zi * img.dim_y + yi) * img.dim_x + xi) * 4;
+				if (xi >= img.dim_x || yi >= img.dim_y || zi >= img.dim_z || !win.has(xi, yi, zi)) continue;
+				// (the decoder's index spelled out: formed through the policy's member, the same expression moved a handful of the kernels' instructions)
+				const size_t at = Window::whole ? (((size_t)zi * img.dim_y + yi) * img.dim_x + xi) * 4 : win.at(img, xi, yi, zi);
 				const uint32_t ra = s.rec[k][0], rc = s.rec[k][2];
 				const bool fast = img.data_type == 0 && (ra & 8u) != 0u;
 				uint32_t px = s.rec[k][3];

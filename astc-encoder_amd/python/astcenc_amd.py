@@ -102,7 +102,8 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compare_blocks_hdr_device", "astcenc_amd_compare_image_set_device",
                "astcenc_amd_compress_block_list_device", "astcenc_amd_select_blocks_device",
                "astcenc_amd_compress_image_adaptive_device", "astcenc_amd_select_blocks_set_device",
-               "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device"]
+               "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
+               "astcenc_amd_decompress_regions_device"]
 NO_BLOCK_BUDGET = 0xFFFFFFFF
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
@@ -164,6 +165,40 @@ def image_set_entry(image, blocks, swizzle=SWZ_RGBA, blocks_len=None):
     h, w = image.shape[-3], image.shape[-2]
     return ImageSetEntry(image.data_ptr(), blocks.data_ptr(), blocks.numel() * blocks.element_size() if blocks_len is None else blocks_len,
                          w, h, d, types[image.dtype], Swizzle(*swizzle))
+
+
+def compressed_entry(blocks, dims, data_type, swizzle=SWZ_RGBA, blocks_len=None):
+    """ImageSetEntry of a compressed image alone (astcenc_amd_decompress_regions_device ignores `image`): `blocks` a uint8
+    device tensor, dims (dim_x, dim_y[, dim_z]), data_type the TYPE_* its windows are decoded to."""
+    assert blocks.is_contiguous()
+    dz = dims[2] if len(dims) > 2 else 1
+    return ImageSetEntry(None, blocks.data_ptr(), blocks.numel() * blocks.element_size() if blocks_len is None else blocks_len,
+                         dims[0], dims[1], dz, data_type, Swizzle(*swizzle))
+
+
+class DecodeRegion(C.Structure):
+    """struct astcenc_amd_decode_region (include/astcenc_amd.h)."""
+    _fields_ = [("entry", C.c_uint), ("x", C.c_uint), ("y", C.c_uint), ("z", C.c_uint),
+                ("size_x", C.c_uint), ("size_y", C.c_uint), ("size_z", C.c_uint),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("slice_pitch", C.c_size_t)]
+
+
+def decode_region(entry, origin, size, out):
+    """DecodeRegion of window `size` = (size_x, size_y, size_z) at `origin` = (x, y, z) of entry `entry`.  `out`: a device
+    tensor view [size_y, size_x, 4] or [size_z, size_y, size_x, 4] whose pitches are taken from its strides (the texels of a row
+    must be contiguous: strides (..., 4, 1)), or an explicit (ptr, row_pitch, slice_pitch) in bytes (0 = tightly packed)."""
+    if isinstance(out, tuple):
+        ptr, row_pitch, slice_pitch = out
+    else:
+        assert out.dim() in (3, 4) and out.shape[-1] == 4, "out is [size_y, size_x, 4] or [size_z, size_y, size_x, 4]"
+        assert tuple(out.shape[-3:-1]) == (size[1], size[0]) and (out.shape[0] if out.dim() == 4 else 1) == size[2], "out does not have the window's shape"
+        st = out.stride()
+        if st[-1] != 1 or st[-2] != 4:
+            raise ValueError("the texels of a row of `out` are not contiguous (strides %r)" % (tuple(st),))
+        item = out.element_size()
+        ptr, row_pitch = out.data_ptr(), st[-3] * item
+        slice_pitch = st[0] * item if out.dim() == 4 else 0
+    return DecodeRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], size[2], ptr, row_pitch, slice_pitch)
 
 
 class ErrorSums(C.Structure):
@@ -295,6 +330,10 @@ class Library:
             L.astcenc_amd_compress_images_device.restype = C.c_int
             L.astcenc_amd_decompress_images_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.c_void_p]
             L.astcenc_amd_decompress_images_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_decompress_regions_device"):
+            L.astcenc_amd_decompress_regions_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(DecodeRegion), C.c_uint,
+                                                                C.c_void_p]
+            L.astcenc_amd_decompress_regions_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_compare_blocks_device"):
             blocks_args = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(Swizzle),
                            C.c_void_p, C.c_size_t]
@@ -483,6 +522,15 @@ class Library:
         """astcenc_amd_decompress_images_device over `entries` (see _set_args): every entry's blocks into its image."""
         arr, n, s = self._set_args(entries, stream)
         return self.lib.astcenc_amd_decompress_images_device(ctx, arr, n, s)
+
+    def decompress_regions_device(self, ctx, entries, regions, stream=None):
+        """astcenc_amd_decompress_regions_device: windows of the compressed images `entries` (see _set_args; compressed_entry makes
+        one without an image) into buffers of their own.  regions: DecodeRegion, or (entry, (x, y, z), (size_x, size_y, size_z), out)
+        tuples (see decode_region)."""
+        arr, n, s = self._set_args(entries, stream)
+        regions = [r if isinstance(r, DecodeRegion) else decode_region(*r) for r in regions]
+        rarr = (DecodeRegion * len(regions))(*regions) if regions else None
+        return self.lib.astcenc_amd_decompress_regions_device(ctx, arr, n, rarr, len(regions), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

@@ -104,6 +104,45 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_images_device(
 	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
 	void* hip_stream);
 
+/* Decoding parts of compressed images: many rectangles (boxes) of many compressed images in one launch -- a batch of crops, a
+ * tile of a mip level, the neighbourhood of a block -- each into a caller buffer with its own origin and pitches.  Only the
+ * blocks a window covers are read and decoded; nothing the size of a source image is written or allocated.
+ *
+ * A region names a window of one entry and where it goes. */
+struct astcenc_amd_decode_region {
+	unsigned int entry;                     /* index into entries[]: the compressed image the window lies in */
+	unsigned int x, y, z;                   /* origin of the window in that image, texels */
+	unsigned int size_x, size_y, size_z;    /* its size, each >= 1 */
+	void* out;                              /* device pointer: size_z slices of size_y rows of size_x RGBA texels of the entry's data_type */
+	size_t row_pitch, slice_pitch;          /* bytes from row to row / slice to slice of `out`; 0 = tightly packed */
+};
+
+/* Decode regions[0 .. region_count).  Texel (i, j, k) of a region's `out` is bit for bit texel (x + i, y + j, z + k) of what
+ * astcenc_amd_decompress_image_device writes for that entry alone: the entry's data_type and swizzle (the Z swizzle included),
+ * the context's profile, error blocks and constant-colour blocks, 2D footprints (z selects array slices) and 3D ones.  No byte
+ * of `out` outside the window's texels is written: not the padding of a pitch, not what lies between regions written into one
+ * atlas or batch tensor.
+ *
+ *   - Each entry describes a compressed image as in astcenc_amd_decompress_images_device; `image` is ignored and may be null.
+ *     `blocks`, `blocks_len`, the dimensions and the swizzle of every entry get the checks and error codes of that call.  Many
+ *     regions may name one entry; an entry that no region names costs nothing.
+ *   - Everything is checked before anything is launched: a failure returns its error with nothing written, and the log callback
+ *     (astcenc_amd_set_log_callback) names the index of the region or entry.
+ *   - region_count == 0 returns ASTCENC_SUCCESS and does nothing.  ASTCENC_ERR_BAD_PARAM: a null context; a null `regions`; a
+ *     null `entries` with a non-zero entry_count; a region whose `entry` is not below entry_count, with a zero size, or whose
+ *     window is not wholly inside the entry's image (x + size_x is compared in 64 bits); a non-zero pitch smaller than the tight
+ *     one (size_x texels / size_y rows of row_pitch) or not a multiple of the texel size (4 / 8 / 16 bytes for U8 / F16 / F32);
+ *     an `out` not aligned to the texel size; more than 2^32 - 1 work items (runs of up to 32 covered blocks of one block row) in
+ *     all.  A null `out`: ASTCENC_ERR_BAD_CONTEXT, as a null buffer elsewhere.
+ *   - The call runs on the device that owns entry 0's blocks; the blocks of an entry some region names or a region's `out` on
+ *     another device return ASTCENC_ERR_BAD_PARAM.  Outputs must not overlap each other or any input (not checked).
+ *   - The call returns once the work on hip_stream (null: the context's own stream) has completed. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_regions_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_decode_region* regions, unsigned int region_count,
+	void* hip_stream);
+
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
  *
  * Level i is max(1, dim_x >> i) x max(1, dim_y >> i) (the GL / Vulkan / KTX rule); level_count == 0 means the full chain down
