@@ -424,61 +424,89 @@ WV_FN void color_error_for_quant_level(const Ctx& c, const PartView& pv, int p, 
 }
 
 /* Combine the per-partition tables for one quant level (ref: :728-766, :842-891, :967-1027). */
-WV_FN void combine_partitions_for_quant(int pc, int quant, const FmtView& fs)
+/* The nest for PC partitions, in registers: each partition's four errors come in with one 16-byte read and its four
+ * formats with one word; the nest is unrolled, so which candidates (i, j, k, l) make which integer count is known when
+ * the code is compiled, and the counts are taken one after the other -- one running minimum and its formats live at a
+ * time, each result stored once.  A count's candidates are still visited in the reference's order and compared with its
+ * `<=`, so ties fall as they do there.  Every count 0 .. 3 PC has a candidate, and min(sum, 1e10) is below the initial
+ * 1e30 whatever the sum (a NaN gives 1e10): a count's first candidate always takes the cell, as it did before. */
+template <int PC>
+WV_FN void combine_partitions_in_registers(int quant, const FmtView& fs)
 {
-	const int ncols = pc == 2 ? 7 : pc == 3 ? 10 : 13;
-	for (int j = 0; j < ncols; j++) fs.comb_error(quant)[j] = ERROR_CALC_DEFAULT;
-	if (quant < QUANT_6) return;
-
-	for (int i = 0; i < 4; i++)
+	constexpr int NCOLS = 3 * PC + 1;
+	float be[PC][4];
+	uint32_t fmt[PC][4];          // partition p's format for integer count i, already in its place (bits 4p .. 4p+3)
+	#pragma unroll
+	for (int p = 0; p < PC; p++)
 	{
-		for (int j = 0; j < 4; j++)
+		const f4 e = load4_aligned(fs.best_error(p, quant));
+		be[p][0] = e.x; be[p][1] = e.y; be[p][2] = e.z; be[p][3] = e.w;
+		uint32_t f;
+		__builtin_memcpy(&f, __builtin_assume_aligned(fs.format_of_choice(p, quant), 4), 4);
+		#pragma unroll
+		for (int i = 0; i < 4; i++) fmt[p][i] = ((f >> (8 * i)) & 0xFFu) << (4 * p);
+	}
+	float* out_error = fs.comb_error(quant);
+
+	#pragma unroll
+	for (int intcnt = 0; intcnt < NCOLS; intcnt++)
+	{
+		float ce = ERROR_CALC_DEFAULT;
+		uint32_t cf = 0u;
+		bool first = true;
+		#pragma unroll
+		for (int i = 0; i < 4; i++)
 		{
-			int low2 = i_min(i, j), high2 = i_max(i, j);
-			if ((high2 - low2) > 1) continue;
-			if (pc == 2)
+			#pragma unroll
+			for (int j = 0; j < 4; j++)
 			{
-				int intcnt = i + j;
-				float errorterm = f_min(fs.best_error(0, quant)[i] + fs.best_error(1, quant)[j], 1e10f);
-				if (errorterm <= fs.comb_error(quant)[intcnt])
+				const int low2 = i_min(i, j), high2 = i_max(i, j);
+				if ((high2 - low2) > 1) continue;
+				#pragma unroll
+				for (int k = 0; k < (PC >= 3 ? 4 : 1); k++)
 				{
-					fs.comb_error(quant)[intcnt] = errorterm;
-					fs.comb_format(quant, intcnt) = (uint16_t)(fs.format_of_choice(0, quant)[i] | (fs.format_of_choice(1, quant)[j] << 4));
-				}
-				continue;
-			}
-			for (int k = 0; k < 4; k++)
-			{
-				int low3 = i_min(k, low2), high3 = i_max(k, high2);
-				if ((high3 - low3) > 1) continue;
-				if (pc == 3)
-				{
-					int intcnt = i + j + k;
-					float errorterm = f_min(fs.best_error(0, quant)[i] + fs.best_error(1, quant)[j] + fs.best_error(2, quant)[k], 1e10f);
-					if (errorterm <= fs.comb_error(quant)[intcnt])
+					const int low3 = PC >= 3 ? i_min(k, low2) : low2, high3 = PC >= 3 ? i_max(k, high2) : high2;
+					if ((high3 - low3) > 1) continue;
+					#pragma unroll
+					for (int l = 0; l < (PC >= 4 ? 4 : 1); l++)
 					{
-						fs.comb_error(quant)[intcnt] = errorterm;
-						fs.comb_format(quant, intcnt) = (uint16_t)(fs.format_of_choice(0, quant)[i] | (fs.format_of_choice(1, quant)[j] << 4) |
-						                                           (fs.format_of_choice(2, quant)[k] << 8));
-					}
-					continue;
-				}
-				for (int l = 0; l < 4; l++)
-				{
-					int low4 = i_min(l, low3), high4 = i_max(l, high3);
-					if ((high4 - low4) > 1) continue;
-					int intcnt = i + j + k + l;
-					float errorterm = f_min(fs.best_error(0, quant)[i] + fs.best_error(1, quant)[j] + fs.best_error(2, quant)[k] + fs.best_error(3, quant)[l], 1e10f);
-					if (errorterm <= fs.comb_error(quant)[intcnt])
-					{
-						fs.comb_error(quant)[intcnt] = errorterm;
-						fs.comb_format(quant, intcnt) = (uint16_t)(fs.format_of_choice(0, quant)[i] | (fs.format_of_choice(1, quant)[j] << 4) |
-						                                           (fs.format_of_choice(2, quant)[k] << 8) | (fs.format_of_choice(3, quant)[l] << 12));
+						const int low4 = PC >= 4 ? i_min(l, low3) : low3, high4 = PC >= 4 ? i_max(l, high3) : high3;
+						if ((high4 - low4) > 1) continue;
+						if (i + j + (PC >= 3 ? k : 0) + (PC >= 4 ? l : 0) != intcnt) continue;
+						float sum = be[0][i] + be[1][j];
+						uint32_t formats = fmt[0][i] | fmt[1][j];
+						if constexpr (PC >= 3) { sum = sum + be[2][k]; formats |= fmt[2][k]; }
+						if constexpr (PC >= 4) { sum = sum + be[3][l]; formats |= fmt[3][l]; }
+						const float errorterm = f_min(sum, 1e10f);
+						const bool take = first || errorterm <= ce;
+						ce = take ? errorterm : ce;
+						cf = take ? formats : cf;
+						first = false;
 					}
 				}
 			}
 		}
+		out_error[intcnt] = ce;
+		fs.comb_format(quant, intcnt) = (uint16_t)cf;
+#if WV_DEVICE
+		// (one count's chain at a time: left to itself the instruction scheduler runs all thirteen side by side, which takes
+		//  more registers than a stage function has without a stack frame)
+		__builtin_amdgcn_sched_barrier(0);
+#endif
 	}
+}
+
+WV_FN void combine_partitions_for_quant(int pc, int quant, const FmtView& fs)
+{
+	if (quant < QUANT_6)
+	{
+		const int ncols = pc == 2 ? 7 : pc == 3 ? 10 : 13;
+		for (int j = 0; j < ncols; j++) fs.comb_error(quant)[j] = ERROR_CALC_DEFAULT;
+		return;
+	}
+	if (pc == 2) combine_partitions_in_registers<2>(quant, fs);
+	else if (pc == 3) combine_partitions_in_registers<3>(quant, fs);
+	else combine_partitions_in_registers<4>(quant, fs);
 }
 
 /* The colour quant level of every integer-pair count for one bit budget: one 16-byte row of the transposed quant mode

@@ -56,22 +56,31 @@ WV_FN void compute_avgs_and_dirs(const Ctx& c, const PartView& pv, const CompSel
 		WV_SYNC();
 		WV_FOR(j, 4)
 		{
+			// (at most three partitions before the last: a literal trip count, the quarter sums of all three read side by
+			//  side -- a row past pc - 1 holds someone else's numbers, still inside fbox, and is not used)
 			if (j < n)
 			{
 				float block_total = blk.data_mean[cs.comp(j)] * (float)T;
 				float rest = block_total;
-				for (int p = 0; p < pc - 1; p++)
+				f4 a[3];
+				#pragma unroll
+				for (int p = 0; p < 3; p++) a[p] = load4(&tr.fbox[(p * n + j) * 4]);
+				#pragma unroll
+				for (int p = 0; p < 3; p++)
 				{
-					const float* a = &tr.fbox[(p * n + j) * 4];
-					float total = hadd4(a[0], a[1], a[2], a[3]);
-					rest = rest - total;
-					tr.pm_avg[p][j] = total / (float)pv.cnt(p);
+					if (p < pc - 1)
+					{
+						float total = hadd4(a[p].x, a[p].y, a[p].z, a[p].w);
+						rest = rest - total;
+						tr.pm_avg[p][j] = total / (float)pv.cnt(p);
+					}
 				}
 				tr.pm_avg[pc - 1][j] = rest / (float)pv.cnt(pc - 1);
 			}
 			else
 			{
-				for (int p = 0; p < pc; p++) tr.pm_avg[p][j] = 0.0f;
+				#pragma unroll
+				for (int p = 0; p < 4; p++) { if (p < pc) tr.pm_avg[p][j] = 0.0f; }
 			}
 		}
 	}
@@ -83,8 +92,10 @@ WV_FN void compute_avgs_and_dirs(const Ctx& c, const PartView& pv, const CompSel
 	uint32_t needed = 0;
 	{
 		uint32_t cols = 0;
-		for (int b = 0; b < n; b++) cols |= 1u << cs.comp(b);
-		for (int a = 0; a < n; a++) needed |= cols << (cs.comp(a) * 4);
+		#pragma unroll
+		for (int b = 0; b < 4; b++) cols |= b < n ? 1u << cs.comp(b) : 0u;
+		#pragma unroll
+		for (int a = 0; a < 4; a++) needed |= a < n ? cols << (cs.comp(a) * 4) : 0u;
 	}
 	const bool cached = pc == 1 && (wv_uniform(tr.dirsum1_mask) & needed) == needed;
 	if (cached)
@@ -124,20 +135,25 @@ WV_FN void compute_avgs_and_dirs(const Ctx& c, const PartView& pv, const CompSel
 
 	WV_FOR64(p, pc)
 	{
-		float best[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+		// (a literal four by four: the partition's four rows are read side by side and everything stays in registers; the
+		//  entries past n -- not written above -- are taken as the zeros of the reference's narrower vectors, the rows past n
+		//  never win)
+		f4 row[4];
+		#pragma unroll
+		for (int which = 0; which < 4; which++) row[which] = load4(&tr.fbox[(p * 4 + which) * 4]);
+		f4 best = mk4(0.0f, 0.0f, 0.0f, 0.0f);
 		float best_sum = 0.0f;
-		for (int which = 0; which < n; which++)
+		#pragma unroll
+		for (int which = 0; which < 4; which++)
 		{
-			float s[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-			for (int j = 0; j < n; j++) s[j] = tr.fbox[(p * 4 + which) * 4 + j];
-			float prod = hadd4(s[0] * s[0], s[1] * s[1], s[2] * s[2], s[3] * s[3]);
-			if (which == 0 || prod > best_sum)
-			{
-				best_sum = prod;
-				for (int j = 0; j < 4; j++) best[j] = s[j];
-			}
+			const f4 r = row[which];
+			const f4 s = mk4(0 < n ? r.x : 0.0f, 1 < n ? r.y : 0.0f, 2 < n ? r.z : 0.0f, 3 < n ? r.w : 0.0f);
+			float prod = hadd4(s.x * s.x, s.y * s.y, s.z * s.z, s.w * s.w);
+			const bool take = which < n && (which == 0 || prod > best_sum);
+			best_sum = take ? prod : best_sum;
+			best = select4(take, s, best);
 		}
-		for (int j = 0; j < 4; j++) tr.pm_dir[p][j] = best[j];
+		store4(tr.pm_dir[p], best);
 	}
 	WV_SYNC();
 }
@@ -217,8 +233,9 @@ WV_FN void ideal_colors_and_weights_1comp(const Ctx& c, const PartView& pv, int 
 	}
 	WV_ONE
 	{
-		bool cw = true;
-		for (int p = 1; p < pc; p++) cw = cw && tr.fbox[p * 4 + 2] == tr.fbox[2];
+		// (the four squared lengths read side by side; a partition past pc does not count)
+		const float l0 = tr.fbox[2], l1 = tr.fbox[6], l2 = tr.fbox[10], l3 = tr.fbox[14];
+		const bool cw = (pc < 2 || l1 == l0) & (pc < 3 || l2 == l0) & (pc < 4 || l3 == l0);
 		tr.is_constant_wes[plane] = cw ? 1 : 0;
 	}
 	WV_SYNC();
@@ -253,11 +270,17 @@ WV_FN void ideal_colors_and_weights_ncomp(const Ctx& c, const PartView& pv, int 
 	// raw line parameter of every texel (ref: :282-291, :431-440, :553-562); with one partition its range is folded
 	// across the wave on the way (minimum / maximum of finite values: exact whatever the order)
 	float lo_part = 1e10f, hi_part = -1e10f;
+	// (the four channel rows once per call; an entry past n names channel 0 -- CompSel::set -- : a row that exists, read
+	//  along with the others and replaced by the reference's zero)
+	const float* const d0 = c.data(cs.comp(0));
+	const float* const d1 = c.data(cs.comp(1));
+	const float* const d2 = c.data(cs.comp(2));
+	const float* const d3 = c.data(cs.comp(3));
 	WV_FOR_T(t, T)
 	{
 		int p = pv.of_texel[t];
-		f4 pt = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-		for (int j = 0; j < n; j++) set_lane(pt, j, c.data(cs.comp(j))[t]);
+		const float v0 = d0[t], v1 = d1[t], v2 = d2[t], v3 = d3[t];
+		f4 pt = mk4(0 < n ? v0 : 0.0f, 1 < n ? v1 : 0.0f, 2 < n ? v2 : 0.0f, 3 < n ? v3 : 0.0f);
 		f4 a = load4(tr.pm_avg[p]);
 		f4 b = load4(&tr.fbox[32 + p * 4]);
 		float param = n == 3 ? dot3_s(pt - a, b) : dot_s(pt - a, b);
@@ -305,10 +328,15 @@ WV_FN void ideal_colors_and_weights_ncomp(const Ctx& c, const PartView& pv, int 
 			tr.ep0[plane][p][k] = blk.data_min[k];
 			tr.ep1[plane][p][k] = blk.data_max[k];
 		}
-		for (int j = 0; j < n; j++)
+		// (a literal trip count: lane(lo, j) is then a register, not a ladder of selects on a run-time j)
+		#pragma unroll
+		for (int j = 0; j < 4; j++)
 		{
-			tr.ep0[plane][p][cs.comp(j)] = lane(lo, j);
-			tr.ep1[plane][p][cs.comp(j)] = lane(hi, j);
+			if (j < n)
+			{
+				tr.ep0[plane][p][cs.comp(j)] = lane(lo, j);
+				tr.ep1[plane][p][cs.comp(j)] = lane(hi, j);
+			}
 		}
 	}
 	WV_SYNC();
@@ -330,8 +358,9 @@ WV_FN void ideal_colors_and_weights_ncomp(const Ctx& c, const PartView& pv, int 
 	}
 	WV_ONE
 	{
-		bool cw = true;
-		for (int p = 1; p < pc; p++) cw = cw && tr.fbox[p * 4 + 2] == tr.fbox[2];
+		// (the four squared lengths read side by side; a partition past pc does not count)
+		const float l0 = tr.fbox[2], l1 = tr.fbox[6], l2 = tr.fbox[10], l3 = tr.fbox[14];
+		const bool cw = (pc < 2 || l1 == l0) & (pc < 3 || l2 == l0) & (pc < 4 || l3 == l0);
 		tr.is_constant_wes[plane] = cw ? 1 : 0;
 	}
 	WV_SYNC();
