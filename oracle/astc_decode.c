@@ -23,6 +23,9 @@
  * Scope: 2D footprints, LDR and LDR_SRGB decode profiles, RGBA8 output (decode_unorm8 rules).
  * HDR endpoint formats decode to the error colour in these profiles, exactly like the reference.
  *
+ * astc_oracle_block_info returns what the decode call parsed before it made texels (parse_header, shared by both): the
+ * census of tests/block_census.py, which shows from an encoder's bytes which encodings its search reached.
+ *
  * Build: gcc -O2 -shared -fPIC -o oracle/_build/libastc_decode.so oracle/astc_decode.c
  */
 #include <stdint.h>
@@ -412,9 +415,11 @@ static void blue_contract(int c[4])
 	c[1] = (c[1] + c[2]) >> 1;
 }
 
-/* Returns 0 for an LDR format, 1 for an HDR format (-> error colour in LDR profiles). */
-static int unpack_endpoints(int fmt, const int *v, int e0[4], int e1[4])
+/* Returns 0 for an LDR format, 1 for an HDR format (-> error colour in LDR profiles).  *contracted: whether
+ * formats 8, 9, 12 and 13 took their blue-contracted arm (0 for every other format). */
+static int unpack_endpoints(int fmt, const int *v, int e0[4], int e1[4], int *contracted)
 {
+	*contracted = 0;
 	switch (fmt)
 	{
 	case 0:
@@ -463,6 +468,7 @@ static int unpack_endpoints(int fmt, const int *v, int e0[4], int e1[4])
 		{
 			blue_contract(a); blue_contract(b);
 			memcpy(e0, b, sizeof b); memcpy(e1, a, sizeof a);
+			*contracted = 1;
 		}
 		return 0;
 	}
@@ -482,6 +488,7 @@ static int unpack_endpoints(int fmt, const int *v, int e0[4], int e1[4])
 		{
 			blue_contract(a); blue_contract(b);
 			for (int k = 0; k < 4; k++) { e0[k] = clamp255(b[k]); e1[k] = clamp255(a[k]); }
+			*contracted = 1;
 		}
 		if (fmt == 9) { e0[3] = 255; e1[3] = 255; }
 		return 0;
@@ -501,15 +508,28 @@ static void fill_block(uint8_t *texels, int count, int r, int g, int b, int a)
 	}
 }
 
-/* Decode one 128-bit block to bx*by*bz RGBA8 texels (x fastest, then y, then z; bz = 1 for a 2D
- * footprint).  Returns 0 ok, 1 error block (magenta written). */
-EXPORT int astc_oracle_decode_block_3d(const uint8_t pcb[16], int bx, int by, int bz, int srgb, uint8_t *texels)
-{
-	const int T = bx * by * bz;
-	unsigned mode = rd_bits(pcb, 0, 11);
-	BlockModeInfo bm = decode_block_mode(mode, bx, by, bz);
+/* What the 128 bits say before any texel is made: shared by the decode call and the info call. */
+enum { KIND_NORMAL = 0, KIND_VOID_LDR = 1, KIND_VOID_FP16 = 2, KIND_ERROR = 3 };
 
-	if (bm.void_extent)
+typedef struct
+{
+	int kind;
+	BlockModeInfo bm;
+	int parts, seed, plane2;        /* plane2: the second plane's component, -1 with one plane */
+	int fmt[4];
+	int nvals, cq, color_start;     /* colour stream: integers, quant level, first bit */
+	int wcount, real_wcount;        /* weights per plane, and stored */
+} BlockHeader;
+
+static void parse_header(const uint8_t pcb[16], int bx, int by, int bz, BlockHeader *h)
+{
+	memset(h, 0, sizeof *h);
+	h->plane2 = -1;
+	h->kind = KIND_ERROR;
+	unsigned mode = rd_bits(pcb, 0, 11);
+	h->bm = decode_block_mode(mode, bx, by, bz);
+
+	if (h->bm.void_extent)
 	{
 		int bad;
 		if (bz > 1)
@@ -527,24 +547,102 @@ EXPORT int astc_oracle_decode_block_3d(const uint8_t pcb[16], int bx, int by, in
 			int all_ones = ls == 0x1FFF && hs == 0x1FFF && lt == 0x1FFF && ht == 0x1FFF;
 			bad = rd_bits(pcb, 10, 2) != 3 || ((ls >= hs || lt >= ht) && !all_ones);
 		}
-		if (bad || (mode & 0x200))      /* FP16 constant colour is an error in LDR profiles */
+		if (!bad) h->kind = (mode & 0x200) ? KIND_VOID_FP16 : KIND_VOID_LDR;
+		return;
+	}
+	if (!h->bm.ok) return;
+
+	h->wcount = h->bm.wx * h->bm.wy * h->bm.wz;
+	h->real_wcount = h->bm.dual ? 2 * h->wcount : h->wcount;
+	int wbits = ise_bits(h->real_wcount, h->bm.wq);
+	int parts = h->parts = (int)rd_bits(pcb, 11, 2) + 1;
+	if (h->bm.dual && parts == 4) return;
+
+	/* colour endpoint modes */
+	int *fmt = h->fmt;
+	int below = 128 - wbits;
+	int extra = 0;
+	if (parts == 1)
+	{
+		fmt[0] = (int)rd_bits(pcb, 13, 4);
+		h->color_start = 17;
+	}
+	else
+	{
+		h->seed = (int)rd_bits(pcb, 13, 10);
+		h->color_start = 29;
+		unsigned cem = rd_bits(pcb, 23, 6);
+		if ((cem & 3) == 0)
 		{
-			fill_block(texels, T, 0xFF, 0, 0xFF, 0xFF);
-			return 1;
+			for (int i = 0; i < parts; i++) fmt[i] = (int)((cem >> 2) & 0xF);
 		}
+		else
+		{
+			extra = 3 * parts - 4;
+			below -= extra;
+			unsigned enc = cem | (rd_bits(pcb, (unsigned)below, (unsigned)extra) << 6);
+			int base = (int)(enc & 3) - 1;
+			for (int i = 0; i < parts; i++)
+			{
+				int cls = base + (int)((enc >> (2 + i)) & 1);
+				int low = (int)((enc >> (2 + parts + 2 * i)) & 3);
+				fmt[i] = cls * 4 + low;
+			}
+		}
+	}
+	if (h->bm.dual)
+	{
+		below -= 2;
+		h->plane2 = (int)rd_bits(pcb, (unsigned)below, 2);
+	}
+
+	for (int i = 0; i < parts; i++) h->nvals += 2 * (fmt[i] >> 2) + 2;
+	if (h->nvals > 18) return;
+
+	/* the colour stream uses the largest quantisation whose BISE size fits the space left */
+	int cbits = below - h->color_start;
+	if (cbits < 0) cbits = 0;
+	h->cq = -1;
+	for (int q = 20; q >= 0; q--)
+	{
+		if (ise_bits(h->nvals, q) <= cbits) { h->cq = q; break; }
+	}
+	if (h->cq < 4) return;         /* fewer than 6 levels is not a legal endpoint encoding */
+	h->kind = KIND_NORMAL;
+}
+
+/* The unquantised colour integers of partition `i` and what they unpack to; returns unpack_endpoints' result. */
+static int partition_endpoints(const BlockHeader *h, const uint8_t *csym, int i, int e0[4], int e1[4], int *contracted)
+{
+	int pos = 0;
+	for (int k = 0; k < i; k++) pos += 2 * (h->fmt[k] >> 2) + 2;
+	int v[8] = { 0 };
+	int n = 2 * (h->fmt[i] >> 2) + 2;
+	for (int j = 0; j < n; j++) v[j] = unquant_color(csym[pos + j], h->cq);
+	return unpack_endpoints(h->fmt[i], v, e0, e1, contracted);
+}
+
+/* Decode one 128-bit block to bx*by*bz RGBA8 texels (x fastest, then y, then z; bz = 1 for a 2D
+ * footprint).  Returns 0 ok, 1 error block (magenta written). */
+EXPORT int astc_oracle_decode_block_3d(const uint8_t pcb[16], int bx, int by, int bz, int srgb, uint8_t *texels)
+{
+	const int T = bx * by * bz;
+	BlockHeader hd;
+	parse_header(pcb, bx, by, bz, &hd);
+	const BlockModeInfo bm = hd.bm;
+
+	if (hd.kind == KIND_VOID_LDR)
+	{
 		int c[4];
 		for (int k = 0; k < 4; k++) c[k] = (pcb[8 + 2 * k] | (pcb[9 + 2 * k] << 8)) >> 8;   /* UNORM16 -> top 8 bits */
 		fill_block(texels, T, c[0], c[1], c[2], c[3]);
 		return 0;
 	}
-	if (!bm.ok) goto error;
+	if (hd.kind != KIND_NORMAL) goto error;      /* (FP16 constant colour is an error in LDR profiles) */
 
 	{
-		int wcount = bm.wx * bm.wy * bm.wz;
-		int real_wcount = bm.dual ? 2 * wcount : wcount;
-		int wbits = ise_bits(real_wcount, bm.wq);
-		int parts = (int)rd_bits(pcb, 11, 2) + 1;
-		if (bm.dual && parts == 4) goto error;
+		int wcount = hd.wcount;
+		int parts = hd.parts, seed = hd.seed, plane2 = hd.plane2;
 
 		/* the weight stream is stored bit-reversed from the top of the block */
 		uint8_t rev[16];
@@ -555,7 +653,7 @@ EXPORT int astc_oracle_decode_block_3d(const uint8_t pcb[16], int bx, int by, in
 			rev[i] = (uint8_t)r;
 		}
 		uint8_t wsym[64];
-		ise_decode(rev, 0, bm.wq, real_wcount, wsym);
+		ise_decode(rev, 0, bm.wq, hd.real_wcount, wsym);
 		int w[2][64];
 		for (int i = 0; i < wcount; i++)
 		{
@@ -563,71 +661,14 @@ EXPORT int astc_oracle_decode_block_3d(const uint8_t pcb[16], int bx, int by, in
 			else { w[0][i] = unquant_weight(wsym[i], bm.wq); w[1][i] = 0; }
 		}
 
-		/* colour endpoint modes */
-		int fmt[4] = { 0, 0, 0, 0 };
-		int below = 128 - wbits;
-		int extra = 0, seed = 0, color_start;
-		if (parts == 1)
-		{
-			fmt[0] = (int)rd_bits(pcb, 13, 4);
-			color_start = 17;
-		}
-		else
-		{
-			seed = (int)rd_bits(pcb, 13, 10);
-			color_start = 29;
-			unsigned cem = rd_bits(pcb, 23, 6);
-			if ((cem & 3) == 0)
-			{
-				for (int i = 0; i < parts; i++) fmt[i] = (int)((cem >> 2) & 0xF);
-			}
-			else
-			{
-				extra = 3 * parts - 4;
-				below -= extra;
-				unsigned enc = cem | (rd_bits(pcb, (unsigned)below, (unsigned)extra) << 6);
-				int base = (int)(enc & 3) - 1;
-				for (int i = 0; i < parts; i++)
-				{
-					int cls = base + (int)((enc >> (2 + i)) & 1);
-					int low = (int)((enc >> (2 + parts + 2 * i)) & 3);
-					fmt[i] = cls * 4 + low;
-				}
-			}
-		}
-		int plane2 = -1;
-		if (bm.dual)
-		{
-			below -= 2;
-			plane2 = (int)rd_bits(pcb, (unsigned)below, 2);
-		}
-
-		int nvals = 0;
-		for (int i = 0; i < parts; i++) nvals += 2 * (fmt[i] >> 2) + 2;
-		if (nvals > 18) goto error;
-
-		/* the colour stream uses the largest quantisation whose BISE size fits the space left */
-		int cbits = below - color_start;
-		if (cbits < 0) cbits = 0;
-		int cq = -1;
-		for (int q = 20; q >= 0; q--)
-		{
-			if (ise_bits(nvals, q) <= cbits) { cq = q; break; }
-		}
-		if (cq < 4) goto error;      /* fewer than 6 levels is not a legal endpoint encoding */
-
 		uint8_t csym[18];
-		ise_decode(pcb, (unsigned)color_start, cq, nvals, csym);
+		ise_decode(pcb, (unsigned)hd.color_start, hd.cq, hd.nvals, csym);
 
 		int ep0[4][4], ep1[4][4], hdr[4];
-		int pos = 0;
 		for (int i = 0; i < parts; i++)
 		{
-			int v[8] = { 0 };
-			int n = 2 * (fmt[i] >> 2) + 2;
-			for (int j = 0; j < n; j++) v[j] = unquant_color(csym[pos + j], cq);
-			pos += n;
-			hdr[i] = unpack_endpoints(fmt[i], v, ep0[i], ep1[i]);
+			int contracted;
+			hdr[i] = partition_endpoints(&hd, csym, i, ep0[i], ep1[i], &contracted);
 			if (hdr[i])
 			{
 				int m[4] = { 0xFF, 0, 0xFF, 0xFF };
@@ -763,4 +804,51 @@ EXPORT int astc_oracle_decode_image(const uint8_t *blocks, int bx, int by, int w
 		}
 	}
 	return errors;
+}
+
+/* The header fields of one block, without decoding texels (tests/block_census.py counts them over a stream).
+ * Unused partition slots hold -1 in format[] and blue_contraction[]; blue_contraction is -1 for every format but 8, 9, 12
+ * and 13, where it is 1 when the stored integers select the blue-contracted arm.  Fields other than kind are meaningful for
+ * KIND_NORMAL only. */
+typedef struct
+{
+	int kind;                   /* 0 normal, 1 LDR void extent, 2 FP16 void extent, 3 error */
+	int partition_count;
+	int dual_plane, plane2_component;   /* component -1 with one plane */
+	int weight_x, weight_y, weight_z, weight_quant;
+	int color_quant;
+	int mixed_classes;          /* partitions whose formats differ in class (format >> 2) */
+	int partition_seed;
+	int format[4];
+	int blue_contraction[4];
+} AstcOracleBlockInfo;
+
+EXPORT int astc_oracle_block_info(const uint8_t pcb[16], int bx, int by, int bz, AstcOracleBlockInfo *info)
+{
+	BlockHeader hd;
+	parse_header(pcb, bx, by, bz, &hd);
+	memset(info, 0, sizeof *info);
+	info->kind = hd.kind;
+	info->plane2_component = -1;
+	for (int i = 0; i < 4; i++) { info->format[i] = -1; info->blue_contraction[i] = -1; }
+	if (hd.kind != KIND_NORMAL) return hd.kind;
+
+	info->partition_count = hd.parts;
+	info->dual_plane = hd.bm.dual;
+	info->plane2_component = hd.plane2;
+	info->weight_x = hd.bm.wx; info->weight_y = hd.bm.wy; info->weight_z = hd.bm.wz;
+	info->weight_quant = hd.bm.wq;
+	info->color_quant = hd.cq;
+	info->partition_seed = hd.seed;
+	uint8_t csym[18];
+	ise_decode(pcb, (unsigned)hd.color_start, hd.cq, hd.nvals, csym);
+	for (int i = 0; i < hd.parts; i++)
+	{
+		int f = hd.fmt[i], e0[4], e1[4], contracted;
+		info->format[i] = f;
+		if ((f >> 2) != (hd.fmt[0] >> 2)) info->mixed_classes = 1;
+		partition_endpoints(&hd, csym, i, e0, e1, &contracted);
+		if (f == 8 || f == 9 || f == 12 || f == 13) info->blue_contraction[i] = contracted;
+	}
+	return hd.kind;
 }

@@ -3,6 +3,7 @@
 reference's own astcenc_decompress_image, then uses it as a format oracle on the committed golden
 encoder outputs: the bytes must decode, with no error blocks, to an image close to the source.
 """
+import collections
 import ctypes
 import json
 import os
@@ -10,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import block_census
 import images
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,11 +37,43 @@ def dec(built):
     return decode
 
 
+def _info_agrees_with_decode(lib, data, block):
+    """For every block of the stream: the kind astc_oracle_block_info reports is what astc_oracle_decode_block_3d does with
+    the block in an LDR profile -- error and FP16 void extent: the error colour; LDR void extent: its constant; normal: no
+    error."""
+    bz = block[2] if len(block) > 2 else 1
+    texels = np.zeros((block[0] * block[1] * bz, 4), dtype=np.uint8)
+    infos = block_census.block_infos(data, block)
+    rows = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, 16)
+    assert len(infos) == len(rows)
+    for i, (info, row) in enumerate(zip(infos, rows)):
+        err = lib.astc_oracle_decode_block_3d(row.ctypes.data, block[0], block[1], bz, 0, texels.ctypes.data)
+        kind = block_census.KINDS[info.kind]
+        assert err == (1 if kind in ("error", "void_fp16") else 0), (i, kind, err)
+        if err:
+            assert (texels == (255, 0, 255, 255)).all(), (i, kind)
+        if kind == "void_ldr":
+            assert (texels == row[9::2][:4]).all(), (i, kind)
+        if kind == "normal":
+            assert 1 <= info.partition_count <= 4 and 4 <= info.color_quant <= 20 and 0 <= info.weight_quant <= 11
+            assert not (info.dual_plane and info.partition_count == 4)
+            assert (info.plane2_component >= 0) == bool(info.dual_plane)
+    return collections.Counter(block_census.KINDS[info.kind] for info in infos)
+
+
+@pytest.fixture(scope="module")
+def dec_lib(dec):
+    lib = ctypes.CDLL(LIB_DECODE)
+    lib.astc_oracle_decode_block_3d.restype = ctypes.c_int
+    lib.astc_oracle_decode_block_3d.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    return lib
+
+
 FOOTPRINTS = [(4, 4), (5, 4), (5, 5), (6, 5), (6, 6), (8, 5), (8, 6), (8, 8), (10, 5), (10, 6), (10, 8), (10, 10), (12, 10), (12, 12)]
 
 
 @pytest.mark.parametrize("block", FOOTPRINTS)
-def test_decoder_matches_reference_on_encoder_output(ref, dec, block, A):
+def test_decoder_matches_reference_on_encoder_output(ref, dec, dec_lib, block, A):
     w, h = block[0] * 7 + 3, block[1] * 6 + 1            # ragged edges
     for name, quality in (("noisy", 60.0), ("random", 10.0), ("two_colour", 98.0)):
         img = images.ALL[name](w, h)
@@ -48,6 +82,8 @@ def test_decoder_matches_reference_on_encoder_output(ref, dec, block, A):
         got, errors = dec(data, block, w, h)
         assert errors == 0
         assert np.array_equal(want, got), (name, np.argwhere(want != got)[:4])
+        kinds = _info_agrees_with_decode(dec_lib, data, block)
+        assert kinds["error"] == 0 and kinds["void_fp16"] == 0, (name, kinds)
     data = ref.compress(images.noisy(w, h, 3), block, 60.0, profile=A.PRF_LDR_SRGB)
     want = ref.decompress(data, w, h, block, profile=A.PRF_LDR_SRGB)
     got, _ = dec(data, block, w, h, srgb=True)
@@ -74,6 +110,22 @@ def test_decoder_matches_reference_on_random_bit_patterns(ref, dec, block):
     assert errors > 0
     bad = np.argwhere((want != got).any(axis=2))
     assert len(bad) == 0, "first differing texels (y, x): %s" % bad[:4]
+
+
+@pytest.mark.parametrize("block", [(4, 4), (6, 6), (8, 5), (12, 12), (4, 4, 4), (6, 6, 6)])
+def test_block_info_agrees_with_decode_on_random_bit_patterns(dec_lib, block):
+    """astc_oracle_block_info and the decode call share one header parse: on random patterns, with a dense share of void
+    extents of both kinds, every kind is met and each agrees with what the decode call returns and writes."""
+    rng = np.random.default_rng(4321 + block[0] + len(block))
+    blocks = rng.integers(0, 256, size=(4096, 16), dtype=np.uint8)
+    blocks[::7, 0] = 0xFC
+    blocks[::7, 1] |= 0x01
+    blocks[::14, 1] = 0xFD
+    blocks[::14, 2:8] = 0xFF
+    blocks[::28, 1] = 0xFF            # FP16 void extents
+    blocks[1::5, 1] &= 0xE7
+    kinds = _info_agrees_with_decode(dec_lib, blocks, block)
+    assert all(kinds[k] >= 8 for k in block_census.KINDS), kinds
 
 
 def test_golden_encoder_output_decodes_cleanly(dec):
@@ -115,7 +167,7 @@ FOOTPRINTS_3D = [(3, 3, 3), (4, 3, 3), (4, 4, 3), (4, 4, 4), (5, 4, 4), (5, 5, 4
 
 
 @pytest.mark.parametrize("block", FOOTPRINTS_3D)
-def test_3d_decoder_matches_reference(ref, dec_volume, block):
+def test_3d_decoder_matches_reference(ref, dec_volume, dec_lib, block):
     """The 3D block modes, simplex weight infill, z-aware partition hash and 3D void extents of the
     oracle decoder against the reference decoder: encoder output and random bit patterns."""
     d, h, w = 2 * block[2] + 1, 2 * block[1] + 2, 3 * block[0] + 1
@@ -125,6 +177,8 @@ def test_3d_decoder_matches_reference(ref, dec_volume, block):
         got, errors = dec_volume(data, block, w, h, d)
         assert errors == 0
         assert np.array_equal(want, got), (kind, np.argwhere(want != got)[:4])
+        kinds = _info_agrees_with_decode(dec_lib, data, block)
+        assert kinds["error"] == 0 and kinds["void_fp16"] == 0, (kind, kinds)
     rng = np.random.default_rng(99 + block[0] + block[2])
     junk = rng.integers(0, 256, size=3 * 3 * 4 * 16, dtype=np.uint8)
     junk.reshape(-1, 16)[::3, 0] = 0xFC
