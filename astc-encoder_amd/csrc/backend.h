@@ -218,6 +218,18 @@ struct DecompressRegionsJob {
 	void*    stream;
 };
 int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job);
+/* astcenc_amd_decompress_tensors_device: the same with the call's tensor format and the regions as DecodeTensorLaunch. */
+struct DecodeTensorFormat;
+struct DecodeTensorLaunch;
+struct DecompressTensorsJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	const DecodeTensorLaunch* regions;
+	uint32_t region_count;
+	void*    stream;
+};
+int backend_decompress_tensors(Backend* b, const DecompressTensorsJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -379,6 +391,25 @@ unsigned long long astc_decode_region_runs(const DecodeRegionLaunch& r, uint32_t
 size_t astc_decode_regions_bytes(uint32_t count);
 uint32_t astc_decode_regions_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeRegionLaunch* regions, uint32_t count);
 int astc_decode_regions_launch(const void* d_table, uint32_t runs, void* stream);
+/* Windows decoded into tensors (astcenc_amd_decompress_tensors_device; decode_tensors.h): the call's format and one
+ * DecodeTensorLaunch per region, checked by the entry point -- pitches in elements of the format's type, resolved (not 0; plane
+ * unused with the interleaved layout), at least the tight ones.  The work items of a region are astc_decode_region_runs of its
+ * window; the table and the launch as above, the kernel build picked by the format's type and layout. */
+struct DecodeTensorFormat {
+	uint32_t type, layout, channels;      // astcenc_amd_tensor_type / _layout, 1..4
+	float    scale[4], bias[4];
+};
+struct DecodeTensorLaunch {
+	uint32_t entry;
+	uint32_t x, y, z, size_x, size_y, size_z;
+	uint32_t flags;                       // ASTCENC_AMD_TENSOR_FLIP_*
+	void*    d_out;                       // element (c = 0, k = 0, j = 0, i = 0)
+	size_t   row_pitch, slice_pitch, plane_pitch;
+};
+size_t astc_decode_tensors_bytes(uint32_t count);
+uint32_t astc_decode_tensors_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format,
+                                   const DecodeTensorLaunch* regions, uint32_t count);
+int astc_decode_tensors_launch(const void* d_table, uint32_t runs, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -1589,13 +1589,17 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 	});
 }
 
-/* astcenc_amd_decompress_regions_device: as backend_decompress_set, with the regions' table (decode_regions.h) in place of the
- * set's.  Only the entries a region names are looked at; their streams and every region's buffer must be on the owner's device. */
-int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job)
+/* astcenc_amd_decompress_regions_device and astcenc_amd_decompress_tensors_device: as backend_decompress_set, with the regions'
+ * table (decode_regions.h, decode_tensors.h) in place of the set's.  Only the entries a region names are looked at; their streams
+ * and every region's buffer must be on the owner's device.  entry_of / out_of: region i's entry and buffer; table(d, out): the
+ * table's bytes, or with `out` the table written there from the entries' launches `d`, returning its runs; launch: its kernel. */
+template <class EntryOf, class OutOf, class Table, class Launch>
+static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, uint32_t entry_count, uint32_t region_count, void* job_stream,
+                              const char* what, EntryOf entry_of, OutOf out_of, Table table, Launch launch)
 {
-	std::vector<uint8_t> used(job.entry_count, 0);
-	for (uint32_t i = 0; i < job.region_count; i++) used[job.regions[i].entry] = 1;
-	return run_on_owner(b, job.entries[0].device_blocks, nullptr, 0, job.stream, [&](DeviceSlot* s, hipStream_t stream)
+	std::vector<uint8_t> used(entry_count, 0);
+	for (uint32_t i = 0; i < region_count; i++) used[entry_of(i)] = 1;
+	return run_on_owner(b, entries[0].device_blocks, nullptr, 0, job_stream, [&](DeviceSlot* s, hipStream_t stream)
 	{
 		auto foreign = [s](const void* p)
 		{
@@ -1604,30 +1608,52 @@ int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job)
 			if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
 			return attr.device != s->device;
 		};
-		for (uint32_t e = 0; e < job.entry_count; e++)
-			if (used[e] && foreign(job.entries[e].device_blocks))
+		for (uint32_t e = 0; e < entry_count; e++)
+			if (used[e] && foreign(entries[e].device_blocks))
 			{
-				log_msg("decode regions: the blocks of entry %u are not on device %d, which owns entry 0's", e, s->device);
+				log_msg("%s: the blocks of entry %u are not on device %d, which owns entry 0's", what, e, s->device);
 				return 3;
 			}
-		for (uint32_t i = 0; i < job.region_count; i++)
-			if (foreign(job.regions[i].d_out))
+		for (uint32_t i = 0; i < region_count; i++)
+			if (foreign(out_of(i)))
 			{
-				log_msg("decode regions: the buffer of region %u is not on device %d, which owns entry 0's blocks", i, s->device);
+				log_msg("%s: the buffer of region %u is not on device %d, which owns entry 0's blocks", what, i, s->device);
 				return 3;
 			}
-		std::vector<DecodeLaunch> d(job.entry_count);
-		for (uint32_t e = 0; e < job.entry_count; e++) d[e] = decode_launch(b, s, job.entries[e], job.entries[e].device_blocks, nullptr, nullptr);
-		const size_t bytes = astc_decode_regions_bytes(job.region_count);
+		std::vector<DecodeLaunch> d(entry_count);
+		for (uint32_t e = 0; e < entry_count; e++) d[e] = decode_launch(b, s, entries[e], entries[e].device_blocks, nullptr, nullptr);
+		const size_t bytes = table(d.data(), nullptr);
 		s->h_set.assign(bytes, 0);
-		const uint32_t runs = astc_decode_regions_build(s->h_set.data(), d.data(), job.entry_count, job.regions, job.region_count);
+		const uint32_t runs = (uint32_t)table(d.data(), s->h_set.data());
 		const int urc = set_table_upload(s, stream, bytes);
 		if (urc != 0) return urc;
-		int lrc = astc_decode_regions_launch(s->d_set, runs, stream);
+		int lrc = launch(s->d_set, runs, stream);
 		if (lrc != 0) { log_msg("decode kernel launch failed (hip error %d)", lrc); return 2; }
 		HIP_TRY(hipStreamSynchronize(stream), return 2);
 		return 0;
 	});
+}
+
+int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job)
+{
+	return decompress_windows(b, job.entries, job.entry_count, job.region_count, job.stream, "decode regions",
+		[&](uint32_t i) { return job.regions[i].entry; }, [&](uint32_t i) { return job.regions[i].d_out; },
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_regions_build(out, d, job.entry_count, job.regions, job.region_count) : astc_decode_regions_bytes(job.region_count);
+		},
+		astc_decode_regions_launch);
+}
+
+int backend_decompress_tensors(Backend* b, const DecompressTensorsJob& job)
+{
+	return decompress_windows(b, job.entries, job.entry_count, job.region_count, job.stream, "decode tensors",
+		[&](uint32_t i) { return job.regions[i].entry; }, [&](uint32_t i) { return job.regions[i].d_out; },
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_tensors_build(out, d, job.entry_count, *job.format, job.regions, job.region_count) : astc_decode_tensors_bytes(job.region_count);
+		},
+		[&](const void* d_table, uint32_t runs, void* stream) { return astc_decode_tensors_launch(d_table, runs, job.format->type, job.format->layout, stream); });
 }
 
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial

@@ -6,6 +6,7 @@
 #include "backend.h"
 #include "wave_decode.h"
 #include "decode_regions.h"
+#include "decode_tensors.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -74,6 +75,25 @@ astc_decode_regions(const ImageSetTable* __restrict__ set, uint32_t run0)
 		t + image_set_records_offset(count) + (size_t)g * sizeof(DecodeRegionRecord)));
 	DecodeStore store;
 	decode_region_run(rec, r - first[g], batch, store);
+}
+
+/* Windows decoded into tensors (astcenc_amd_decompress_tensors_device): astc_decode_regions with the tensor policies of
+ * decode_tensors.h -- the same table shape, lookup and grid; the record also carries the call's format, and the texels leave
+ * converted, scaled and placed (TensorStore, TensorWindow).  One build per tensor type and layout, which hold for a call. */
+template <uint32_t kType, uint32_t kLayout>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
+astc_decode_tensors(const ImageSetTable* __restrict__ set, uint32_t run0)
+{
+	__shared__ DecodeBatch batch;
+	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
+	const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
+	const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
+	const __attribute__((address_space(4))) uint32_t* first = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
+	const uint32_t r = run0 + blockIdx.x;
+	const uint32_t g = image_set_find(first, count, r);
+	const DecodeTensorRecord rec = image_set_record<DecodeTensorRecord>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
+		t + image_set_records_offset(count) + (size_t)g * sizeof(DecodeTensorRecord)));
+	decode_tensor_run<kType, kLayout>(rec, r - first[g], batch);
 }
 
 size_t astc_decode_tables_bytes() { return sizeof(DecodeTables); }
@@ -196,6 +216,38 @@ int astc_decode_regions_launch(const void* d_table, uint32_t runs, void* stream)
 	{
 		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
 		hipLaunchKernelGGL(astc_decode_regions, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
+	}
+	return (int)hipGetLastError();
+}
+
+size_t astc_decode_tensors_bytes(uint32_t count) { return decode_tensors_bytes(count); }
+
+uint32_t astc_decode_tensors_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format,
+                                   const DecodeTensorLaunch* regions, uint32_t count)
+{
+	std::vector<DecodeImage> images(entry_count);
+	std::vector<const uint8_t*> streams(entry_count);
+	for (uint32_t e = 0; e < entry_count; e++)
+	{
+		images[e] = decode_image(entries[e]);
+		streams[e] = entries[e].d_blocks;
+	}
+	return decode_tensors_build(out, images.data(), streams.data(), format, regions, count);
+}
+
+int astc_decode_tensors_launch(const void* d_table, uint32_t runs, uint32_t type, uint32_t layout, void* stream)
+{
+	typedef void (*Kernel)(const ImageSetTable*, uint32_t);
+	static const Kernel kernels[3][2] = { { astc_decode_tensors<0, 0>, astc_decode_tensors<0, 1> }, { astc_decode_tensors<1, 0>, astc_decode_tensors<1, 1> },
+	                                      { astc_decode_tensors<2, 0>, astc_decode_tensors<2, 1> } };
+	if (type > 2 || layout > 1) return (int)hipErrorInvalidValue;
+	// (the grid of astc_decode_set_launch, and its test limit)
+	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 0xFFFFFFFFu / 64u; }();
+	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);
+	for (uint32_t run0 = 0; run0 < runs; run0 += limit)
+	{
+		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
+		hipLaunchKernelGGL(kernels[type][layout], dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
 	}
 	return (int)hipGetLastError();
 }

@@ -103,7 +103,10 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_block_list_device", "astcenc_amd_select_blocks_device",
                "astcenc_amd_compress_image_adaptive_device", "astcenc_amd_select_blocks_set_device",
                "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
-               "astcenc_amd_decompress_regions_device"]
+               "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device"]
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
+TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
+TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
 NO_BLOCK_BUDGET = 0xFFFFFFFF
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
@@ -199,6 +202,57 @@ def decode_region(entry, origin, size, out):
         ptr, row_pitch = out.data_ptr(), st[-3] * item
         slice_pitch = st[0] * item if out.dim() == 4 else 0
     return DecodeRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], size[2], ptr, row_pitch, slice_pitch)
+
+
+class TensorFormat(C.Structure):
+    """struct astcenc_amd_tensor_format (include/astcenc_amd.h)."""
+    _fields_ = [("type", C.c_int), ("layout", C.c_int), ("channels", C.c_uint), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+def tensor_format(type, layout, channels, scale=(1.0,) * 4, bias=(0.0,) * 4):
+    """TensorFormat from TENSOR_* constants and per-channel sequences (shorter ones are padded with scale 1, bias 0)."""
+    scale, bias = list(scale) + [1.0] * (4 - len(scale)), list(bias) + [0.0] * (4 - len(bias))
+    return TensorFormat(type, layout, channels, (C.c_float * 4)(*scale[:4]), (C.c_float * 4)(*bias[:4]))
+
+
+class TensorRegion(C.Structure):
+    """struct astcenc_amd_tensor_region (include/astcenc_amd.h)."""
+    _fields_ = [("entry", C.c_uint), ("x", C.c_uint), ("y", C.c_uint), ("z", C.c_uint),
+                ("size_x", C.c_uint), ("size_y", C.c_uint), ("size_z", C.c_uint), ("flags", C.c_uint),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("slice_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
+
+
+def tensor_region(entry, origin, size, out_view, flip_x=False, flip_y=False, layout=TENSOR_PLANAR):
+    """TensorRegion of window `size` = (size_x, size_y, size_z) at `origin` = (x, y, z) of entry `entry`, written into the torch
+    view `out_view`: [C, H, W] or [C, D, H, W] for TENSOR_PLANAR, [H, W, C] or [D, H, W, C] for TENSOR_INTERLEAVED, with H, W, D
+    the window's size_y, size_x, size_z and C the format's channels.  Pointer and pitches (in elements) come from the view's
+    strides; ValueError for strides the layout cannot express: columns that are not `1` (planar) or `C` (interleaved) elements
+    apart, interleaved channels that are not adjacent, a negative stride.  Or an explicit (ptr, row_pitch, slice_pitch,
+    plane_pitch) in elements (0 = tightly packed)."""
+    flags = (TENSOR_FLIP_X if flip_x else 0) | (TENSOR_FLIP_Y if flip_y else 0)
+    if isinstance(out_view, tuple):
+        ptr, row_pitch, slice_pitch, plane_pitch = out_view
+        return TensorRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], size[2], flags, ptr, row_pitch, slice_pitch, plane_pitch)
+    shape, st = tuple(out_view.shape), tuple(out_view.stride())
+    if out_view.dim() not in (3, 4):
+        raise ValueError("out_view has %d dimensions: [C, H, W], [C, D, H, W], [H, W, C] or [D, H, W, C]" % out_view.dim())
+    if any(v < 0 for v in st):
+        raise ValueError("out_view has a negative stride %r" % (st,))
+    if layout == TENSOR_PLANAR:
+        depth = shape[1] if len(shape) == 4 else 1
+        if (shape[-1], shape[-2], depth) != tuple(size):
+            raise ValueError("out_view %r does not have the window's shape %r" % (shape, tuple(size)))
+        if st[-1] != 1 and shape[-1] > 1:
+            raise ValueError("the columns of a planar view must be adjacent elements (strides %r)" % (st,))
+        row_pitch, slice_pitch, plane_pitch = st[-2], (st[1] if len(shape) == 4 else 0), st[0]
+    else:
+        depth = shape[0] if len(shape) == 4 else 1
+        if (shape[-2], shape[-3], depth) != tuple(size):
+            raise ValueError("out_view %r does not have the window's shape %r" % (shape, tuple(size)))
+        if (st[-1] != 1 and shape[-1] > 1) or (st[-2] != shape[-1] and shape[-2] > 1):
+            raise ValueError("the channels of an interleaved view must be adjacent and its columns C elements apart (strides %r)" % (st,))
+        row_pitch, slice_pitch, plane_pitch = st[-3], (st[0] if len(shape) == 4 else 0), 0
+    return TensorRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], size[2], flags, out_view.data_ptr(), row_pitch, slice_pitch, plane_pitch)
 
 
 class ErrorSums(C.Structure):
@@ -334,6 +388,10 @@ class Library:
             L.astcenc_amd_decompress_regions_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(DecodeRegion), C.c_uint,
                                                                 C.c_void_p]
             L.astcenc_amd_decompress_regions_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_decompress_tensors_device"):
+            L.astcenc_amd_decompress_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat),
+                                                                C.POINTER(TensorRegion), C.c_uint, C.c_void_p]
+            L.astcenc_amd_decompress_tensors_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_compare_blocks_device"):
             blocks_args = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(Swizzle),
                            C.c_void_p, C.c_size_t]
@@ -531,6 +589,16 @@ class Library:
         regions = [r if isinstance(r, DecodeRegion) else decode_region(*r) for r in regions]
         rarr = (DecodeRegion * len(regions))(*regions) if regions else None
         return self.lib.astcenc_amd_decompress_regions_device(ctx, arr, n, rarr, len(regions), s)
+
+    def decompress_tensors_device(self, ctx, entries, format, regions, stream=None):
+        """astcenc_amd_decompress_tensors_device: windows of the compressed images `entries` (see _set_args, compressed_entry)
+        decoded into tensors of `format` (a TensorFormat, see tensor_format).  regions: TensorRegion, or (entry, (x, y, z),
+        (size_x, size_y, size_z), out_view[, flip_x[, flip_y]]) tuples (see tensor_region; the view is read with the format's
+        layout)."""
+        arr, n, s = self._set_args(entries, stream)
+        regions = [r if isinstance(r, TensorRegion) else tensor_region(*r, layout=format.layout) for r in regions]
+        rarr = (TensorRegion * len(regions))(*regions) if regions else None
+        return self.lib.astcenc_amd_decompress_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None, rarr, len(regions), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

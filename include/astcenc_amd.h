@@ -143,6 +143,75 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_regions_device(
 	const struct astcenc_amd_decode_region* regions, unsigned int region_count,
 	void* hip_stream);
 
+/* Windows decoded straight into tensors: what astcenc_amd_decompress_regions_device decodes, converted, scaled, mirrored and
+ * laid out the way a training step computes on it -- a batch of crops as [N, 3, H, W] halves with mean and deviation folded in,
+ * every other sample mirrored -- in the same single launch, with no RGBA image in between.
+ *
+ * The format holds for the whole call. */
+enum astcenc_amd_tensor_type {
+	ASTCENC_AMD_TENSOR_F32 = 0,             /* IEEE binary32, 4 bytes an element */
+	ASTCENC_AMD_TENSOR_F16 = 1,             /* IEEE binary16, 2 bytes */
+	ASTCENC_AMD_TENSOR_BF16 = 2             /* bfloat16 (the upper half of a binary32), 2 bytes */
+};
+enum astcenc_amd_tensor_layout {
+	ASTCENC_AMD_TENSOR_PLANAR = 0,          /* C, D, H, W: a plane per channel */
+	ASTCENC_AMD_TENSOR_INTERLEAVED = 1      /* D, H, W, C: the channels of a texel side by side */
+};
+#define ASTCENC_AMD_TENSOR_FLIP_X 0x1u      /* the window's columns are written right to left */
+#define ASTCENC_AMD_TENSOR_FLIP_Y 0x2u      /* ... its rows bottom to top */
+
+struct astcenc_amd_tensor_format {
+	enum astcenc_amd_tensor_type type;
+	enum astcenc_amd_tensor_layout layout;
+	unsigned int channels;                  /* 1..4: components 0 .. channels - 1 of the swizzled texel become channels */
+	float scale[4], bias[4];                /* per output channel; the first `channels` of each are used and must be finite */
+};
+
+/* A region names a window of one entry and where it goes. */
+struct astcenc_amd_tensor_region {
+	unsigned int entry;                     /* index into entries[] */
+	unsigned int x, y, z;                   /* origin of the window in that image, texels */
+	unsigned int size_x, size_y, size_z;    /* its size, each >= 1 */
+	unsigned int flags;                     /* ASTCENC_AMD_TENSOR_FLIP_X | ASTCENC_AMD_TENSOR_FLIP_Y */
+	void* out;                              /* device pointer: element (c = 0, k = 0, j = 0, i = 0) */
+	size_t row_pitch, slice_pitch, plane_pitch;   /* in ELEMENTS of the format's type; 0 = tightly packed */
+};
+
+/* Decode regions[0 .. region_count) into tensors.  For position (i, j, k) of a region's window, 0 <= i < size_x, 0 <= j <
+ * size_y, 0 <= k < size_z, and channel c < format->channels:
+ *
+ *   Source.  s[0 .. 3] is the texel astcenc_amd_decompress_regions_device writes for that position of that entry: the entry's
+ *     data_type and swizzle (the Z swizzle and the constants 0 / 1 included), the context's profile, error blocks and
+ *     constant-colour blocks as there.  s[c] is converted to binary32 exactly: a U8 code v is (float)v, 0 .. 255 -- it is not
+ *     divided by 255, fold 1 / 255 into `scale`; an F16 value is widened; an F32 value is itself.  Entries of different data
+ *     types may share a call.
+ *   Arithmetic.  t = s[c] * scale[c] rounded to binary32, then y = t + bias[c] rounded to binary32: two IEEE operations, round
+ *     to nearest even, never fused, subnormal operands and results kept.  y is stored as the format's type: F32 as it is; F16
+ *     and BF16 rounded to nearest even, overflow to infinity, subnormals produced.  A NaN y of any sign and payload is stored
+ *     as the type's canonical quiet NaN: 0x7FC00000, 0x7E00, 0x7FC0.
+ *   Placement.  With i' = size_x - 1 - i under ASTCENC_AMD_TENSOR_FLIP_X and i otherwise, j' = size_y - 1 - j under
+ *     ASTCENC_AMD_TENSOR_FLIP_Y and j otherwise (z is never mirrored), the value is element
+ *       PLANAR:       c * plane_pitch + k * slice_pitch + j' * row_pitch + i'
+ *       INTERLEAVED:  k * slice_pitch + j' * row_pitch + i' * channels + c
+ *     of `out`, counted in elements of the format's type.  A zero pitch is the tight one: row_pitch = size_x (PLANAR) or
+ *     size_x * channels (INTERLEAVED); slice_pitch = row_pitch * size_y; plane_pitch = slice_pitch * size_z (PLANAR only).
+ *     No other element is written: not the padding of a pitch, not the unused channels of a wider tensor, not what lies
+ *     between the regions of one batch tensor.
+ *
+ *   - Entries, windows, the work-item bound, device ownership, the null / zero-count cases and the stream are those of
+ *     astcenc_amd_decompress_regions_device, with its error codes; everything is checked before anything is launched, a
+ *     failure returns its error with nothing written, and the log callback names the index of the region or entry.
+ *   - Also ASTCENC_ERR_BAD_PARAM: a null `format`; a type or layout that is not one of the above; `channels` outside 1..4; a
+ *     scale or bias among the first `channels` that is not finite; flag bits other than the two above; a non-zero pitch
+ *     below the tight one (formed and compared in 64 bits; a tensor extent that overflows them is an error); a non-zero
+ *     plane_pitch with INTERLEAVED; an `out` not aligned to the element size.  A null `out`: ASTCENC_ERR_BAD_CONTEXT. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_tensors_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_tensor_region* regions, unsigned int region_count,
+	void* hip_stream);
+
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
  *
  * Level i is max(1, dim_x >> i) x max(1, dim_y >> i) (the GL / Vulkan / KTX rule); level_count == 0 means the full chain down
