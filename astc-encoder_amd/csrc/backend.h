@@ -230,6 +230,18 @@ struct DecompressTensorsJob {
 	void*    stream;
 };
 int backend_decompress_tensors(Backend* b, const DecompressTensorsJob& job);
+/* astcenc_amd_decompress_scaled_tensors_device: the same with the call's filter and the regions as DecodeScaledLaunch. */
+struct DecodeScaledLaunch;
+struct DecompressScaledJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	uint32_t filter;                      // astcenc_amd_window_filter
+	const DecodeScaledLaunch* regions;
+	uint32_t region_count;
+	void*    stream;
+};
+int backend_decompress_scaled(Backend* b, const DecompressScaledJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -410,6 +422,24 @@ size_t astc_decode_tensors_bytes(uint32_t count);
 uint32_t astc_decode_tensors_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format,
                                    const DecodeTensorLaunch* regions, uint32_t count);
 int astc_decode_tensors_launch(const void* d_table, uint32_t runs, uint32_t type, uint32_t layout, void* stream);
+/* Scaled windows decoded into tensors (astcenc_amd_decompress_scaled_tensors_device; decode_scaled.h, kernel_decode_scaled.hip):
+ * the call's format and filter and one DecodeScaledLaunch per region, checked by the entry point -- 2D footprints, sizes
+ * 1 .. 65535, pitches in elements, resolved, at least the tight ones of the output.  A work item is a tile of a region's output
+ * (astc_decode_scaled_tiles of them: their width depends on the ratio, the entry's data type and the footprint); the table and the
+ * launch as above. */
+struct DecodeScaledLaunch {
+	uint32_t entry;
+	uint32_t x, y, z, size_x, size_y;     // the window; z: the slice
+	uint32_t out_x, out_y;                // what it becomes
+	uint32_t flags;                       // ASTCENC_AMD_TENSOR_FLIP_*
+	void*    d_out;                       // element (c = 0, j = 0, i = 0)
+	size_t   row_pitch, plane_pitch;
+};
+unsigned long long astc_decode_scaled_tiles(const DecodeScaledLaunch& r, uint32_t data_type, uint32_t block_x, uint32_t block_y);
+size_t astc_decode_scaled_bytes(uint32_t count);
+uint32_t astc_decode_scaled_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, uint32_t filter,
+                                  const DecodeScaledLaunch* regions, uint32_t count);
+int astc_decode_scaled_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -1589,10 +1589,11 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 	});
 }
 
-/* astcenc_amd_decompress_regions_device and astcenc_amd_decompress_tensors_device: as backend_decompress_set, with the regions'
- * table (decode_regions.h, decode_tensors.h) in place of the set's.  Only the entries a region names are looked at; their streams
- * and every region's buffer must be on the owner's device.  entry_of / out_of: region i's entry and buffer; table(d, out): the
- * table's bytes, or with `out` the table written there from the entries' launches `d`, returning its runs; launch: its kernel. */
+/* astcenc_amd_decompress_regions_device, astcenc_amd_decompress_tensors_device and astcenc_amd_decompress_scaled_tensors_device: as
+ * backend_decompress_set, with the regions' table (decode_regions.h, decode_tensors.h, decode_scaled.h) in place of the set's.
+ * Only the entries a region names are looked at; their streams and every region's buffer must be on the owner's device.
+ * entry_of / out_of: region i's entry and buffer; table(d, out): the table's bytes, or with `out` the table written there from
+ * the entries' launches `d`, returning its runs; launch: its kernel. */
 template <class EntryOf, class OutOf, class Table, class Launch>
 static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, uint32_t entry_count, uint32_t region_count, void* job_stream,
                               const char* what, EntryOf entry_of, OutOf out_of, Table table, Launch launch)
@@ -1654,6 +1655,17 @@ int backend_decompress_tensors(Backend* b, const DecompressTensorsJob& job)
 			return out ? astc_decode_tensors_build(out, d, job.entry_count, *job.format, job.regions, job.region_count) : astc_decode_tensors_bytes(job.region_count);
 		},
 		[&](const void* d_table, uint32_t runs, void* stream) { return astc_decode_tensors_launch(d_table, runs, job.format->type, job.format->layout, stream); });
+}
+
+int backend_decompress_scaled(Backend* b, const DecompressScaledJob& job)
+{
+	return decompress_windows(b, job.entries, job.entry_count, job.region_count, job.stream, "decode scaled tensors",
+		[&](uint32_t i) { return job.regions[i].entry; }, [&](uint32_t i) { return job.regions[i].d_out; },
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_scaled_build(out, d, job.entry_count, *job.format, job.filter, job.regions, job.region_count) : astc_decode_scaled_bytes(job.region_count);
+		},
+		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_scaled_launch(d_table, tiles, job.format->type, job.format->layout, stream); });
 }
 
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial

@@ -103,10 +103,12 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_block_list_device", "astcenc_amd_select_blocks_device",
                "astcenc_amd_compress_image_adaptive_device", "astcenc_amd_select_blocks_set_device",
                "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
-               "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device"]
+               "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
+               "astcenc_amd_decompress_scaled_tensors_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
+WINDOW_BILINEAR, WINDOW_BOX = 0, 1
 NO_BLOCK_BUDGET = 0xFFFFFFFF
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
@@ -255,6 +257,57 @@ def tensor_region(entry, origin, size, out_view, flip_x=False, flip_y=False, lay
     return TensorRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], size[2], flags, out_view.data_ptr(), row_pitch, slice_pitch, plane_pitch)
 
 
+class ScaledRegion(C.Structure):
+    """struct astcenc_amd_scaled_region (include/astcenc_amd.h)."""
+    _fields_ = [("entry", C.c_uint), ("x", C.c_uint), ("y", C.c_uint), ("z", C.c_uint),
+                ("size_x", C.c_uint), ("size_y", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint), ("flags", C.c_uint),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
+
+
+def scaled_region(entry, origin, size, out_view, flip_x=False, flip_y=False, layout=TENSOR_PLANAR, type=None):
+    """ScaledRegion of window `size` = (size_x, size_y) at `origin` = (x, y, z) of entry `entry`, resampled into the torch view
+    `out_view`: [C, H, W] for TENSOR_PLANAR, [H, W, C] for TENSOR_INTERLEAVED -- out_x, out_y are its W and H, pointer and pitches
+    (in elements) come from its strides.  ValueError for a view the layouts cannot express: not three dimensions, columns that
+    are not `1` (planar) or `C` (interleaved) elements apart, interleaved channels that are not adjacent, a negative stride, a
+    zero stride along an axis longer than one (an expanded view: its rows or planes alias each other, and a zero pitch means
+    `tightly packed` to the call), a size outside 1 .. 65535; with `type` (the format's TENSOR_*), also for a view of another
+    dtype.  Or an explicit (ptr, out_x, out_y, row_pitch, plane_pitch) in elements (0 = tightly packed)."""
+    flags = (TENSOR_FLIP_X if flip_x else 0) | (TENSOR_FLIP_Y if flip_y else 0)
+    if isinstance(out_view, tuple):
+        ptr, out_x, out_y, row_pitch, plane_pitch = out_view
+        return ScaledRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], out_x, out_y, flags, ptr, row_pitch, plane_pitch)
+    shape, st = tuple(out_view.shape), tuple(out_view.stride())
+    if out_view.dim() != 3:
+        raise ValueError("out_view has %d dimensions: [C, H, W] or [H, W, C]" % out_view.dim())
+    if any(v < 0 for v in st):
+        raise ValueError("out_view has a negative stride %r" % (st,))
+    if any(v == 0 and n > 1 for v, n in zip(st, shape)):
+        raise ValueError("out_view has a zero stride along an axis longer than one (shape %r, strides %r): its elements alias" % (shape, st))
+    if type is not None:
+        import torch
+        want = {TENSOR_F32: torch.float32, TENSOR_F16: torch.float16, TENSOR_BF16: torch.bfloat16}.get(type)
+        if out_view.dtype != want:
+            raise ValueError("out_view is %s, the format's type %r is %s" % (out_view.dtype, type, want))
+    if layout == TENSOR_PLANAR:
+        out_x, out_y = shape[2], shape[1]
+        if st[2] != 1 and out_x > 1:
+            raise ValueError("the columns of a planar view must be adjacent elements (strides %r)" % (st,))
+        row_pitch, plane_pitch = st[1], st[0]
+    else:
+        out_x, out_y = shape[1], shape[0]
+        if (st[2] != 1 and shape[2] > 1) or (st[1] != shape[2] and out_x > 1):
+            raise ValueError("the channels of an interleaved view must be adjacent and its columns C elements apart (strides %r)" % (st,))
+        row_pitch, plane_pitch = st[0], 0
+    if not (1 <= out_x <= 65535 and 1 <= out_y <= 65535 and 1 <= size[0] <= 65535 and 1 <= size[1] <= 65535):
+        raise ValueError("window %r to %r: every size is 1 .. 65535" % (tuple(size), (out_x, out_y)))
+    # (the stride of an axis of length one says nothing: the tight pitch)
+    if out_y == 1:
+        row_pitch = 0
+    if layout == TENSOR_PLANAR and shape[0] == 1:
+        plane_pitch = 0
+    return ScaledRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], out_x, out_y, flags, out_view.data_ptr(), row_pitch, plane_pitch)
+
+
 class ErrorSums(C.Structure):
     """struct astcenc_amd_error_sums (include/astcenc_amd.h)."""
     _fields_ = [("squared_error", C.c_double * 4), ("alpha_scaled_squared_error", C.c_double * 4),
@@ -392,6 +445,10 @@ class Library:
             L.astcenc_amd_decompress_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat),
                                                                 C.POINTER(TensorRegion), C.c_uint, C.c_void_p]
             L.astcenc_amd_decompress_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_decompress_scaled_tensors_device"):
+            L.astcenc_amd_decompress_scaled_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.c_int,
+                                                                       C.POINTER(ScaledRegion), C.c_uint, C.c_void_p]
+            L.astcenc_amd_decompress_scaled_tensors_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_compare_blocks_device"):
             blocks_args = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(Swizzle),
                            C.c_void_p, C.c_size_t]
@@ -599,6 +656,15 @@ class Library:
         regions = [r if isinstance(r, TensorRegion) else tensor_region(*r, layout=format.layout) for r in regions]
         rarr = (TensorRegion * len(regions))(*regions) if regions else None
         return self.lib.astcenc_amd_decompress_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None, rarr, len(regions), s)
+
+    def decompress_scaled_tensors_device(self, ctx, entries, format, filter, regions, stream=None):
+        """astcenc_amd_decompress_scaled_tensors_device: windows of the compressed images `entries` resampled with `filter`
+        (WINDOW_BILINEAR / WINDOW_BOX) into tensors of `format`.  regions: ScaledRegion, or (entry, (x, y, z), (size_x, size_y),
+        out_view[, flip_x[, flip_y]]) tuples (see scaled_region; the view is read with the format's layout and must have its type)."""
+        arr, n, s = self._set_args(entries, stream)
+        regions = [r if isinstance(r, ScaledRegion) else scaled_region(*r, layout=format.layout, type=format.type) for r in regions]
+        rarr = (ScaledRegion * len(regions))(*regions) if regions else None
+        return self.lib.astcenc_amd_decompress_scaled_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None, filter, rarr, len(regions), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

@@ -212,6 +212,85 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_tensors_device(
 	const struct astcenc_amd_tensor_region* regions, unsigned int region_count,
 	void* hip_stream);
 
+/* Scaled windows decoded straight into tensors: the random resized crop of a vision loader.  Every region takes a window of
+ * its own size and aspect ratio and resamples it to an output size of its own -- for a batch, one fixed size -- in the same
+ * single launch that decodes, normalises, mirrors and lays out; no image at the window's size exists in between.
+ *
+ * The filter holds for the whole call.  Both filters have taps that are exact rationals of three integers. */
+enum astcenc_amd_window_filter {
+	ASTCENC_AMD_WINDOW_BILINEAR = 0,        /* two taps an axis, half-texel centres */
+	ASTCENC_AMD_WINDOW_BOX = 1              /* exact area average */
+};
+
+struct astcenc_amd_scaled_region {
+	unsigned int entry;                     /* index into entries[] */
+	unsigned int x, y, z;                   /* origin of the window in that image, texels; z: the slice */
+	unsigned int size_x, size_y;            /* the window, each 1 .. 65535 */
+	unsigned int out_x, out_y;              /* what it becomes, each 1 .. 65535 */
+	unsigned int flags;                     /* ASTCENC_AMD_TENSOR_FLIP_X | ASTCENC_AMD_TENSOR_FLIP_Y */
+	void* out;                              /* device pointer: element (c = 0, j = 0, i = 0) */
+	size_t row_pitch, plane_pitch;          /* in ELEMENTS of the format's type; 0 = tightly packed */
+};
+
+/* Decode and resample regions[0 .. region_count) into tensors of `format` (astcenc_amd_decompress_tensors_device's: type,
+ * layout, channels, scale, bias).  For output position (i, j) of a region, 0 <= i < out_x, 0 <= j < out_y, and channel
+ * c < format->channels:
+ *
+ *   Taps.  Along each axis on its own, with S the window's size, D the output size and p the output position (i along x, j
+ *     along y), in integer arithmetic of 64 bits:
+ *       BILINEAR: n = (2p + 1) * S - D (signed); i0 = floor(n / 2D), f = n - i0 * 2D, so 0 <= f < 2D.  Tap 0 is source index
+ *         clamp(i0, 0, S - 1) with weight 2D - f; tap 1 is source index clamp(i0 + 1, 0, S - 1) with weight f; den = 2D.
+ *         Indices are counted from the window's origin and clamp at the WINDOW's edges, not the image's: the result is that
+ *         of cropping, then resizing.
+ *       BOX: a = p * S, b = (p + 1) * S; the taps are the source indices k = a / D .. (b - 1) / D (integer divisions), tap k
+ *         has weight min(b, (k + 1) * D) - max(a, k * D), which is at least 1; den = S.
+ *     A tap of weight 0 (BILINEAR's tap 1 when f = 0) is not part of any sum and its texel is not read into one: a NaN or an
+ *     infinity there does not reach the result.  (BILINEAR, S = 2, D = 3: texel 0, (t0 + t1) / 2, texel 1.  BOX, S = 3, D = 2:
+ *     (2 t0 + t1) / 3, (t1 + 2 t2) / 3.)
+ *   Source.  v(kx, ky)[c] is component c of the texel astcenc_amd_decompress_regions_device writes for position (kx, ky) of
+ *     the window at slice z: the entry's data_type and swizzle, the context's profile, error blocks and constant-colour blocks
+ *     as there.  The filter works on those stored values as they are: no sRGB linearisation and no alpha weighting is done.
+ *     Entries of different data types may share a call.
+ *       v is widened to binary64 (exact for U8 codes 0 .. 255, F16 and F32 values).  Per source row ky that has a y tap:
+ *         r(ky) = sum over the x taps, in increasing tap order, of (double)wx * v(kx, ky)[c];
+ *       then acc = sum over the y taps, in increasing tap order, of (double)wy * r(ky).  A sum starts as its first product
+ *       (nothing is added to a zero); every product and every sum is one IEEE binary64 operation, round to nearest even,
+ *       never fused.  s[c] = (float)(acc / ((double)den_x * (double)den_y)): one binary64 division, one rounding to binary32.
+ *       For U8 entries every product and sum is an integer below 2^42, exact in binary64: acc is the integer
+ *       N = sum wy * (sum wx * v), and s[c] is N / (den_x * den_y) correctly rounded to binary64, then to binary32.
+ *   Arithmetic, storage.  Those of astcenc_amd_decompress_tensors_device: t = s[c] * scale[c], y = t + bias[c], two binary32
+ *     roundings; F32 / F16 / BF16 round to nearest even; a NaN y is stored as the type's canonical quiet NaN.
+ *   Placement.  The flips apply to the OUTPUT position: i' = out_x - 1 - i under ASTCENC_AMD_TENSOR_FLIP_X and i otherwise,
+ *     j' = out_y - 1 - j under ASTCENC_AMD_TENSOR_FLIP_Y and j otherwise; the value is element
+ *       PLANAR:       c * plane_pitch + j' * row_pitch + i'
+ *       INTERLEAVED:  j' * row_pitch + i' * channels + c
+ *     of `out`.  A zero pitch is the tight one: row_pitch = out_x (PLANAR) or out_x * channels (INTERLEAVED); plane_pitch =
+ *     row_pitch * out_y (PLANAR only).  No other element is written.
+ *
+ *   Consequence: with out_x = size_x and out_y = size_y either filter writes bit for bit what
+ *   astcenc_amd_decompress_tensors_device writes for the same window (size_z = 1): every position has one tap of weight den
+ *   per axis (BOX: one tap of weight S = den; BILINEAR: f = 0), so a U8 sum is den_x * den_y times the code, and a float sum
+ *   lies within a binary64 rounding or two of den_x * den_y times a value that is exactly a binary32.
+ *
+ *   - 2D footprints only: z selects an array slice and nothing is resampled along z.  A context whose footprint is 3D
+ *     (block_z > 1) returns ASTCENC_ERR_BAD_PARAM.
+ *   - Entries, the window inside the image (z included), device ownership, the null / zero-count cases, the alignment of `out`,
+ *     flag bits, pitches below the tight ones (of the OUTPUT size), a plane_pitch with INTERLEAVED, the format and the stream
+ *     are checked as in astcenc_amd_decompress_tensors_device, with its error codes; everything is checked before anything is
+ *     launched, a failure returns its error with nothing written, and the log callback names the index of the region or entry.
+ *   - Also ASTCENC_ERR_BAD_PARAM: a filter that is not one of the above; a size_x, size_y, out_x or out_y that is zero or above
+ *     65535; more than 2^32 - 1 work items in all.  A work item is a tile of one region's output: up to 64 output columns by
+ *     up to 8 output rows -- fewer columns, down to 8, where the window is reduced so strongly that the taps of 64 columns reach
+ *     more blocks than are decoded at once -- so a region has at most ceil(out_x / 8) * ceil(out_y / min(out_y, 8)) of them.  A
+ *     tile decodes the blocks its taps reach; blocks at the seams of tiles are decoded by each tile that needs them. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_scaled_tensors_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	enum astcenc_amd_window_filter filter,
+	const struct astcenc_amd_scaled_region* regions, unsigned int region_count,
+	void* hip_stream);
+
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
  *
  * Level i is max(1, dim_x >> i) x max(1, dim_y >> i) (the GL / Vulkan / KTX rule); level_count == 0 means the full chain down
