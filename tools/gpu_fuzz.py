@@ -84,12 +84,28 @@ while time.time() - t0 < BUDGET:
         cfg.tune_3partition_index_limit = int(rng.integers(1, 120))
         cfg.tune_4partition_index_limit = int(rng.integers(1, 80))
         cfg.tune_block_mode_limit = int(rng.integers(1, 101))
-        cfg.tune_2partitioning_candidate_limit = int(rng.integers(1, 5))
-        cfg.tune_3partitioning_candidate_limit = int(rng.integers(1, 5))
-        cfg.tune_4partitioning_candidate_limit = int(rng.integers(1, 5))
+        cfg.tune_2partitioning_candidate_limit = int(rng.integers(1, 9))
+        cfg.tune_3partitioning_candidate_limit = int(rng.integers(1, 9))
+        cfg.tune_4partitioning_candidate_limit = int(rng.integers(1, 9))
         cfg.tune_db_limit = float(rng.choice([0.0, 30.0, 45.0, 200.0]))
+        cfg.tune_mse_overshoot = float(rng.choice([1.0, 2.0, 3.5, 10.0]))
+        cfg.tune_2partition_early_out_limit_factor = float(rng.choice([0.0, 0.5, 1.2, 2.0, 1e9]))
+        cfg.tune_3partition_early_out_limit_factor = float(rng.choice([0.0, 0.5, 1.2, 2.0, 1e9]))
         cfg.tune_2plane_early_out_limit_correlation = float(rng.choice([0.5, 0.8, 0.99, 1.0]))
-        cfg.tune_search_mode0_enable = float(rng.choice([0.0, 1.0]))
+        cfg.tune_search_mode0_enable = float(rng.choice([0.0, 0.84, 0.86, 1.0]))
+        if flags & A.FLG_MAP_RGBM:
+            cfg.rgbm_m_scale = float(rng.choice([1.0, 3.0, 5.0, 20.0]))
+        if rng.random() < 0.1:
+            # outside the valid ranges, where both libraries clamp (validate_config); NaN and +inf in the float fields
+            for field in ("tune_partition_count_limit", "tune_2partition_index_limit", "tune_3partition_index_limit", "tune_4partition_index_limit",
+                          "tune_block_mode_limit", "tune_refinement_limit", "tune_candidate_limit", "tune_2partitioning_candidate_limit",
+                          "tune_3partitioning_candidate_limit", "tune_4partitioning_candidate_limit"):
+                if rng.random() < 0.4:
+                    setattr(cfg, field, int(rng.choice([0, 9, 13, 250, 5000])))
+            for field in ("tune_db_limit", "tune_mse_overshoot", "tune_2partition_early_out_limit_factor",
+                          "tune_3partition_early_out_limit_factor", "tune_2plane_early_out_limit_correlation", "tune_search_mode0_enable", "rgbm_m_scale"):
+                if rng.random() < 0.4:
+                    setattr(cfg, field, float(rng.choice([-1.0, 0.5, np.nan, np.inf])))
     if not is3d and pixels.ndim == 3 and rng.random() < 0.15:
         cfg.a_scale_radius = int(rng.integers(1, 12))
     want = run(ref, cfg, pixels, swz, threads)
