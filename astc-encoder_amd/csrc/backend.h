@@ -242,6 +242,19 @@ struct DecompressScaledJob {
 	void*    stream;
 };
 int backend_decompress_scaled(Backend* b, const DecompressScaledJob& job);
+/* astcenc_amd_sample_tensors_device: the same with the call's sampler and the grids as DecodeSampleLaunch. */
+struct DecodeSampler;
+struct DecodeSampleLaunch;
+struct DecompressSampleJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	const DecodeSampler* sampler;
+	const DecodeSampleLaunch* grids;
+	uint32_t grid_count;
+	void*    stream;
+};
+int backend_decompress_sample(Backend* b, const DecompressSampleJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -440,6 +453,27 @@ size_t astc_decode_scaled_bytes(uint32_t count);
 uint32_t astc_decode_scaled_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, uint32_t filter,
                                   const DecodeScaledLaunch* regions, uint32_t count);
 int astc_decode_scaled_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
+/* Images sampled at coordinates into tensors (astcenc_amd_sample_tensors_device; decode_sample.h, kernel_decode_sample.hip): the
+ * call's format and sampler and one DecodeSampleLaunch per grid, checked by the entry point -- 2D footprints, sizes 1 .. 65535,
+ * pitches resolved (not 0), at least the tight ones, the coordinates aligned to a pair.  A work item is a tile of 64 points of a
+ * grid (astc_decode_sample_tiles of them); the table and the launch as above. */
+struct DecodeSampler {
+	uint32_t filter, address_x, address_y;    // astcenc_amd_sample_filter / _address
+};
+struct DecodeSampleLaunch {
+	uint32_t entry;
+	uint32_t z;                           // the slice
+	uint32_t out_x, out_y;                // points per row, rows of points
+	const float* d_coords;                // point (i, j): d_coords[j * coord_row_pitch + 2 i], x then y
+	size_t   coord_row_pitch;             // floats
+	void*    d_out;                       // element (c = 0, j = 0, i = 0)
+	size_t   row_pitch, plane_pitch;
+};
+unsigned long long astc_decode_sample_tiles(uint32_t out_x, uint32_t out_y);
+size_t astc_decode_sample_bytes(uint32_t count);
+uint32_t astc_decode_sample_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeSampler& sampler,
+                                  const DecodeSampleLaunch* grids, uint32_t count);
+int astc_decode_sample_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -1592,11 +1592,11 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 /* astcenc_amd_decompress_regions_device, astcenc_amd_decompress_tensors_device and astcenc_amd_decompress_scaled_tensors_device: as
  * backend_decompress_set, with the regions' table (decode_regions.h, decode_tensors.h, decode_scaled.h) in place of the set's.
  * Only the entries a region names are looked at; their streams and every region's buffer must be on the owner's device.
- * entry_of / out_of: region i's entry and buffer; table(d, out): the table's bytes, or with `out` the table written there from
+ * entry_of / out_of: region i's entry and buffer (with `buffers` of them a region, buffer i belongs to region i / buffers); table(d, out): the table's bytes, or with `out` the table written there from
  * the entries' launches `d`, returning its runs; launch: its kernel. */
 template <class EntryOf, class OutOf, class Table, class Launch>
 static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, uint32_t entry_count, uint32_t region_count, void* job_stream,
-                              const char* what, EntryOf entry_of, OutOf out_of, Table table, Launch launch)
+                              const char* what, EntryOf entry_of, OutOf out_of, Table table, Launch launch, uint32_t buffers = 1)
 {
 	std::vector<uint8_t> used(entry_count, 0);
 	for (uint32_t i = 0; i < region_count; i++) used[entry_of(i)] = 1;
@@ -1615,10 +1615,10 @@ static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, ui
 				log_msg("%s: the blocks of entry %u are not on device %d, which owns entry 0's", what, e, s->device);
 				return 3;
 			}
-		for (uint32_t i = 0; i < region_count; i++)
+		for (uint32_t i = 0; i < region_count * buffers; i++)
 			if (foreign(out_of(i)))
 			{
-				log_msg("%s: the buffer of region %u is not on device %d, which owns entry 0's blocks", what, i, s->device);
+				log_msg("%s: the buffer of region %u is not on device %d, which owns entry 0's blocks", what, i / buffers, s->device);
 				return 3;
 			}
 		std::vector<DecodeLaunch> d(entry_count);
@@ -1666,6 +1666,19 @@ int backend_decompress_scaled(Backend* b, const DecompressScaledJob& job)
 			return out ? astc_decode_scaled_build(out, d, job.entry_count, *job.format, job.filter, job.regions, job.region_count) : astc_decode_scaled_bytes(job.region_count);
 		},
 		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_scaled_launch(d_table, tiles, job.format->type, job.format->layout, stream); });
+}
+
+/* (the coordinates are checked with the outputs: both are buffers of the grid) */
+int backend_decompress_sample(Backend* b, const DecompressSampleJob& job)
+{
+	return decompress_windows(b, job.entries, job.entry_count, job.grid_count, job.stream, "sample tensors",
+		[&](uint32_t i) { return job.grids[i].entry; },
+		[&](uint32_t i) { return (i & 1u) ? static_cast<const void*>(job.grids[i >> 1].d_coords) : static_cast<const void*>(job.grids[i >> 1].d_out); },
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_sample_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_sample_bytes(job.grid_count);
+		},
+		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_sample_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 2u);
 }
 
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial

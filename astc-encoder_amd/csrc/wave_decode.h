@@ -1296,15 +1296,24 @@ WV_FN void decode_row_texels(const DecodeImage& img, uint32_t bx0, uint32_t by, 
 	}
 }
 
-/* Decode blocks bx0 .. bx0 + count - 1 (count <= DECODE_BATCH) of block row `by`, layer `bz` of the stream into the image
- * -- with a window (`win`, see DecodeWhole / DecodeWindow above) the texels of those blocks that lie inside it, into its buffer.
- * All 64 lanes call this.  The arithmetic, block by block, is that of the single-block routines above (parse_block_header,
- * unpack_block_payload, infill_texel_weights: what astcenc_get_block_info runs on the host). */
-template <class Sink, class Window = DecodeWhole>
-WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink, const Window win = Window())
+/* Which blocks of the stream a batch holds: slot k (0 <= k < count) is block at(k), counted in blocks from the stream's start.
+ * DecodeRunBlocks is the decoder's: consecutive blocks of one block row from `first` on.  (decode_sample.h has a list.) */
+struct DecodeRunBlocks {
+	size_t first;
+	WV_FN size_t operator()(int k) const { return first + (size_t)k; }
+};
+
+/* What the texel phases need to know about a decoded batch (wave-uniform): it has blocks with more than one partition, with
+ * three or four, with two weight planes, with a texel that does not leave as an integer-built RGBA8 pixel. */
+struct DecodeBatchKinds { bool any_multi, any_many, any_dual, any_general; };
+
+/* The phases in front of the texels -- headers and constant colours, weights, colour values, endpoints -- of the `count` blocks
+ * (count <= DECODE_BATCH) that `at` names, into the batch scratch.  All 64 lanes call this.  (Always inlined, like the texel
+ * body below: decode_row_batch is then the one body it was, in every kernel that holds it.) */
+template <class Blocks>
+__attribute__((always_inline)) WV_FN DecodeBatchKinds decode_batch_blocks(const DecodeImage& img, const uint8_t* blocks, const Blocks at, int count, DecodeBatch& s)
 {
 	const int block_x = (int)img.block_x, block_y = (int)img.block_y, block_z = (int)img.block_z;
-	const int T = block_x * block_y * block_z;
 	const int profile = (int)img.profile;
 	const bool u8_out = img.data_type == 0 || profile == 0;        // (ref: get_u8_component_mask)
 	const float error_nan = int_as_float((int)0xFFFFE000u);
@@ -1313,7 +1322,6 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 	// reference's route, astcenc_image.cpp:345-420 after decompress_symbolic.cpp:66-120), so the texel is built
 	// from integers alone; LNS (HDR) endpoints and the Z swizzle take the general route.
 	const bool bytes_swz = img.data_type == 0 && img.swz[0] < 6 && img.swz[1] < 6 && img.swz[2] < 6 && img.swz[3] < 6;
-	const size_t first = ((size_t)bz * img.blocks_y + by) * img.blocks_x + bx0;
 
 	// ---- headers and constant colours: one lane per block ----
 	bool multi_part = false, many_part = false, dual_part = false;      // per-lane partials, folded below
@@ -1322,7 +1330,7 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 		// (every lane loads a block -- the lanes past the run's last block that one again -- and its share of the weight
 		//  unquantization table the wave keeps in LDS, so that all these loads are in flight together)
 		Bits128 blk;
-		const uint32_t* p = reinterpret_cast<const uint32_t*>(blocks + (first + (size_t)i_min(k, count - 1)) * 16);
+		const uint32_t* p = reinterpret_cast<const uint32_t*>(blocks + at(i_min(k, count - 1)) * 16);
 		blk.w[0] = p[0]; blk.w[1] = p[1]; blk.w[2] = p[2]; blk.w[3] = p[3];
 		{
 			const uint32_t t0 = weight_unquant_lut_word(k), t1 = weight_unquant_lut_word(64 + (k & 31));
@@ -1524,6 +1532,57 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 	}
 	const bool any_general = wv_any(general_part);
 	WV_SYNC();
+	const DecodeBatchKinds kinds = { any_multi, any_many, any_dual, any_general };
+	return kinds;
+}
+
+/* Texel (tx, ty, tz) of the block in slot k of a decoded batch, to the sink: weights infilled from the grid, the partition from
+ * the hash, the endpoints interpolated, then the integer-built RGBA8 pixel or store_texel_general.  block_z: img.block_z (a
+ * caller that knows it passes a constant); small_block, swz_sel: of the footprint and of img.swz; `at`, `lane`: handed to the sink. */
+template <class Sink>
+WV_FN void decode_batch_texel(const DecodeImage& img, const DecodeBatch& s, int k, int block_z, int tx, int ty, int tz, bool small_block, uint32_t swz_sel, size_t at,
+                              Sink& sink, int lane)
+{
+	const uint32_t ra = s.rec[k][0], rc = s.rec[k][2];
+	const bool fast = img.data_type == 0 && (ra & 8u) != 0u;
+	uint32_t px = s.rec[k][3];
+	int cv[4] = { 0, 0, 0, 0 };
+	int p = 0;
+	if (!(ra & 1u))
+	{
+		const bool dual = (rc & 0x1000u) != 0u;
+		const int parts = (int)((rc >> 13) & 7u);
+		const int plane2 = dual ? (int)((rc >> 16) & 3u) : -1;
+		int wp[2];
+		infill_texel_weights((int)(rc & 15u), (int)((rc >> 4) & 15u), (int)((rc >> 8) & 15u), dual, s.weights[k], s.weights[k] + (dual ? 1 : 0), dual ? 2 : 1,
+		                     (int)img.ds, (int)img.dt, (int)img.dr, block_z, tx, ty, tz, wp);
+		if (parts > 1)
+		{
+			PartitionHash ph;
+			for (int q = 0; q < 4; q++) ph.term[q] = s.hash[k][q];
+			p = partition_from_hash(ph, tx, ty, tz, small_block);
+		}
+		uint32_t x[4];
+		for (int q = 0; q < 4; q++) x[q] = lerp_terms(s.ep[k][p * 4 + q], lerp_weight_pair(q == plane2 ? wp[1] : wp[0]));
+		if (fast) px = pixel_from_lerps(swz_sel, x);
+		else for (int q = 0; q < 4; q++) cv[q] = (int)(x[q] >> 8);
+	}
+	if (fast) sink.pixel(img, lane, at, px);
+	else store_texel_general(img, s, k, ra, p, cv, at, sink, lane);
+}
+
+/* Decode blocks bx0 .. bx0 + count - 1 (count <= DECODE_BATCH) of block row `by`, layer `bz` of the stream into the image
+ * -- with a window (`win`, see DecodeWhole / DecodeWindow above) the texels of those blocks that lie inside it, into its buffer.
+ * All 64 lanes call this.  The arithmetic, block by block, is that of the single-block routines above (parse_block_header,
+ * unpack_block_payload, infill_texel_weights: what astcenc_get_block_info runs on the host). */
+template <class Sink, class Window = DecodeWhole>
+WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint32_t bx0, uint32_t by, uint32_t bz, int count, DecodeBatch& s, Sink& sink, const Window win = Window())
+{
+	const int block_x = (int)img.block_x, block_y = (int)img.block_y, block_z = (int)img.block_z;
+	const int T = block_x * block_y * block_z;
+	const DecodeRunBlocks run = { ((size_t)bz * img.blocks_y + by) * img.blocks_x + bx0 };
+	const DecodeBatchKinds kinds = decode_batch_blocks(img, blocks, run, count, s);
+	const bool any_multi = kinds.any_multi, any_many = kinds.any_many, any_dual = kinds.any_dual, any_general = kinds.any_general;
 
 	// ---- texels ----
 	if (block_z == 1)
@@ -1568,32 +1627,7 @@ WV_FN void decode_row_batch(const DecodeImage& img, const uint8_t* blocks, uint3
 				if (xi >= img.dim_x || yi >= img.dim_y || zi >= img.dim_z || !win.has(xi, yi, zi)) continue;
 				// (the decoder's index spelled out: formed through the policy's member, the same expression moved a handful of the kernels' instructions)
 				const size_t at = Window::whole ? (((size_t)zi * img.dim_y + yi) * img.dim_x + xi) * 4 : win.at(img, xi, yi, zi);
-				const uint32_t ra = s.rec[k][0], rc = s.rec[k][2];
-				const bool fast = img.data_type == 0 && (ra & 8u) != 0u;
-				uint32_t px = s.rec[k][3];
-				int cv[4] = { 0, 0, 0, 0 };
-				int p = 0;
-				if (!(ra & 1u))
-				{
-					const bool dual = (rc & 0x1000u) != 0u;
-					const int parts = (int)((rc >> 13) & 7u);
-					const int plane2 = dual ? (int)((rc >> 16) & 3u) : -1;
-					int wp[2];
-					infill_texel_weights((int)(rc & 15u), (int)((rc >> 4) & 15u), (int)((rc >> 8) & 15u), dual, s.weights[k], s.weights[k] + (dual ? 1 : 0), dual ? 2 : 1,
-					                     (int)img.ds, (int)img.dt, (int)img.dr, block_z, tx, ty, tz, wp);
-					if (parts > 1)
-					{
-						PartitionHash ph;
-						for (int q = 0; q < 4; q++) ph.term[q] = s.hash[k][q];
-						p = partition_from_hash(ph, tx, ty, tz, small_block);
-					}
-					uint32_t x[4];
-					for (int q = 0; q < 4; q++) x[q] = lerp_terms(s.ep[k][p * 4 + q], lerp_weight_pair(q == plane2 ? wp[1] : wp[0]));
-					if (fast) px = pixel_from_lerps(swz_sel, x);
-					else for (int q = 0; q < 4; q++) cv[q] = (int)(x[q] >> 8);
-				}
-				if (fast) sink.pixel(img, l, at, px);
-				else store_texel_general(img, s, k, ra, p, cv, at, sink, l);
+				decode_batch_texel(img, s, k, block_z, tx, ty, tz, small_block, swz_sel, at, sink, l);
 			}
 			sink.trip_end(j0, T, count);
 		}

@@ -104,11 +104,13 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_image_adaptive_device", "astcenc_amd_select_blocks_set_device",
                "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
                "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
-               "astcenc_amd_decompress_scaled_tensors_device"]
+               "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
 WINDOW_BILINEAR, WINDOW_BOX = 0, 1
+SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
+ADDRESS_CLAMP, ADDRESS_REPEAT, ADDRESS_MIRROR, ADDRESS_BORDER = 0, 1, 2, 3
 NO_BLOCK_BUDGET = 0xFFFFFFFF
 OPT_PER_SLICE_FAST_LOAD = 1
 MAX_MIP_LEVELS = 32
@@ -308,6 +310,51 @@ def scaled_region(entry, origin, size, out_view, flip_x=False, flip_y=False, lay
     return ScaledRegion(entry, origin[0], origin[1], origin[2], size[0], size[1], out_x, out_y, flags, out_view.data_ptr(), row_pitch, plane_pitch)
 
 
+class Sampler(C.Structure):
+    """struct astcenc_amd_sampler (include/astcenc_amd.h): SAMPLE_* filter, ADDRESS_* mode per axis."""
+    _fields_ = [("filter", C.c_int), ("address_x", C.c_int), ("address_y", C.c_int)]
+
+
+class SampleGrid(C.Structure):
+    """struct astcenc_amd_sample_grid (include/astcenc_amd.h)."""
+    _fields_ = [("entry", C.c_uint), ("z", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint),
+                ("coords", C.c_void_p), ("coord_row_pitch", C.c_size_t),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
+
+
+def sample_grid(entry, z, coords, out_view, layout=TENSOR_PLANAR, type=None):
+    """SampleGrid of slice `z` of entry `entry`: `coords` is a float32 torch tensor [H, W, 2] of (x, y) pairs in texel units,
+    `out_view` the torch view [C, H, W] for TENSOR_PLANAR or [H, W, C] for TENSOR_INTERLEAVED the points are written to;
+    pointers and pitches (in floats / elements) come from the strides.  ValueError for what the call cannot express: coordinates
+    that are not float32, not [H, W, 2], whose pairs are not adjacent or not two floats apart, whose rows are an odd number of
+    floats apart or which do not start on 8 bytes; an output of another H, W; the views scaled_region rejects (not three
+    dimensions, columns not `1` / `C` elements apart, channels not adjacent, negative or aliasing zero strides, a size outside
+    1 .. 65535, with `type` another dtype).  Or explicit tuples: coords = (ptr, out_x, out_y, coord_row_pitch) and out_view =
+    (ptr, row_pitch, plane_pitch)."""
+    if isinstance(coords, tuple):
+        cptr, out_x, out_y, coord_row_pitch = coords
+        optr, row_pitch, plane_pitch = out_view
+        return SampleGrid(entry, z, out_x, out_y, cptr, coord_row_pitch, optr, row_pitch, plane_pitch)
+    import torch
+    if coords.dtype != torch.float32:
+        raise ValueError("coords is %s: float32 pairs" % coords.dtype)
+    cshape, cst = tuple(coords.shape), tuple(coords.stride())
+    if coords.dim() != 3 or cshape[2] != 2:
+        raise ValueError("coords has shape %r: [H, W, 2]" % (cshape,))
+    if cst[2] != 1 or (cst[1] != 2 and cshape[1] > 1) or cst[0] < 0 or (cst[0] == 0 and cshape[0] > 1) or cst[0] % 2 != 0:
+        raise ValueError("the pairs of coords must be adjacent floats, two floats apart, its rows an even number of floats apart (strides %r)" % (cst,))
+    if coords.data_ptr() % 8 != 0:
+        raise ValueError("coords does not start on 8 bytes")
+    # (the output's checks are scaled_region's: a window of 1 x 1 stands in for the one this call does not have)
+    r = scaled_region(entry, (0, 0, z), (1, 1), out_view, layout=layout, type=type)
+    if (r.out_x, r.out_y) != (cshape[1], cshape[0]):
+        raise ValueError("out_view is %u x %u points, coords %u x %u" % (r.out_x, r.out_y, cshape[1], cshape[0]))
+    coord_row_pitch = cst[0] if cshape[0] > 1 else 0
+    if coord_row_pitch != 0 and coord_row_pitch < 2 * cshape[1]:
+        raise ValueError("the rows of coords overlap (strides %r)" % (cst,))
+    return SampleGrid(entry, z, r.out_x, r.out_y, coords.data_ptr(), coord_row_pitch, r.out, r.row_pitch, r.plane_pitch)
+
+
 class ErrorSums(C.Structure):
     """struct astcenc_amd_error_sums (include/astcenc_amd.h)."""
     _fields_ = [("squared_error", C.c_double * 4), ("alpha_scaled_squared_error", C.c_double * 4),
@@ -449,6 +496,10 @@ class Library:
             L.astcenc_amd_decompress_scaled_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.c_int,
                                                                        C.POINTER(ScaledRegion), C.c_uint, C.c_void_p]
             L.astcenc_amd_decompress_scaled_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_sample_tensors_device"):
+            L.astcenc_amd_sample_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(Sampler),
+                                                            C.POINTER(SampleGrid), C.c_uint, C.c_void_p]
+            L.astcenc_amd_sample_tensors_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_compare_blocks_device"):
             blocks_args = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.POINTER(Swizzle),
                            C.c_void_p, C.c_size_t]
@@ -665,6 +716,18 @@ class Library:
         regions = [r if isinstance(r, ScaledRegion) else scaled_region(*r, layout=format.layout, type=format.type) for r in regions]
         rarr = (ScaledRegion * len(regions))(*regions) if regions else None
         return self.lib.astcenc_amd_decompress_scaled_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None, filter, rarr, len(regions), s)
+
+    def sample_tensors_device(self, ctx, entries, format, sampler, grids, stream=None):
+        """astcenc_amd_sample_tensors_device: the compressed images `entries` sampled at coordinates into tensors of `format`.
+        sampler: a Sampler, or a (filter, address_x, address_y) tuple of SAMPLE_* / ADDRESS_* constants.  grids: SampleGrid, or
+        (entry, z, coords, out_view) tuples (see sample_grid; the view is read with the format's layout and must have its type)."""
+        arr, n, s = self._set_args(entries, stream)
+        if sampler is not None and not isinstance(sampler, Sampler):
+            sampler = Sampler(*sampler)
+        grids = [g if isinstance(g, SampleGrid) else sample_grid(*g, layout=format.layout, type=format.type) for g in grids]
+        garr = (SampleGrid * len(grids))(*grids) if grids else None
+        return self.lib.astcenc_amd_sample_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
+                                                          C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

@@ -291,6 +291,100 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_decompress_scaled_tensors_device(
 	const struct astcenc_amd_scaled_region* regions, unsigned int region_count,
 	void* hip_stream);
 
+/* Compressed images sampled at arbitrary coordinates straight into tensors: what a texture unit does -- "the filtered texel at
+ * (x, y)" for a buffer of coordinates: the UV buffer of a rasteriser or ray caster, a warp field, a rotated or perspective
+ * crop, torch.nn.functional.grid_sample -- with the image staying compressed.  A grid is out_y rows of out_x points; a grid of
+ * one row is a plain list of points.
+ *
+ * The sampler holds for the whole call. */
+enum astcenc_amd_sample_filter {
+	ASTCENC_AMD_SAMPLE_NEAREST = 0,         /* the texel the point lies in */
+	ASTCENC_AMD_SAMPLE_BILINEAR = 1         /* the four texels whose centres surround the point */
+};
+enum astcenc_amd_sample_address {
+	ASTCENC_AMD_ADDRESS_CLAMP = 0,          /* a tap outside the image reads the nearest edge texel */
+	ASTCENC_AMD_ADDRESS_REPEAT = 1,         /* the image tiles the plane */
+	ASTCENC_AMD_ADDRESS_MIRROR = 2,         /* ... every other tile mirrored */
+	ASTCENC_AMD_ADDRESS_BORDER = 3          /* a tap outside the image is +0.0 in every channel */
+};
+struct astcenc_amd_sampler {
+	enum astcenc_amd_sample_filter filter;
+	enum astcenc_amd_sample_address address_x, address_y;
+};
+
+struct astcenc_amd_sample_grid {
+	unsigned int entry;                     /* index into entries[] */
+	unsigned int z;                         /* the slice */
+	unsigned int out_x, out_y;              /* points per row / rows of points, each 1 .. 65535 */
+	const float* coords;                    /* device pointer: point (i, j) is the pair at coords[j * coord_row_pitch + 2 * i], x then y */
+	size_t coord_row_pitch;                 /* in floats, even; 0 = 2 * out_x */
+	void* out;                              /* device pointer: element (c = 0, j = 0, i = 0) */
+	size_t row_pitch, plane_pitch;          /* in ELEMENTS of the format's type; 0 = tightly packed */
+};
+
+/* Sample grids[0 .. grid_count) into tensors of `format` (astcenc_amd_decompress_tensors_device's: type, layout, channels,
+ * scale, bias).  For point (i, j) of a grid, 0 <= i < out_x, 0 <= j < out_y, with the coordinates (x, y) read from `coords`,
+ * and channel c < format->channels (integers are unbounded and reals are IEEE binary64 below, unless said otherwise):
+ *
+ *   Coordinates.  x and y are binary32 in texel units of the entry's image of W x H texels: texel k covers [k, k + 1) and its
+ *     centre is k + 0.5.  Any normalisation is the caller's: torch's grid_sample with align_corners=False has g in [-1, 1] and
+ *     x = (g + 1) * W / 2.  A point is VALID when both coordinates are finite and no larger than 2^30 in magnitude (2^30 itself
+ *     is valid).  An invalid point has s[c] = +0.0 for every channel and then goes through "Arithmetic, storage" like any other.
+ *   Taps.  Along each axis on its own, with S the image's size along it (W or H) and u the coordinate widened to binary64:
+ *       NEAREST: one tap, index floor(u), weight 1.
+ *       BILINEAR: t = u - 0.5 (one binary64 subtraction), i0 = floor(t), f = t - i0 (exact).  Tap 0 is index i0 with weight
+ *         1.0 - f (one binary64 subtraction); tap 1 is index i0 + 1 with weight f.
+ *     A tap of weight 0 (BILINEAR's tap 1 when f = 0) is not part of any sum and its texel is not read into one: a NaN or an
+ *     infinity there does not reach the result -- the rule of astcenc_amd_decompress_scaled_tensors_device.
+ *   Addressing of a tap index i, by the sampler's mode for that axis; the edges are the image's:
+ *       CLAMP:  min(max(i, 0), S - 1).
+ *       REPEAT: i mod S, the non-negative remainder.
+ *       MIRROR: m = i mod 2S (non-negative); m when m < S, else 2S - 1 - m.
+ *       BORDER: i when 0 <= i <= S - 1; a tap outside (on either axis) has the value +0.0 in every channel and IS part of the sum.
+ *   Source.  v(kx, ky)[c] is component c of the texel astcenc_amd_decompress_regions_device writes for (kx, ky, z) of that entry:
+ *     the entry's data_type and swizzle (the Z swizzle and the constants included), the context's profile, error blocks and
+ *     constant-colour blocks as there; widened to binary64 (exact for U8 codes 0 .. 255, F16 and F32 values), as in the scaled
+ *     call.  Entries of different data types may share a call.
+ *   Sums.  r(ky) = the sum over the x taps, in tap order, of wx * v(kx, ky)[c], for every y tap; acc = the sum over the y taps,
+ *     in tap order, of wy * r(ky).  A sum starts as its first product (nothing is added to a zero); every product and every sum
+ *     is one IEEE binary64 operation, round to nearest even, never fused.  s[c] = (float)acc: one rounding to binary32.  There
+ *     is no division: the weights of an axis sum to 1.
+ *   Arithmetic, storage.  Those of astcenc_amd_decompress_tensors_device: t = s[c] * scale[c], y = t + bias[c], two binary32
+ *     roundings; F32 / F16 / BF16 round to nearest even; a NaN y is stored as the type's canonical quiet NaN.
+ *   Placement.  The value is element
+ *       PLANAR:       c * plane_pitch + j * row_pitch + i
+ *       INTERLEAVED:  j * row_pitch + i * channels + c
+ *     of `out`.  A zero pitch is the tight one: row_pitch = out_x (PLANAR) or out_x * channels (INTERLEAVED); plane_pitch =
+ *     row_pitch * out_y (PLANAR only).  No other element is written.
+ *
+ *   Consequences: NEAREST anywhere inside texel k -- k <= u < k + 1 -- reproduces texel k; BILINEAR at (kx + 0.5, ky + 0.5)
+ *   reproduces texel (kx, ky) too, because f = 0 on both axes and 1.0 * v is v.  So a grid of the texel centres of a window
+ *   writes, with either filter and any address mode, bit for bit what astcenc_amd_decompress_tensors_device writes for that
+ *   window without flips, for U8, F16 and F32 entries.
+ *
+ *   Out of scope: mip level selection and trilinear filtering (a caller samples the level it wants; each level is an entry);
+ *   anisotropy; sampling along z (z selects an array slice); 3D footprints; gradients with respect to coordinates or texels.
+ *
+ *   - Entries, z inside the image, device ownership (of `coords` too), the null / zero-count cases, the format, pitches below the
+ *     tight ones, a plane_pitch with INTERLEAVED, the alignment of `out`, a null `out` and the stream are checked as in
+ *     astcenc_amd_decompress_scaled_tensors_device, with its error codes; everything is checked before anything is launched, a
+ *     failure returns its error with nothing written, and the log callback names the index of the grid or entry.
+ *   - Also ASTCENC_ERR_BAD_PARAM: a null `sampler`; a filter or an address mode that is not one of the above; an out_x or out_y
+ *     that is zero or above 65535; a `coords` not aligned to 8 bytes; an odd coord_row_pitch, or a non-zero one below 2 * out_x;
+ *     a context whose footprint is 3D (block_z > 1); an entry of 2^32 - 1 blocks or more; more than 2^32 - 1 work items in all.
+ *     A null `coords`: ASTCENC_ERR_BAD_CONTEXT, like a null buffer elsewhere.  Coordinates are data: none of them is an error.
+ *   - A work item is a tile of tw x th points of one grid with tw * th = 64: th = min(8, out_y rounded up to a power of two) --
+ *     64 x 1 for one row, 32 x 2, 16 x 4, and 8 x 8 from five rows on -- so a grid has ceil(out_x / tw) * ceil(out_y / th) of
+ *     them.  A tile decodes every block its points' taps reach once, at most 256 of them, wherever they lie in the image;
+ *     blocks that several tiles need are decoded by each. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_tensors_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_sampler* sampler,
+	const struct astcenc_amd_sample_grid* grids, unsigned int grid_count,
+	void* hip_stream);
+
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
  *
  * Level i is max(1, dim_x >> i) x max(1, dim_y >> i) (the GL / Vulkan / KTX rule); level_count == 0 means the full chain down
