@@ -1,0 +1,134 @@
+// SPDX-License-Identifier: Apache-2.0
+// astcenc_amd_sample_lod_tensors_device (include/astcenc_amd.h): device-resident compressed mip chains sampled at buffers of
+// normalised coordinates with a level of detail per point -- the UV and LOD buffers of a rasteriser, a neural-texture trainer, a
+// texture-space shading pass -- and written as tensors, many grids per launch.  The format, the sampler, every entry and every
+// grid are checked here, all of them before anything is launched; the backend then covers the tiles of all grids as one range of
+// work items (backend_decompress_lod).  The coordinates and the levels of detail themselves are data: none of
+// them is an error.
+// Product library only, like astcenc_sample.cpp.
+#include "sample_internal.h"
+
+using namespace astcd;
+
+extern "C" {
+
+astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                                    const astcenc_amd_tensor_format* format, const astcenc_amd_lod_sampler* sampler,
+                                                    const astcenc_amd_lod_grid* grids, unsigned int grid_count, void* hip_stream)
+{
+	const char* fn = "astcenc_amd_sample_lod_tensors_device";
+	if (grid_count == 0) return ASTCENC_SUCCESS;
+	if (!ctx || !grids || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
+	astcenc_error status = check_sample_format(fn, format);
+	if (status != ASTCENC_SUCCESS) return status;
+	if (!sampler)
+	{
+		backend_log("%s: sampler is null", fn);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
+	if (status != ASTCENC_SUCCESS) return status;
+	if ((int)sampler->mip_filter != ASTCENC_AMD_MIP_NEAREST && (int)sampler->mip_filter != ASTCENC_AMD_MIP_LINEAR)
+	{
+		backend_log("%s: sampler: mip_filter %d: not a mip filter", fn, (int)sampler->mip_filter);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	DecodeTensorFormat fmt;
+	status = check_sample_factors(fn, ctx, format, fmt);
+	if (status != ASTCENC_SUCCESS) return status;
+
+	std::vector<DecompressDeviceJob> jobs;
+	status = check_sample_entries(fn, ctx, entries, entry_count, jobs);
+	if (status != ASTCENC_SUCCESS) return status;
+
+	std::vector<DecodeLodLaunch> launches(grid_count);
+	unsigned long long tiles = 0;
+	for (unsigned int i = 0; i < grid_count; i++)
+	{
+		const astcenc_amd_lod_grid& g = grids[i];
+		if (g.level_count == 0 || g.level_count > 32)
+		{
+			backend_log("%s: grid %u of %u: %u levels: a chain has 1 to 32", fn, i, grid_count, g.level_count);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		if ((unsigned long long)g.first_entry + g.level_count > entry_count)
+		{
+			backend_log("%s: grid %u of %u: levels are entries %u to %llu, the call has %u entries", fn, i, grid_count, g.first_entry,
+			            (unsigned long long)g.first_entry + g.level_count - 1, entry_count);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		for (unsigned int l = 0; l < g.level_count; l++)
+		{
+			const astcenc_amd_image_set_entry& en = entries[g.first_entry + l];
+			if (g.z >= en.dim_z)
+			{
+				backend_log("%s: grid %u of %u: slice %u is not inside the %u x %u x %u image of entry %u (level %u)", fn, i, grid_count, g.z, en.dim_x, en.dim_y,
+				            en.dim_z, g.first_entry + l, l);
+				return ASTCENC_ERR_BAD_PARAM;
+			}
+			// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
+			if (en.dim_x > 65536 || en.dim_y > 65536)
+			{
+				backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u texels: a level is at most 65536 along x and y", fn, i, grid_count, g.first_entry + l, l,
+				            en.dim_x, en.dim_y);
+				return ASTCENC_ERR_BAD_PARAM;
+			}
+		}
+		if (!std::isfinite(g.lod_bias))
+		{
+			backend_log("%s: grid %u of %u: lod_bias %g: not finite", fn, i, grid_count, (double)g.lod_bias);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		if (g.lod_row_pitch != 0 && g.lod_row_pitch < g.out_x)
+		{
+			backend_log("%s: grid %u of %u: lod_row_pitch %zu: at least %u floats", fn, i, grid_count, g.lod_row_pitch, g.out_x);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		SampleGridShape shape = { g.out_x, g.out_y, g.coords, g.coord_row_pitch, g.out, g.row_pitch, g.plane_pitch };
+		status = check_sample_grid(fn, i, grid_count, format, shape);
+		if (status != ASTCENC_SUCCESS) return status;
+		const size_t lod_row_pitch = g.lod_row_pitch ? g.lod_row_pitch : g.out_x;
+		bool overflow = false;
+		(void)mul_safe(mul_safe(lod_row_pitch, g.out_y, overflow), sizeof(float), overflow);
+		if (overflow)
+		{
+			backend_log("%s: grid %u of %u: lod_row_pitch %zu: the levels of detail do not fit 64 bits", fn, i, grid_count, g.lod_row_pitch);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		if (reinterpret_cast<uintptr_t>(g.lod) % 4 != 0)
+		{
+			backend_log("%s: grid %u of %u: lod %p is not aligned to a float (4 bytes)", fn, i, grid_count, static_cast<const void*>(g.lod));
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		DecodeLodLaunch& l = launches[i];
+		l.first_entry = g.first_entry; l.level_count = g.level_count;
+		l.z = g.z;
+		l.out_x = g.out_x; l.out_y = g.out_y;
+		l.d_coords = g.coords;
+		l.coord_row_pitch = shape.coord_row_pitch;
+		l.d_lod = g.lod;
+		l.lod_row_pitch = lod_row_pitch;
+		l.lod_bias = g.lod_bias;
+		l.d_out = g.out;
+		l.row_pitch = shape.row_pitch; l.plane_pitch = shape.plane_pitch;
+		if (!add_sample_tiles(fn, i, grid_count, g.out_x, g.out_y, tiles)) return ASTCENC_ERR_BAD_PARAM;
+	}
+
+	DecodeLodSampler smp;
+	smp.filter = (uint32_t)sampler->filter; smp.address_x = (uint32_t)sampler->address_x; smp.address_y = (uint32_t)sampler->address_y;
+	smp.mip_filter = (uint32_t)sampler->mip_filter;
+	DecompressLodJob job;
+	memset(&job, 0, sizeof(job));
+	job.entries = jobs.data();
+	job.entry_count = entry_count;
+	job.format = &fmt;
+	job.sampler = &smp;
+	job.grids = launches.data();
+	job.grid_count = grid_count;
+	job.stream = hip_stream;
+	status = windows_rc_to_error(backend_decompress_lod(ctx->backend, job));
+	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream is not on the device of entry 0's blocks", fn);
+	return status;
+}
+
+} // extern "C"

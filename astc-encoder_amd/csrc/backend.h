@@ -255,6 +255,20 @@ struct DecompressSampleJob {
 	void*    stream;
 };
 int backend_decompress_sample(Backend* b, const DecompressSampleJob& job);
+/* astcenc_amd_sample_lod_tensors_device: the same with the call's level-of-detail sampler and the grids as DecodeLodLaunch; a grid
+ * uses the entries of all its levels. */
+struct DecodeLodSampler;
+struct DecodeLodLaunch;
+struct DecompressLodJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	const DecodeLodSampler* sampler;
+	const DecodeLodLaunch* grids;
+	uint32_t grid_count;
+	void*    stream;
+};
+int backend_decompress_lod(Backend* b, const DecompressLodJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -474,6 +488,31 @@ size_t astc_decode_sample_bytes(uint32_t count);
 uint32_t astc_decode_sample_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeSampler& sampler,
                                   const DecodeSampleLaunch* grids, uint32_t count);
 int astc_decode_sample_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
+/* Mip chains sampled at a level of detail per point (astcenc_amd_sample_lod_tensors_device; decode_lod.h, kernel_decode_lod.hip):
+ * the call's format and sampler and one DecodeLodLaunch per grid, checked by the entry point -- as above, and: 1 .. 32 levels, all
+ * of them entries of the call no larger than 65536 along x and y that hold slice z, lod (when given) aligned to a float, lod_bias
+ * finite.  A work item is a tile of 64 points of a grid (astc_decode_sample_tiles of them); the table -- a record per grid, then a
+ * record per level of every grid -- and the launch as above. */
+struct DecodeLodSampler {
+	uint32_t filter, address_x, address_y;    // astcenc_amd_sample_filter / _address
+	uint32_t mip_filter;                      // astcenc_amd_mip_level_filter
+};
+struct DecodeLodLaunch {
+	uint32_t first_entry, level_count;    // level l is entry first_entry + l
+	uint32_t z;                           // the slice, in every level
+	uint32_t out_x, out_y;                // points per row, rows of points
+	const float* d_coords;                // point (i, j): the pair at d_coords[j * coord_row_pitch + 2 i], u then v
+	size_t   coord_row_pitch;             // floats
+	const float* d_lod;                   // point (i, j): d_lod[j * lod_row_pitch + i]; null: 0 everywhere
+	size_t   lod_row_pitch;               // floats
+	float    lod_bias;
+	void*    d_out;                       // element (c = 0, j = 0, i = 0)
+	size_t   row_pitch, plane_pitch;
+};
+size_t astc_decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count);
+uint32_t astc_decode_lod_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                               const DecodeLodLaunch* grids, uint32_t count);
+int astc_decode_lod_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -1591,15 +1591,13 @@ int backend_decompress_set(Backend* b, const DecompressSetJob& job)
 
 /* astcenc_amd_decompress_regions_device, astcenc_amd_decompress_tensors_device and astcenc_amd_decompress_scaled_tensors_device: as
  * backend_decompress_set, with the regions' table (decode_regions.h, decode_tensors.h, decode_scaled.h) in place of the set's.
- * Only the entries a region names are looked at; their streams and every region's buffer must be on the owner's device.
- * entry_of / out_of: region i's entry and buffer (with `buffers` of them a region, buffer i belongs to region i / buffers); table(d, out): the table's bytes, or with `out` the table written there from
+ * Only the entries a region names (used[e]) are looked at; their streams and every region's buffer must be on the owner's device.
+ * out_of: region i's buffer (with `buffers` of them a region, buffer i belongs to region i / buffers); table(d, out): the table's bytes, or with `out` the table written there from
  * the entries' launches `d`, returning its runs; launch: its kernel. */
-template <class EntryOf, class OutOf, class Table, class Launch>
-static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, uint32_t entry_count, uint32_t region_count, void* job_stream,
-                              const char* what, EntryOf entry_of, OutOf out_of, Table table, Launch launch, uint32_t buffers = 1)
+template <class OutOf, class Table, class Launch>
+static int decompress_windows_of(Backend* b, const DecompressDeviceJob* entries, uint32_t entry_count, const std::vector<uint8_t>& used, uint32_t region_count,
+                                 void* job_stream, const char* what, OutOf out_of, Table table, Launch launch, uint32_t buffers)
 {
-	std::vector<uint8_t> used(entry_count, 0);
-	for (uint32_t i = 0; i < region_count; i++) used[entry_of(i)] = 1;
 	return run_on_owner(b, entries[0].device_blocks, nullptr, 0, job_stream, [&](DeviceSlot* s, hipStream_t stream)
 	{
 		auto foreign = [s](const void* p)
@@ -1633,6 +1631,16 @@ static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, ui
 		HIP_TRY(hipStreamSynchronize(stream), return 2);
 		return 0;
 	});
+}
+
+/* (a region names one entry: used[e] of decompress_windows_of from entry_of) */
+template <class EntryOf, class OutOf, class Table, class Launch>
+static int decompress_windows(Backend* b, const DecompressDeviceJob* entries, uint32_t entry_count, uint32_t region_count, void* job_stream,
+                              const char* what, EntryOf entry_of, OutOf out_of, Table table, Launch launch, uint32_t buffers = 1)
+{
+	std::vector<uint8_t> used(entry_count, 0);
+	for (uint32_t i = 0; i < region_count; i++) used[entry_of(i)] = 1;
+	return decompress_windows_of(b, entries, entry_count, used, region_count, job_stream, what, out_of, table, launch, buffers);
 }
 
 int backend_decompress_regions(Backend* b, const DecompressRegionsJob& job)
@@ -1679,6 +1687,25 @@ int backend_decompress_sample(Backend* b, const DecompressSampleJob& job)
 			return out ? astc_decode_sample_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_sample_bytes(job.grid_count);
 		},
 		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_sample_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 2u);
+}
+
+/* (a grid uses the entries of all its levels; its buffers are the output, the coordinates and, unless null, the levels of detail) */
+int backend_decompress_lod(Backend* b, const DecompressLodJob& job)
+{
+	std::vector<uint8_t> used(job.entry_count, 0);
+	for (uint32_t i = 0; i < job.grid_count; i++)
+		for (uint32_t l = 0; l < job.grids[i].level_count; l++) used[job.grids[i].first_entry + l] = 1;
+	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample lod tensors",
+		[&](uint32_t i)
+		{
+			const DecodeLodLaunch& g = job.grids[i / 3u];
+			return i % 3u == 0u || (i % 3u == 2u && !g.d_lod) ? static_cast<const void*>(g.d_out) : i % 3u == 1u ? static_cast<const void*>(g.d_coords) : static_cast<const void*>(g.d_lod);
+		},
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_lod_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_lod_bytes(job.grids, job.grid_count);
+		},
+		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_lod_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
 }
 
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial

@@ -15,7 +15,11 @@
 // After the last batch the lane forms the sums in the defined order (binary64, x taps then y taps, a sum starting as its first
 // product), rounds once to binary32 and stores through TensorStore::put.
 //
-// Included by kernel_decode_sample.hip and tests/harness/decode_sample_check.cpp only: not part of wave_decode.h's include graph.
+// The taps of a point, the batch loop and the sums are routines of their own (sample_point_taps, sample_batches,
+// sample_point_sums): decode_lod.h runs them once per mip level a tile's points need.
+//
+// Included by kernel_decode_sample.hip, decode_lod.h and the harnesses of tests/harness only: not part of wave_decode.h's
+// include graph.
 //
 // Layout: ImageSetTable (count = grids, total = tiles), first[count], padding, DecodeSampleRecord[count].
 #pragma once
@@ -59,6 +63,24 @@ inline unsigned long long decode_sample_tiles(uint32_t out_x, uint32_t out_y)
 inline size_t decode_sample_bytes(uint32_t count)
 {
 	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeSampleRecord);
+}
+
+/* The image of an entry's launch, prepared, without `data`: what the tables here and in decode_lod.h hold of an entry. */
+inline DecodeImage decode_sample_image(const DecodeLaunch& d)
+{
+	DecodeImage img;
+	img.data = nullptr;
+	img.tabs = static_cast<const DecodeTables*>(d.d_tables);
+	img.dim_x = d.dim_x; img.dim_y = d.dim_y; img.dim_z = d.dim_z;
+	img.data_type = d.data_type;
+	for (int i = 0; i < 4; i++) img.swz[i] = d.swz[i];
+	img.block_x = d.block_x; img.block_y = d.block_y; img.block_z = d.block_z;
+	img.blocks_x = (d.dim_x + d.block_x - 1) / d.block_x;
+	img.blocks_y = (d.dim_y + d.block_y - 1) / d.block_y;
+	img.blocks_z = (d.dim_z + d.block_z - 1) / d.block_z;
+	img.profile = d.profile;
+	decode_image_prepare(img);
+	return img;
 }
 
 /* Writes the table of `count` grids over the images `images` (prepared, 2D footprints, `data` unused) and their streams;
@@ -136,16 +158,17 @@ WV_FN bool sample_address(uint32_t mode, int32_t i, uint32_t S, uint32_t& k)
 /* The taps of a coordinate along one axis: n of them (1 or 2), their indices before addressing and their binary64 weights. */
 struct SampleAxis { int32_t i0; uint32_t n; double w0, w1; };
 
-WV_FN SampleAxis sample_axis(uint32_t filter, float x)
+/* (the coordinate as binary64: the level coordinates of decode_lod.h are products that a binary32 does not hold) */
+WV_FN SampleAxis sample_axis(uint32_t filter, double x)
 {
 	SampleAxis a;
 	if (filter == 0u)
 	{
-		a.i0 = (int32_t)__builtin_floor((double)x);
+		a.i0 = (int32_t)__builtin_floor(x);
 		a.n = 1u; a.w0 = 1.0; a.w1 = 0.0;
 		return a;
 	}
-	const double t = (double)x - 0.5;
+	const double t = x - 0.5;
 	const double fl = __builtin_floor(t);
 	const double f = t - fl;
 	a.i0 = (int32_t)fl;
@@ -153,6 +176,8 @@ WV_FN SampleAxis sample_axis(uint32_t filter, float x)
 	a.n = f == 0.0 ? 1u : 2u;
 	return a;
 }
+
+WV_FN SampleAxis sample_axis(uint32_t filter, float x) { return sample_axis(filter, (double)x); }
 
 /* A point is valid when both coordinates are finite and no larger than 2^30 in magnitude. */
 WV_FN bool sample_valid(float x, float y)
@@ -174,9 +199,13 @@ struct SamplePoint {
 
 #if WV_DEVICE
 #define SAMPLE_POINTS_DECL SamplePoint point_regs
+#define SAMPLE_POINTS_PARAM SamplePoint& point_regs
+#define SAMPLE_POINTS_ARG point_regs
 #define SAMPLE_POINT(l) point_regs
 #else
 #define SAMPLE_POINTS_DECL SamplePoint point_lanes[SAMPLE_POINTS]
+#define SAMPLE_POINTS_PARAM SamplePoint* point_lanes
+#define SAMPLE_POINTS_ARG point_lanes
 #define SAMPLE_POINT(l) point_lanes[l]
 #endif
 
@@ -242,68 +271,61 @@ WV_FN uint32_t sample_all_umin(uint32_t v)
 /* What a tile did, for the harness (`blocks` mode, the batch checks): batches run and blocks decoded. */
 struct SampleTileCount { uint32_t batches, blocks; };
 
-/* Tile `local` of the grid of `rec` (all 64 lanes call this; `local` is uniform); kType / kLayout are the record's. */
-template <uint32_t kType, uint32_t kLayout>
-WV_FN SampleTileCount decode_sample_tile(const DecodeSampleRecord& rec, uint32_t local, DecodeBatch& batch, SampleTile& tile)
+/* A point without taps: nothing pending, every texel +0.0. */
+__attribute__((always_inline)) WV_FN void sample_point_clear(SamplePoint& P)
 {
-	const uint32_t tw_log2 = rec.tw_log2, tw_mask = (1u << tw_log2) - 1u, th_log2 = 6u - tw_log2;
-	const uint32_t tile_y = local / rec.tiles_x, tile_x = local - tile_y * rec.tiles_x;
-	const uint32_t i0 = tile_x << tw_log2, j0 = tile_y << th_log2;
-	const uint32_t block_x = rec.img.block_x, block_y = rec.img.block_y;
-	const uint32_t filter = rec.filter;
-	SAMPLE_POINTS_DECL;
-
-	// ---- the taps of every point ----
-	WV_FOR64(l, 64)
+	P.pending = 0u;
+	P.nx = 0u; P.ny = 0u;
+	P.wx[0] = 0.0; P.wx[1] = 0.0; P.wy[0] = 0.0; P.wy[1] = 0.0;
+	for (int t = 0; t < SAMPLE_TAPS; t++)
 	{
-		SamplePoint& P = SAMPLE_POINT(l);
-		const uint32_t i = i0 + ((uint32_t)l & tw_mask), j = j0 + ((uint32_t)l >> tw_log2);
-		P.live = i < rec.out_x && j < rec.out_y ? 1u : 0u;
-		P.pending = 0u;
-		P.nx = 0u; P.ny = 0u;
-		P.wx[0] = 0.0; P.wx[1] = 0.0; P.wy[0] = 0.0; P.wy[1] = 0.0;
-		for (int t = 0; t < SAMPLE_TAPS; t++)
-		{
-			P.blk[t] = 0xFFFFFFFFu; P.txy[t] = 0u;
-			for (int c = 0; c < 4; c++) P.v[t][c] = 0.0f;
-		}
-		if (P.live)
-		{
-			// (coords is aligned to 8 bytes and the pitch is even: one 8-byte load)
-			const float* xy = static_cast<const float*>(__builtin_assume_aligned(rec.coords + (size_t)j * rec.coord_row + 2u * (size_t)i, 8));
-			const float x = xy[0], y = xy[1];
-			if (sample_valid(x, y))
-			{
-				P.live = 3u;
-				const SampleAxis ax = sample_axis(filter, x), ay = sample_axis(filter, y);
-				P.nx = ax.n; P.ny = ay.n;
-				P.wx[0] = ax.w0; P.wx[1] = ax.w1; P.wy[0] = ay.w0; P.wy[1] = ay.w1;
-				uint32_t kx[2] = { 0u, 0u }, ky[2] = { 0u, 0u };
-				bool inx[2], iny[2];
-				for (int a = 0; a < 2; a++)
-				{
-					inx[a] = (uint32_t)a < ax.n && sample_address(rec.address_x, ax.i0 + a, rec.img.dim_x, kx[a]);
-					iny[a] = (uint32_t)a < ay.n && sample_address(rec.address_y, ay.i0 + a, rec.img.dim_y, ky[a]);
-				}
-#if WV_DEVICE
-				#pragma unroll
-#endif
-				for (int t = 0; t < SAMPLE_TAPS; t++)
-				{
-					if (!inx[t & 1] || !iny[t >> 1]) continue;
-					const uint32_t bx = kx[t & 1] / block_x, by = ky[t >> 1] / block_y;
-					P.blk[t] = (rec.z * rec.img.blocks_y + by) * rec.img.blocks_x + bx;
-					P.txy[t] = (kx[t & 1] - bx * block_x) | ((ky[t >> 1] - by * block_y) << 8);
-					P.pending |= 1u << t;
-				}
-			}
-		}
+		P.blk[t] = 0xFFFFFFFFu; P.txy[t] = 0u;
+		for (int c = 0; c < 4; c++) P.v[t][c] = 0.0f;
 	}
+}
 
-	// ---- batches of distinct blocks until no tap is pending ----
-	const bool small_block = block_x * block_y < 31u;
-	const uint32_t swz_sel = swizzle_selector(rec.img.swz);
-	SampleTileCount done = { 0u, 0u };
+/* The taps of a cleared point at (x, y), binary64 in texel units of slice z of `img`, |x|, |y| <= 2^30: weights, blocks, texels
+ * and the pending bits. */
+__attribute__((always_inline)) WV_FN void sample_point_taps(SamplePoint& P, const DecodeImage& img, uint32_t z, uint32_t filter, uint32_t address_x, uint32_t address_y,
+                                                            double x, double y)
+{
+	const uint32_t block_x = img.block_x, block_y = img.block_y;
+	const SampleAxis ax = sample_axis(filter, x), ay = sample_axis(filter, y);
+	P.nx = ax.n; P.ny = ay.n;
+	P.wx[0] = ax.w0; P.wx[1] = ax.w1; P.wy[0] = ay.w0; P.wy[1] = ay.w1;
+	// (a tap that is not there -- the second of an axis with one, a BORDER tap outside -- has no index: an index is at most
+	//  2^30 + 1.  The flag travels in the integer, not as a boolean across the address modes' branches.)
+	uint32_t kx[2] = { 0xFFFFFFFFu, 0xFFFFFFFFu }, ky[2] = { 0xFFFFFFFFu, 0xFFFFFFFFu };
+	for (int a = 0; a < 2; a++)
+	{
+		uint32_t k = 0u;
+		if ((uint32_t)a < ax.n) kx[a] = sample_address(address_x, ax.i0 + a, img.dim_x, k) ? k : 0xFFFFFFFFu;
+		if ((uint32_t)a < ay.n) ky[a] = sample_address(address_y, ay.i0 + a, img.dim_y, k) ? k : 0xFFFFFFFFu;
+	}
+	// (one division per axis tap, not per tap; the quotient of a tap that is not there is not used)
+	const uint32_t bx[2] = { kx[0] / block_x, kx[1] / block_x }, by[2] = { ky[0] / block_y, ky[1] / block_y };
+#if WV_DEVICE
+	#pragma unroll
+#endif
+	for (int t = 0; t < SAMPLE_TAPS; t++)
+	{
+		if (kx[t & 1] == 0xFFFFFFFFu || ky[t >> 1] == 0xFFFFFFFFu) continue;
+		P.blk[t] = (z * img.blocks_y + by[t >> 1]) * img.blocks_x + bx[t & 1];
+		P.txy[t] = (kx[t & 1] - bx[t & 1] * block_x) | ((ky[t >> 1] - by[t >> 1] * block_y) << 8);
+		P.pending |= 1u << t;
+	}
+}
+
+/* Batches of distinct blocks of `img` (stream `blocks`) until no tap of the wave's points is pending (all 64 lanes call this);
+ * `done` counts on. */
+__attribute__((always_inline)) WV_FN void sample_batches(const DecodeImage& img, const uint8_t* blocks, DecodeBatch& batch, SampleTile& tile, SAMPLE_POINTS_PARAM,
+                                                         SampleTileCount& done)
+{
+	const bool small_block = img.block_x * img.block_y < 31u;
+	const uint32_t swz_sel = swizzle_selector(img.swz);
+#if !WV_DEVICE
+	uint32_t listed_blocks = 0u;
+#endif
 	for (;;)
 	{
 		// 1. the smallest pending block indices, ascending: a wave minimum a slot
@@ -329,12 +351,13 @@ WV_FN SampleTileCount decode_sample_tile(const DecodeSampleRecord& rec, uint32_t
 		if (count == 0) break;
 		WV_SYNC();
 #if !WV_DEVICE
-		// (a tile references at most 256 blocks: eight full batches)
-		if (done.blocks + (uint32_t)count > (uint32_t)SAMPLE_TILE_BLOCKS) __builtin_trap();
+		// (the points of a tile reference at most 256 blocks of an image: eight full batches)
+		listed_blocks += (uint32_t)count;
+		if (listed_blocks > (uint32_t)SAMPLE_TILE_BLOCKS) __builtin_trap();
 #endif
 		// 2. the decoder's phases over the list
 		const SampleBlocks listed = { tile.list };
-		(void)decode_batch_blocks(rec.img, rec.blocks, listed, count, batch);
+		(void)decode_batch_blocks(img, blocks, listed, count, batch);
 		// 3. the taps that landed in the batch: those whose block is below `lower`
 		WV_FOR64(l, 64)
 		{
@@ -357,7 +380,7 @@ WV_FN SampleTileCount decode_sample_tile(const DecodeSampleRecord& rec, uint32_t
 				if (tile.list[k] != b) __builtin_trap();
 #endif
 				SampleSink sink;
-				decode_batch_texel(rec.img, batch, k, 1, (int)(txy & 0xFFu), (int)(txy >> 8), 0, small_block, swz_sel, (size_t)0, sink, l);
+				decode_batch_texel(img, batch, k, 1, (int)(txy & 0xFFu), (int)(txy >> 8), 0, small_block, swz_sel, (size_t)0, sink, l);
 				for (int c = 0; c < 4; c++)
 				{
 					P.v[0][c] = t == 0u ? sink.s[c] : P.v[0][c];
@@ -372,6 +395,58 @@ WV_FN SampleTileCount decode_sample_tile(const DecodeSampleRecord& rec, uint32_t
 		done.batches++;
 		done.blocks += (uint32_t)count;
 	}
+}
+
+/* The sums of a point whose taps are decoded, in the defined order, one rounding. */
+__attribute__((always_inline)) WV_FN void sample_point_sums(const SamplePoint& P, float s[4])
+{
+	for (int c = 0; c < 4; c++)
+	{
+		double r0 = P.wx[0] * (double)P.v[0][c];
+		if (P.nx > 1u) r0 = r0 + P.wx[1] * (double)P.v[1][c];
+		double acc = P.wy[0] * r0;
+		if (P.ny > 1u)
+		{
+			double r1 = P.wx[0] * (double)P.v[2][c];
+			if (P.nx > 1u) r1 = r1 + P.wx[1] * (double)P.v[3][c];
+			acc = acc + P.wy[1] * r1;
+		}
+		s[c] = (float)acc;
+	}
+}
+
+/* Tile `local` of the grid of `rec` (all 64 lanes call this; `local` is uniform); kType / kLayout are the record's. */
+template <uint32_t kType, uint32_t kLayout>
+WV_FN SampleTileCount decode_sample_tile(const DecodeSampleRecord& rec, uint32_t local, DecodeBatch& batch, SampleTile& tile)
+{
+	const uint32_t tw_log2 = rec.tw_log2, tw_mask = (1u << tw_log2) - 1u, th_log2 = 6u - tw_log2;
+	const uint32_t tile_y = local / rec.tiles_x, tile_x = local - tile_y * rec.tiles_x;
+	const uint32_t i0 = tile_x << tw_log2, j0 = tile_y << th_log2;
+	SAMPLE_POINTS_DECL;
+
+	// ---- the taps of every point ----
+	WV_FOR64(l, 64)
+	{
+		SamplePoint& P = SAMPLE_POINT(l);
+		const uint32_t i = i0 + ((uint32_t)l & tw_mask), j = j0 + ((uint32_t)l >> tw_log2);
+		P.live = i < rec.out_x && j < rec.out_y ? 1u : 0u;
+		sample_point_clear(P);
+		if (P.live)
+		{
+			// (coords is aligned to 8 bytes and the pitch is even: one 8-byte load)
+			const float* xy = static_cast<const float*>(__builtin_assume_aligned(rec.coords + (size_t)j * rec.coord_row + 2u * (size_t)i, 8));
+			const float x = xy[0], y = xy[1];
+			if (sample_valid(x, y))
+			{
+				P.live = 3u;
+				sample_point_taps(P, rec.img, rec.z, rec.filter, rec.address_x, rec.address_y, (double)x, (double)y);
+			}
+		}
+	}
+
+	// ---- batches of distinct blocks until no tap is pending ----
+	SampleTileCount done = { 0u, 0u };
+	sample_batches(rec.img, rec.blocks, batch, tile, SAMPLE_POINTS_ARG, done);
 
 	// ---- the sums in the defined order, one rounding, the tensors call's arithmetic and stores ----
 	TensorStore<kType, kLayout> store = { rec.fmt };
@@ -381,22 +456,7 @@ WV_FN SampleTileCount decode_sample_tile(const DecodeSampleRecord& rec, uint32_t
 		if (!(P.live & 1u)) continue;
 		const uint32_t i = i0 + ((uint32_t)l & tw_mask), j = j0 + ((uint32_t)l >> tw_log2);
 		float s[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-		if (P.live & 2u)
-		{
-			for (int c = 0; c < 4; c++)
-			{
-				double r0 = P.wx[0] * (double)P.v[0][c];
-				if (P.nx > 1u) r0 = r0 + P.wx[1] * (double)P.v[1][c];
-				double acc = P.wy[0] * r0;
-				if (P.ny > 1u)
-				{
-					double r1 = P.wx[0] * (double)P.v[2][c];
-					if (P.nx > 1u) r1 = r1 + P.wx[1] * (double)P.v[3][c];
-					acc = acc + P.wy[1] * r1;
-				}
-				s[c] = (float)acc;
-			}
-		}
+		if (P.live & 2u) sample_point_sums(P, s);
 		store.template put<false>(rec.img, (size_t)j * rec.row + (size_t)i * rec.x_step, s);
 	}
 	WV_SYNC();

@@ -48,20 +48,8 @@ uint32_t astc_decode_sample_build(void* out, const DecodeLaunch* entries, uint32
 	std::vector<const uint8_t*> streams(entry_count);
 	for (uint32_t e = 0; e < entry_count; e++)
 	{
-		const DecodeLaunch& d = entries[e];
-		DecodeImage& img = images[e];
-		img.data = nullptr;
-		img.tabs = static_cast<const DecodeTables*>(d.d_tables);
-		img.dim_x = d.dim_x; img.dim_y = d.dim_y; img.dim_z = d.dim_z;
-		img.data_type = d.data_type;
-		for (int i = 0; i < 4; i++) img.swz[i] = d.swz[i];
-		img.block_x = d.block_x; img.block_y = d.block_y; img.block_z = d.block_z;
-		img.blocks_x = (d.dim_x + d.block_x - 1) / d.block_x;
-		img.blocks_y = (d.dim_y + d.block_y - 1) / d.block_y;
-		img.blocks_z = (d.dim_z + d.block_z - 1) / d.block_z;
-		img.profile = d.profile;
-		decode_image_prepare(img);
-		streams[e] = d.d_blocks;
+		images[e] = decode_sample_image(entries[e]);
+		streams[e] = entries[e].d_blocks;
 	}
 	return decode_sample_build(out, images.data(), streams.data(), format, sampler, grids, count);
 }

@@ -104,12 +104,14 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_image_adaptive_device", "astcenc_amd_select_blocks_set_device",
                "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
                "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
-               "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device"]
+               "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device",
+               "astcenc_amd_sample_lod_tensors_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
 WINDOW_BILINEAR, WINDOW_BOX = 0, 1
 SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
+MIP_NEAREST, MIP_LINEAR = 0, 1
 ADDRESS_CLAMP, ADDRESS_REPEAT, ADDRESS_MIRROR, ADDRESS_BORDER = 0, 1, 2, 3
 NO_BLOCK_BUDGET = 0xFFFFFFFF
 OPT_PER_SLICE_FAST_LOAD = 1
@@ -355,6 +357,57 @@ def sample_grid(entry, z, coords, out_view, layout=TENSOR_PLANAR, type=None):
     return SampleGrid(entry, z, r.out_x, r.out_y, coords.data_ptr(), coord_row_pitch, r.out, r.row_pitch, r.plane_pitch)
 
 
+class LodSampler(C.Structure):
+    """struct astcenc_amd_lod_sampler (include/astcenc_amd.h): SAMPLE_* filter within a level, ADDRESS_* mode per axis, MIP_NEAREST /
+    MIP_LINEAR between levels."""
+    _fields_ = [("filter", C.c_int), ("address_x", C.c_int), ("address_y", C.c_int), ("mip_filter", C.c_int)]
+
+
+class LodGrid(C.Structure):
+    """struct astcenc_amd_lod_grid (include/astcenc_amd.h)."""
+    _fields_ = [("first_entry", C.c_uint), ("level_count", C.c_uint), ("z", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint),
+                ("coords", C.c_void_p), ("coord_row_pitch", C.c_size_t), ("lod", C.c_void_p), ("lod_row_pitch", C.c_size_t), ("lod_bias", C.c_float),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
+
+
+def lod_grid(first_entry, level_count, z, coords, lod, out_view, lod_bias=0.0, layout=TENSOR_PLANAR, type=None):
+    """LodGrid of slice `z` of the chain entries[first_entry : first_entry + level_count]: `coords` is a float32 torch tensor
+    [H, W, 2] of NORMALISED (u, v) pairs, `lod` a float32 torch tensor [H, W] of levels of detail or None (0 everywhere), `out_view`
+    the torch view [C, H, W] for TENSOR_PLANAR or [H, W, C] for TENSOR_INTERLEAVED the points are written to; pointers and pitches
+    come from the strides.  ValueError for what the call cannot express: everything sample_grid rejects of `coords` and `out_view`;
+    a level_count outside 1 .. 32; a lod_bias that is not finite; a `lod` that is not float32, not [H, W] with the H, W of `coords`,
+    whose columns are not adjacent floats, whose rows overlap or alias or have a negative stride, or which lives on another device
+    than `coords`.  Or explicit tuples: coords = (ptr, out_x, out_y, coord_row_pitch), lod = (ptr, lod_row_pitch) or None, out_view =
+    (ptr, row_pitch, plane_pitch)."""
+    import math
+    if not 1 <= level_count <= MAX_MIP_LEVELS:
+        raise ValueError("level_count %r: a chain has 1 .. %d levels" % (level_count, MAX_MIP_LEVELS))
+    if not math.isfinite(lod_bias):
+        raise ValueError("lod_bias %r is not finite" % (lod_bias,))
+    if isinstance(coords, tuple):
+        g = sample_grid(first_entry, z, coords, out_view)
+        lptr, lod_row_pitch = lod if lod is not None else (None, 0)
+    else:
+        g = sample_grid(first_entry, z, coords, out_view, layout=layout, type=type)
+        lptr, lod_row_pitch = None, 0
+        if lod is not None:
+            import torch
+            if lod.dtype != torch.float32:
+                raise ValueError("lod is %s: float32" % lod.dtype)
+            lshape, lst = tuple(lod.shape), tuple(lod.stride())
+            if lod.dim() != 2 or lshape != (g.out_y, g.out_x):
+                raise ValueError("lod has shape %r: [H, W] = [%u, %u]" % (lshape, g.out_y, g.out_x))
+            if (lst[1] != 1 and lshape[1] > 1) or lst[0] < 0 or (lst[0] == 0 and lshape[0] > 1):
+                raise ValueError("the columns of lod must be adjacent floats and its rows apart (strides %r)" % (lst,))
+            if lod.device != coords.device:
+                raise ValueError("lod is on %s, coords on %s" % (lod.device, coords.device))
+            lod_row_pitch = lst[0] if lshape[0] > 1 else 0
+            if lod_row_pitch != 0 and lod_row_pitch < lshape[1]:
+                raise ValueError("the rows of lod overlap (strides %r)" % (lst,))
+            lptr = lod.data_ptr()
+    return LodGrid(first_entry, level_count, z, g.out_x, g.out_y, g.coords, g.coord_row_pitch, lptr, lod_row_pitch, lod_bias, g.out, g.row_pitch, g.plane_pitch)
+
+
 class ErrorSums(C.Structure):
     """struct astcenc_amd_error_sums (include/astcenc_amd.h)."""
     _fields_ = [("squared_error", C.c_double * 4), ("alpha_scaled_squared_error", C.c_double * 4),
@@ -496,6 +549,10 @@ class Library:
             L.astcenc_amd_decompress_scaled_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.c_int,
                                                                        C.POINTER(ScaledRegion), C.c_uint, C.c_void_p]
             L.astcenc_amd_decompress_scaled_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_sample_lod_tensors_device"):
+            L.astcenc_amd_sample_lod_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(LodSampler),
+                                                                C.POINTER(LodGrid), C.c_uint, C.c_void_p]
+            L.astcenc_amd_sample_lod_tensors_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_sample_tensors_device"):
             L.astcenc_amd_sample_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(Sampler),
                                                             C.POINTER(SampleGrid), C.c_uint, C.c_void_p]
@@ -728,6 +785,19 @@ class Library:
         garr = (SampleGrid * len(grids))(*grids) if grids else None
         return self.lib.astcenc_amd_sample_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
                                                           C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_lod_tensors_device(self, ctx, entries, format, sampler, grids, stream=None):
+        """astcenc_amd_sample_lod_tensors_device: mip chains among the compressed images `entries` sampled at normalised coordinates
+        and a level of detail per point into tensors of `format`.  sampler: a LodSampler, or a (filter, address_x, address_y,
+        mip_filter) tuple of SAMPLE_* / ADDRESS_* / MIP_NEAREST, MIP_LINEAR constants.  grids: LodGrid, or (first_entry, level_count,
+        z, coords, lod, out_view[, lod_bias]) tuples (see lod_grid; the view is read with the format's layout and must have its type)."""
+        arr, n, s = self._set_args(entries, stream)
+        if sampler is not None and not isinstance(sampler, LodSampler):
+            sampler = LodSampler(*sampler)
+        grids = [g if isinstance(g, LodGrid) else lod_grid(*g, layout=format.layout, type=format.type) for g in grids]
+        garr = (LodGrid * len(grids))(*grids) if grids else None
+        return self.lib.astcenc_amd_sample_lod_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
+                                                              C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

@@ -362,8 +362,8 @@ struct astcenc_amd_sample_grid {
  *   writes, with either filter and any address mode, bit for bit what astcenc_amd_decompress_tensors_device writes for that
  *   window without flips, for U8, F16 and F32 entries.
  *
- *   Out of scope: mip level selection and trilinear filtering (a caller samples the level it wants; each level is an entry);
- *   anisotropy; sampling along z (z selects an array slice); 3D footprints; gradients with respect to coordinates or texels.
+ *   Out of scope: anisotropy; sampling along z (z selects an array slice); 3D footprints; gradients with respect to coordinates or texels.
+ *   Mip level selection and trilinear filtering are astcenc_amd_sample_lod_tensors_device's, below.
  *
  *   - Entries, z inside the image, device ownership (of `coords` too), the null / zero-count cases, the format, pitches below the
  *     tight ones, a plane_pitch with INTERLEAVED, the alignment of `out`, a null `out` and the stream are checked as in
@@ -383,6 +383,91 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_tensors_device(
 	const struct astcenc_amd_tensor_format* format,
 	const struct astcenc_amd_sampler* sampler,
 	const struct astcenc_amd_sample_grid* grids, unsigned int grid_count,
+	void* hip_stream);
+
+/* Compressed mip chains sampled at a level of detail per point straight into tensors: the other half of a texture unit -- "the
+ * filtered texel at (u, v) at level of detail lambda" for a UV buffer and a per-pixel level of detail: a differentiable
+ * rasteriser, a neural-texture trainer, a texture-space shading pass -- with every level staying compressed, the points of one
+ * grid on any levels, in one launch for many grids.  A chain is level_count consecutive entries, entries[first_entry + l] being
+ * level l: what astcenc_amd_compress_mip_chain_device and its kin write (one entry per level), the outputs of
+ * astcenc_amd_resize_image_device compressed, or levels assembled by hand.
+ *
+ * The sampler holds for the whole call. */
+/* (the tag astcenc_amd_mip_filter is the mip GENERATION filter's, further down: this is the filter between levels when sampling) */
+enum astcenc_amd_mip_level_filter {
+	ASTCENC_AMD_MIP_NEAREST = 0,            /* the one level nearest to lambda */
+	ASTCENC_AMD_MIP_LINEAR = 1              /* the two levels around lambda, blended linearly: trilinear with SAMPLE_BILINEAR */
+};
+struct astcenc_amd_lod_sampler {
+	enum astcenc_amd_sample_filter filter;  /* within a level */
+	enum astcenc_amd_sample_address address_x, address_y;
+	enum astcenc_amd_mip_level_filter mip_filter;
+};
+
+struct astcenc_amd_lod_grid {
+	unsigned int first_entry, level_count;  /* entries[first_entry + l] is level l; 1 <= level_count <= 32 */
+	unsigned int z;                         /* the slice, inside every level */
+	unsigned int out_x, out_y;              /* points per row / rows of points, each 1 .. 65535 */
+	const float* coords;                    /* device pointer: point (i, j) is the pair at coords[j * coord_row_pitch + 2 * i], u then v,
+	                                           NORMALISED: the image is [0, 1) x [0, 1) at every level */
+	size_t coord_row_pitch;                 /* in floats, even; 0 = 2 * out_x */
+	const float* lod;                       /* device pointer: point (i, j) has lod[j * lod_row_pitch + i]; NULL: 0 everywhere */
+	size_t lod_row_pitch;                   /* in floats; 0 = out_x */
+	float lod_bias;                         /* added to every point's lod; finite */
+	void* out;                              /* device pointer: element (c = 0, j = 0, i = 0) */
+	size_t row_pitch, plane_pitch;          /* in ELEMENTS of the format's type; 0 = tightly packed */
+};
+
+/* Sample grids[0 .. grid_count) into tensors of `format` (astcenc_amd_decompress_tensors_device's).  For point (i, j) of a grid,
+ * 0 <= i < out_x, 0 <= j < out_y, with (u, v) read from `coords` and lod from `lod`, and channel c < format->channels (reals are
+ * IEEE binary64 below unless said otherwise; "one operation" is one IEEE operation, round to nearest even, never fused):
+ *
+ *   Levels.  Level l is the image of entries[first_entry + l], W_l x H_l texels.  The levels of a chain may have any sizes --
+ *     normalised coordinates make each level well defined -- and each level has its entry's data_type and swizzle; levels of
+ *     different data types may share a chain.
+ *   Validity.  lambda' = lod + lod_bias, one binary32 addition; lod = +0.0 when `lod` is NULL.  A point is VALID when u and v are
+ *     finite and no larger than 2^14 in magnitude (2^14 itself is valid) and lambda' is not a NaN.  An invalid point has
+ *     s[c] = +0.0 for every channel and then goes through "Arithmetic, storage" like any other.  No level is larger than 65536
+ *     along x or y (see below), so every level coordinate stays within the 2^30 the sample call allows.
+ *   Level of detail.  lambda_c = min(max(lambda', 0), level_count - 1); the infinities clamp.
+ *       MIP_NEAREST: one level, l = ceil(lambda_c + 0.5) - 1 (the sum is one binary64 addition; it selects what the exact sum
+ *         would) -- the GL rule, the finer level on a tie: 0.5 selects level 0 -- with weight 1.
+ *       MIP_LINEAR: l0 = floor(lambda_c), g = lambda_c - l0 (exact).  Level l0 has weight 1.0 - g (one binary64 subtraction),
+ *         level l0 + 1 has weight g.  When g = 0 -- which includes l0 = level_count - 1 -- level l0 + 1 is not part of the sum and
+ *         none of its blocks is read: a NaN there does not reach the result (the zero-weight rule of the sample call's taps).
+ *   Within a level.  x_l = (double)u * (double)W_l and y_l = (double)v * (double)H_l: exact products (24 bits by 17).  s_l[c] is
+ *     exactly what astcenc_amd_sample_tensors_device defines as s[c] for that entry and slice z, with x_l and y_l in the place of
+ *     "the coordinate widened to binary64": the same taps under `filter`, the same addressing, BORDER rule, source texels and
+ *     order of sums, and one rounding to binary32.
+ *   Blend.  One level: s[c] = s_l[c].  Two levels: s[c] = (float)((1.0 - g) * (double)s_l0[c] + g * (double)s_l1[c]): two
+ *     products and one sum, one operation each, then one rounding to binary32.
+ *   Arithmetic, storage, placement.  Those of astcenc_amd_sample_tensors_device.
+ *
+ *   Consequences: with a chain of one level, or wherever lambda' is an integer (or beyond either end of the chain), the result is
+ *   that level's s_l under either mip filter.  Where W_l and H_l are powers of two, u * W_l and v * H_l are binary32 values, so
+ *   the bytes are those astcenc_amd_sample_tensors_device writes for that entry at (u * W_l, v * H_l).
+ *
+ *   Out of scope: level selection from coordinate derivatives (a log2 cannot be given a bit-exact contract: the caller supplies
+ *   lambda); anisotropy; cube maps; sampling along z; 3D footprints; gradients.
+ *
+ *   - Everything astcenc_amd_sample_tensors_device checks is checked here with the same error codes -- the entries, the format,
+ *     the sampler's filter and address modes, out_x and out_y, `coords` and its pitch, `out` and its pitches, device ownership,
+ *     the context's footprint, the work items -- everything before anything is launched; a failure returns its error with
+ *     nothing written, and the log callback names the index: "grid i of n".
+ *   - Also ASTCENC_ERR_BAD_PARAM: a null `sampler` or a mip_filter that is not one of the above; a level_count of 0 or above 32;
+ *     first_entry + level_count beyond entry_count; a z outside any level of the chain; a level (an entry used as one) with
+ *     dim_x or dim_y above 65536; a lod_bias that is not finite; a `lod` not aligned to 4 bytes; a non-zero lod_row_pitch below
+ *     out_x; a `lod` that is not on the device of entry 0's blocks (as `coords`).  A null `lod` is legal.  Coordinates and levels
+ *     of detail are data: none of them is an error.
+ *   - A work item is a tile of 64 points, those of astcenc_amd_sample_tensors_device.  A tile runs one pass per distinct level
+ *     its points need, at most level_count of them (counted on a 1920 x 1080 grid whose lambda rises over four levels: 2.02 a
+ *     tile), and a pass decodes every block of that level its points' taps reach once. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_lod_tensors_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_lod_sampler* sampler,
+	const struct astcenc_amd_lod_grid* grids, unsigned int grid_count,
 	void* hip_stream);
 
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
