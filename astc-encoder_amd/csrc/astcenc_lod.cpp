@@ -19,7 +19,7 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 	const char* fn = "astcenc_amd_sample_lod_tensors_device";
 	if (grid_count == 0) return ASTCENC_SUCCESS;
 	if (!ctx || !grids || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
-	astcenc_error status = check_sample_format(fn, format);
+	astcenc_error status = check_tensor_format(fn, format);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (!sampler)
 	{
@@ -33,8 +33,10 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 		backend_log("%s: sampler: mip_filter %d: not a mip filter", fn, (int)sampler->mip_filter);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
+	status = check_sample_footprint(fn, ctx);
+	if (status != ASTCENC_SUCCESS) return status;
 	DecodeTensorFormat fmt;
-	status = check_sample_factors(fn, ctx, format, fmt);
+	status = check_tensor_factors(fn, format, fmt);
 	if (status != ASTCENC_SUCCESS) return status;
 
 	std::vector<DecompressDeviceJob> jobs;
@@ -119,16 +121,11 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 	smp.mip_filter = (uint32_t)sampler->mip_filter;
 	DecompressLodJob job;
 	memset(&job, 0, sizeof(job));
-	job.entries = jobs.data();
-	job.entry_count = entry_count;
 	job.format = &fmt;
 	job.sampler = &smp;
 	job.grids = launches.data();
 	job.grid_count = grid_count;
-	job.stream = hip_stream;
-	status = windows_rc_to_error(backend_decompress_lod(ctx->backend, job));
-	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream is not on the device of entry 0's blocks", fn);
-	return status;
+	return run_windows_job(fn, ctx, jobs, hip_stream, job, backend_decompress_lod);
 }
 
 } // extern "C"

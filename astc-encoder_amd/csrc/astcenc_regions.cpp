@@ -69,14 +69,9 @@ astcenc_error astcenc_amd_decompress_regions_device(astcenc_context* ctx, const 
 
 	DecompressRegionsJob job;
 	memset(&job, 0, sizeof(job));
-	job.entries = jobs.data();
-	job.entry_count = entry_count;
 	job.regions = launches.data();
 	job.region_count = region_count;
-	job.stream = hip_stream;
-	const astcenc_error status = windows_rc_to_error(backend_decompress_regions(ctx->backend, job));
-	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream is not on the device of entry 0's blocks", fn);
-	return status;
+	return run_windows_job(fn, ctx, jobs, hip_stream, job, backend_decompress_regions);
 }
 
 } // extern "C"

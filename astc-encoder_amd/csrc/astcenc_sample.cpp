@@ -18,7 +18,7 @@ astcenc_error astcenc_amd_sample_tensors_device(astcenc_context* ctx, const astc
 	const char* fn = "astcenc_amd_sample_tensors_device";
 	if (grid_count == 0) return ASTCENC_SUCCESS;
 	if (!ctx || !grids || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
-	astcenc_error status = check_sample_format(fn, format);
+	astcenc_error status = check_tensor_format(fn, format);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (!sampler)
 	{
@@ -27,8 +27,10 @@ astcenc_error astcenc_amd_sample_tensors_device(astcenc_context* ctx, const astc
 	}
 	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
 	if (status != ASTCENC_SUCCESS) return status;
+	status = check_sample_footprint(fn, ctx);
+	if (status != ASTCENC_SUCCESS) return status;
 	DecodeTensorFormat fmt;
-	status = check_sample_factors(fn, ctx, format, fmt);
+	status = check_tensor_factors(fn, format, fmt);
 	if (status != ASTCENC_SUCCESS) return status;
 
 	std::vector<DecompressDeviceJob> jobs;
@@ -69,16 +71,11 @@ astcenc_error astcenc_amd_sample_tensors_device(astcenc_context* ctx, const astc
 	smp.filter = (uint32_t)sampler->filter; smp.address_x = (uint32_t)sampler->address_x; smp.address_y = (uint32_t)sampler->address_y;
 	DecompressSampleJob job;
 	memset(&job, 0, sizeof(job));
-	job.entries = jobs.data();
-	job.entry_count = entry_count;
 	job.format = &fmt;
 	job.sampler = &smp;
 	job.grids = launches.data();
 	job.grid_count = grid_count;
-	job.stream = hip_stream;
-	status = windows_rc_to_error(backend_decompress_sample(ctx->backend, job));
-	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream is not on the device of entry 0's blocks", fn);
-	return status;
+	return run_windows_job(fn, ctx, jobs, hip_stream, job, backend_decompress_sample);
 }
 
 } // extern "C"

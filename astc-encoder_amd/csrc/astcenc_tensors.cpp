@@ -6,8 +6,6 @@
 // Product library only, like astcenc_regions.cpp.
 #include "regions_internal.h"
 
-#include <cmath>
-
 using namespace astcd;
 
 extern "C" {
@@ -19,91 +17,38 @@ astcenc_error astcenc_amd_decompress_tensors_device(astcenc_context* ctx, const 
 	const char* fn = "astcenc_amd_decompress_tensors_device";
 	if (region_count == 0) return ASTCENC_SUCCESS;
 	if (!ctx || !regions || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
-	if (!format)
-	{
-		backend_log("%s: format is null", fn);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if ((int)format->type < ASTCENC_AMD_TENSOR_F32 || (int)format->type > ASTCENC_AMD_TENSOR_BF16 ||
-	    (int)format->layout < ASTCENC_AMD_TENSOR_PLANAR || (int)format->layout > ASTCENC_AMD_TENSOR_INTERLEAVED)
-	{
-		backend_log("%s: format: type %d, layout %d: not a tensor type / layout", fn, (int)format->type, (int)format->layout);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if (format->channels < 1 || format->channels > 4)
-	{
-		backend_log("%s: format: %u channels: 1 to 4 can be had", fn, format->channels);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
+	astcenc_error status = check_tensor_format(fn, format);
+	if (status != ASTCENC_SUCCESS) return status;
 	DecodeTensorFormat fmt;
-	memset(&fmt, 0, sizeof(fmt));
-	fmt.type = (uint32_t)format->type; fmt.layout = (uint32_t)format->layout; fmt.channels = format->channels;
-	for (unsigned int c = 0; c < format->channels; c++)
-	{
-		if (!std::isfinite(format->scale[c]) || !std::isfinite(format->bias[c]))
-		{
-			backend_log("%s: format: scale %g, bias %g of channel %u: not finite", fn, (double)format->scale[c], (double)format->bias[c], c);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		fmt.scale[c] = format->scale[c]; fmt.bias[c] = format->bias[c];
-	}
-	const bool planar = format->layout == ASTCENC_AMD_TENSOR_PLANAR;
-	const size_t element = format->type == ASTCENC_AMD_TENSOR_F32 ? 4 : 2;
+	status = check_tensor_factors(fn, format, fmt);
+	if (status != ASTCENC_SUCCESS) return status;
 
 	std::vector<DecompressDeviceJob> jobs;
-	const astcenc_error entries_status = check_window_entries(fn, ctx, entries, entry_count, jobs);
-	if (entries_status != ASTCENC_SUCCESS) return entries_status;
+	status = check_window_entries(fn, ctx, entries, entry_count, jobs);
+	if (status != ASTCENC_SUCCESS) return status;
 
 	std::vector<DecodeTensorLaunch> launches(region_count);
 	unsigned long long runs = 0;
 	for (unsigned int i = 0; i < region_count; i++)
 	{
 		const astcenc_amd_tensor_region& r = regions[i];
-		const astcenc_error window_status = check_window(fn, i, region_count, entries, entry_count, r.entry, r.x, r.y, r.z, r.size_x, r.size_y, r.size_z);
-		if (window_status != ASTCENC_SUCCESS) return window_status;
+		status = check_window(fn, i, region_count, entries, entry_count, r.entry, r.x, r.y, r.z, r.size_x, r.size_y, r.size_z);
+		if (status != ASTCENC_SUCCESS) return status;
 		if (r.flags & ~(ASTCENC_AMD_TENSOR_FLIP_X | ASTCENC_AMD_TENSOR_FLIP_Y))
 		{
 			backend_log("%s: region %u of %u: flags 0x%x: unknown bits", fn, i, region_count, r.flags);
 			return ASTCENC_ERR_BAD_PARAM;
 		}
-		// pitches in elements, every product in 64 bits: the tensor's extent in bytes must fit them too
-		bool overflow = false;
-		const size_t tight_row = mul_safe(r.size_x, planar ? 1 : format->channels, overflow);
-		const size_t row_pitch = r.row_pitch ? r.row_pitch : tight_row;
-		const size_t tight_slice = mul_safe(row_pitch, r.size_y, overflow);
-		const size_t slice_pitch = r.slice_pitch ? r.slice_pitch : tight_slice;
-		const size_t tight_plane = mul_safe(slice_pitch, r.size_z, overflow);
-		const size_t plane_pitch = r.plane_pitch ? r.plane_pitch : tight_plane;
-		(void)mul_safe(planar ? mul_safe(plane_pitch, format->channels, overflow) : tight_plane, element, overflow);
-		if (overflow || row_pitch < tight_row || slice_pitch < tight_slice || (planar && plane_pitch < tight_plane))
-		{
-			backend_log("%s: region %u of %u: row_pitch %zu, slice_pitch %zu, plane_pitch %zu: the window needs at least %zu, %zu and %zu elements", fn, i,
-			            region_count, r.row_pitch, r.slice_pitch, r.plane_pitch, tight_row, tight_slice, tight_plane);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		if (!planar && r.plane_pitch != 0)
-		{
-			backend_log("%s: region %u of %u: plane_pitch %zu: the interleaved layout has no planes", fn, i, region_count, r.plane_pitch);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		// (a null buffer: what the other device calls return for one)
-		if (!r.out)
-		{
-			backend_log("%s: region %u of %u: out is null", fn, i, region_count);
-			return ASTCENC_ERR_BAD_CONTEXT;
-		}
-		if (reinterpret_cast<uintptr_t>(r.out) % element != 0)
-		{
-			backend_log("%s: region %u of %u: out %p is not aligned to the element size %zu", fn, i, region_count, r.out, element);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
+		TensorPitches pitches = { r.row_pitch, r.slice_pitch, r.plane_pitch };
+		status = check_output_tensor(fn, "region", i, region_count, format, r.size_x, r.size_y, r.size_z, pitches, r.out);
+		if (status != ASTCENC_SUCCESS) return status;
 		DecodeTensorLaunch& l = launches[i];
 		l.entry = r.entry;
 		l.x = r.x; l.y = r.y; l.z = r.z;
 		l.size_x = r.size_x; l.size_y = r.size_y; l.size_z = r.size_z;
 		l.flags = r.flags;
 		l.d_out = r.out;
-		l.row_pitch = row_pitch; l.slice_pitch = slice_pitch; l.plane_pitch = planar ? plane_pitch : 0;
+		l.row_pitch = pitches.row; l.slice_pitch = pitches.slice; l.plane_pitch = pitches.plane;
 		DecodeRegionLaunch window;
 		memset(&window, 0, sizeof(window));
 		window.x = r.x; window.y = r.y; window.z = r.z;
@@ -113,15 +58,10 @@ astcenc_error astcenc_amd_decompress_tensors_device(astcenc_context* ctx, const 
 
 	DecompressTensorsJob job;
 	memset(&job, 0, sizeof(job));
-	job.entries = jobs.data();
-	job.entry_count = entry_count;
 	job.format = &fmt;
 	job.regions = launches.data();
 	job.region_count = region_count;
-	job.stream = hip_stream;
-	const astcenc_error status = windows_rc_to_error(backend_decompress_tensors(ctx->backend, job));
-	if (status == ASTCENC_ERR_BAD_PARAM) backend_log("%s: a buffer or hip_stream is not on the device of entry 0's blocks", fn);
-	return status;
+	return run_windows_job(fn, ctx, jobs, hip_stream, job, backend_decompress_tensors);
 }
 
 } // extern "C"

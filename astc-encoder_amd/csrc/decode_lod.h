@@ -51,7 +51,7 @@ static_assert(sizeof(DecodeLodLevel) % 8 == 0, "records are read word by word an
 
 inline size_t decode_lod_levels_offset(uint32_t count)
 {
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeLodRecord);
+	return decode_table_bytes<DecodeLodRecord>(count);
 }
 
 inline size_t decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count)
@@ -67,9 +67,8 @@ inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uin
                                  const DecodeLodLaunch* grids, uint32_t count)
 {
 	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, decode_lod_bytes(grids, count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	DecodeLodRecord* rec = reinterpret_cast<DecodeLodRecord*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	DecodeLodRecord* rec = decode_table_begin<DecodeLodRecord>(out, decode_lod_bytes(grids, count), count, first);
 	size_t level_at = decode_lod_levels_offset(count);
 	uint32_t tiles = 0;
 	for (uint32_t i = 0; i < count; i++)
@@ -89,16 +88,9 @@ inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uin
 		r.filter = sampler.filter; r.address_x = sampler.address_x; r.address_y = sampler.address_y; r.mip_filter = sampler.mip_filter;
 		r.tw_log2 = decode_sample_tw_log2(g.out_y);
 		r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
-		r.x_step = format.layout == 1 ? format.channels : 1u;
+		r.x_step = tensor_x_step(format);
 		r.lod_bias = g.lod_bias;
-		r.fmt.type = format.type; r.fmt.layout = format.layout; r.fmt.channels = format.channels;
-		for (int c = 0; c < 4; c++)
-		{
-			// (channels the format does not use: computed and dropped, so they are given harmless factors)
-			r.fmt.scale[c] = (uint32_t)c < format.channels ? format.scale[c] : 0.0f;
-			r.fmt.bias[c] = (uint32_t)c < format.channels ? format.bias[c] : 0.0f;
-		}
-		r.fmt.plane = g.plane_pitch;
+		r.fmt = tensor_params(format, g.plane_pitch);
 		for (uint32_t l = 0; l < g.level_count; l++)
 		{
 			DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at);
@@ -110,10 +102,7 @@ inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uin
 		first[i] = tiles;
 		tiles += (uint32_t)decode_sample_tiles(g.out_x, g.out_y);
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = tiles;
-	return tiles;
+	return decode_table_finish(out, count, tiles);
 }
 
 /* A point is valid when u and v are finite and no larger than 2^14 in magnitude and lambda' is not a NaN. */

@@ -3,16 +3,14 @@
 // does with it.  A work item is a run of at most DECODE_BATCH consecutive covered blocks of one block row and one layer of
 // blocks of one region; the runs of all regions sit back to back, a run finds its region in the table (image_set.h) and decodes
 // its blocks with the window policy of wave_decode.h (DecodeWindow): blocks outside a window's covered range are never read.
-// The table is built on the host by plain code (decode_regions_build: kernel_decode.hip calls it for the kernel,
+// The table is built on the host by plain code over the frame of decode_table.h (decode_regions_build: kernel_decode.hip calls it for the kernel,
 // tests/harness/decode_region_check.cpp for the sequential build); decode_region_run is the kernel's body.
 //
 // Layout (16-byte aligned), as image_set.h lays an image set out: ImageSetTable (count = regions, total = runs), first[count],
 // padding, DecodeRegionRecord[count].
 #pragma once
 #include "backend.h"          // DecodeRegionLaunch: one region as the host hands it over, everything checked already
-#include "image_set.h"
-#include "wave_decode.h"
-#include <cstring>
+#include "decode_table.h"
 
 namespace astcd { inline namespace ASTC_VARIANT {
 
@@ -45,19 +43,14 @@ inline unsigned long long decode_region_runs(uint32_t x, uint32_t y, uint32_t z,
 	return (unsigned long long)((cx + (uint32_t)DECODE_BATCH - 1u) / (uint32_t)DECODE_BATCH) * cy * cz;
 }
 
-inline size_t decode_regions_bytes(uint32_t count)
-{
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeRegionRecord);
-}
+inline size_t decode_regions_bytes(uint32_t count) { return decode_table_bytes<DecodeRegionRecord>(count); }
 
 /* Writes the table of `count` regions over the images `images` (prepared, `data` unused) and their streams; returns the runs
  * of all regions (the caller has made sure they fit 32 bits). */
 inline uint32_t decode_regions_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeRegionLaunch* regions, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, decode_regions_bytes(count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	DecodeRegionRecord* rec = reinterpret_cast<DecodeRegionRecord*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	DecodeRegionRecord* rec = decode_table_begin<DecodeRegionRecord>(out, decode_regions_bytes(count), count, first);
 	uint32_t runs = 0;
 	for (uint32_t i = 0; i < count; i++)
 	{
@@ -80,10 +73,7 @@ inline uint32_t decode_regions_build(void* out, const DecodeImage* images, const
 		first[i] = runs;
 		runs += r.runs_xy * layers;
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = runs;
-	return runs;
+	return decode_table_finish(out, count, runs);
 }
 
 /* Run `local` of the region of `rec` (all 64 lanes call this; `local` is uniform): its place among the covered blocks -- run,

@@ -60,38 +60,15 @@ inline unsigned long long decode_sample_tiles(uint32_t out_x, uint32_t out_y)
 	return (unsigned long long)((out_x + tw - 1u) / tw) * ((out_y + th - 1u) / th);
 }
 
-inline size_t decode_sample_bytes(uint32_t count)
-{
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeSampleRecord);
-}
-
-/* The image of an entry's launch, prepared, without `data`: what the tables here and in decode_lod.h hold of an entry. */
-inline DecodeImage decode_sample_image(const DecodeLaunch& d)
-{
-	DecodeImage img;
-	img.data = nullptr;
-	img.tabs = static_cast<const DecodeTables*>(d.d_tables);
-	img.dim_x = d.dim_x; img.dim_y = d.dim_y; img.dim_z = d.dim_z;
-	img.data_type = d.data_type;
-	for (int i = 0; i < 4; i++) img.swz[i] = d.swz[i];
-	img.block_x = d.block_x; img.block_y = d.block_y; img.block_z = d.block_z;
-	img.blocks_x = (d.dim_x + d.block_x - 1) / d.block_x;
-	img.blocks_y = (d.dim_y + d.block_y - 1) / d.block_y;
-	img.blocks_z = (d.dim_z + d.block_z - 1) / d.block_z;
-	img.profile = d.profile;
-	decode_image_prepare(img);
-	return img;
-}
+inline size_t decode_sample_bytes(uint32_t count) { return decode_table_bytes<DecodeSampleRecord>(count); }
 
 /* Writes the table of `count` grids over the images `images` (prepared, 2D footprints, `data` unused) and their streams;
  * returns the tiles of all grids (the caller has made sure they fit 32 bits). */
 inline uint32_t decode_sample_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeSampler& sampler,
                                     const DecodeSampleLaunch* grids, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, decode_sample_bytes(count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	DecodeSampleRecord* rec = reinterpret_cast<DecodeSampleRecord*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	DecodeSampleRecord* rec = decode_table_begin<DecodeSampleRecord>(out, decode_sample_bytes(count), count, first);
 	uint32_t tiles = 0;
 	for (uint32_t i = 0; i < count; i++)
 	{
@@ -108,22 +85,12 @@ inline uint32_t decode_sample_build(void* out, const DecodeImage* images, const 
 		r.filter = sampler.filter; r.address_x = sampler.address_x; r.address_y = sampler.address_y;
 		r.tw_log2 = decode_sample_tw_log2(g.out_y);
 		r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
-		r.x_step = format.layout == 1 ? format.channels : 1u;
-		r.fmt.type = format.type; r.fmt.layout = format.layout; r.fmt.channels = format.channels;
-		for (int c = 0; c < 4; c++)
-		{
-			// (channels the format does not use: computed and dropped, so they are given harmless factors)
-			r.fmt.scale[c] = (uint32_t)c < format.channels ? format.scale[c] : 0.0f;
-			r.fmt.bias[c] = (uint32_t)c < format.channels ? format.bias[c] : 0.0f;
-		}
-		r.fmt.plane = g.plane_pitch;
+		r.x_step = tensor_x_step(format);
+		r.fmt = tensor_params(format, g.plane_pitch);
 		first[i] = tiles;
 		tiles += (uint32_t)decode_sample_tiles(g.out_x, g.out_y);
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = tiles;
-	return tiles;
+	return decode_table_finish(out, count, tiles);
 }
 
 /* A tap index under an address mode (0 CLAMP, 1 REPEAT, 2 MIRROR, 3 BORDER) along an axis of S texels; |i| <= 2^30 + 1.
@@ -221,31 +188,21 @@ struct SampleBlocks {
 };
 
 /* The sink: the texel in whichever form it leaves the decoder becomes s[0 .. 3], the regions call's texel as binary32
- * (TensorStore's three routes, kept instead of stored). */
+ * (decode_tensors.h: what TensorStore stores, kept). */
 struct SampleSink {
 	float s[4];
-	WV_FN void pixel(const DecodeImage&, int, size_t, uint32_t px)
-	{
-		s[0] = (float)(px & 0xFFu); s[1] = (float)((px >> 8) & 0xFFu); s[2] = (float)((px >> 16) & 0xFFu); s[3] = (float)(px >> 24);
-	}
-	WV_FN void halves(const DecodeImage&, int, size_t, uint64_t px)
-	{
-		for (int c = 0; c < 4; c++) s[c] = tensor_widen_half((uint16_t)(px >> (16 * c)));
-	}
-	WV_FN void texel(const DecodeImage& img, int lane, size_t at, float r, float g, float b, float a)
+	WV_FN void pixel(const DecodeImage&, int, size_t, uint32_t px) { tensor_from_pixel(px, s); }
+	WV_FN void halves(const DecodeImage&, int, size_t, uint64_t px) { tensor_from_halves(px, s); }
+	WV_FN void texel(const DecodeImage& img, int, size_t, float r, float g, float b, float a)
 	{
 		if (img.data_type == 0)
 		{
-			pixel(img, lane, at, pack_texel_u8(img, r, g, b, a));
+			tensor_from_pixel(pack_texel_u8(img, r, g, b, a), s);
 			return;
 		}
 		float src[7];
 		swizzle_sources(r, g, b, a, src);
-		for (int c = 0; c < 4; c++)
-		{
-			const float v = src[img.swz[c]];
-			s[c] = img.data_type == 1 ? tensor_through_half(v) : v;
-		}
+		for (int c = 0; c < 4; c++) s[c] = tensor_from_source(img, src, c);
 	}
 	WV_FN void trip_end(int, int, int) {}
 };

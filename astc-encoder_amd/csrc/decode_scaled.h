@@ -199,20 +199,15 @@ inline unsigned long long decode_scaled_tiles(uint32_t size_x, uint32_t out_x, u
 	return (unsigned long long)strips * bands;
 }
 
-inline size_t decode_scaled_bytes(uint32_t count)
-{
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeScaledRecord);
-}
+inline size_t decode_scaled_bytes(uint32_t count) { return decode_table_bytes<DecodeScaledRecord>(count); }
 
 /* Writes the table of `count` regions over the images `images` (prepared, 2D footprints, `data` unused) and their streams;
  * returns the tiles of all regions (the caller has made sure they fit 32 bits). */
 inline uint32_t decode_scaled_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, uint32_t filter,
                                     const DecodeScaledLaunch* regions, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, decode_scaled_bytes(count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	DecodeScaledRecord* rec = reinterpret_cast<DecodeScaledRecord*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	DecodeScaledRecord* rec = decode_table_begin<DecodeScaledRecord>(out, decode_scaled_bytes(count), count, first);
 	uint32_t tiles = 0;
 	for (uint32_t i = 0; i < count; i++)
 	{
@@ -225,25 +220,15 @@ inline uint32_t decode_scaled_build(void* out, const DecodeImage* images, const 
 		r.size_x = g.size_x; r.size_y = g.size_y;
 		r.out_x = g.out_x; r.out_y = g.out_y;
 		r.filter = filter; r.flags = g.flags;
-		r.x_step = format.layout == 1 ? format.channels : 1u;
+		r.x_step = tensor_x_step(format);
 		r.row = g.row_pitch;
-		r.fmt.type = format.type; r.fmt.layout = format.layout; r.fmt.channels = format.channels;
-		for (int c = 0; c < 4; c++)
-		{
-			// (channels the format does not use: computed and dropped, so they are given harmless factors)
-			r.fmt.scale[c] = (uint32_t)c < format.channels ? format.scale[c] : 0.0f;
-			r.fmt.bias[c] = (uint32_t)c < format.channels ? format.bias[c] : 0.0f;
-		}
-		r.fmt.plane = g.plane_pitch;
+		r.fmt = tensor_params(format, g.plane_pitch);
 		uint32_t bands;
 		decode_scaled_tiling(g.size_x, g.out_x, g.out_y, r.img.data_type, r.img.block_x, r.img.block_y, r.run_blocks, r.cols, r.strips, r.band, bands);
 		first[i] = tiles;
 		tiles += r.strips * bands;
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = tiles;
-	return tiles;
+	return decode_table_finish(out, count, tiles);
 }
 
 /* The output columns [c0, c0 + nc) and rows [r0, r0 + nr) of tile `local` of a region, and the window-relative source

@@ -10,7 +10,9 @@
 // The format holds for a whole call, so its type and layout are template parameters of the sink and the kernel, picked on the host:
 // the texel loops hold one kind of store and no dispatch.  `channels`, scale and bias are wave-uniform values of the record.
 //
-// Included by kernel_decode.hip and tests/harness/decode_tensor_check.cpp only: not part of wave_decode.h's include graph.
+// Included by kernel_decode.hip, tests/harness/decode_tensor_check.cpp and the headers of the other tensor calls (decode_scaled.h,
+// decode_sample.h and, through it, decode_lod.h: the format in a record, the texel conversions and TensorStore::put are theirs
+// too) only: not part of wave_decode.h's include graph.
 //
 // Layout: ImageSetTable (count = regions, total = runs), first[count], padding, DecodeTensorRecord[count].  The call's format
 // sits in every record rather than in the table's head: a run then reads all it needs with the one block of scalar loads that
@@ -48,6 +50,21 @@ struct TensorParams {
 	float    scale[4], bias[4];
 	size_t   plane;                   // elements from channel to channel (planar)
 };
+
+/* The call's format as a record holds it, `plane_pitch` the region's; ... */
+inline TensorParams tensor_params(const DecodeTensorFormat& format, size_t plane_pitch)
+{
+	TensorParams f;
+	memset(&f, 0, sizeof(f));
+	f.type = format.type; f.layout = format.layout; f.channels = format.channels;
+	// (channels the format does not use are computed and dropped: their factors stay the harmless 0)
+	for (uint32_t c = 0; c < format.channels && c < 4u; c++) { f.scale[c] = format.scale[c]; f.bias[c] = format.bias[c]; }
+	f.plane = plane_pitch;
+	return f;
+}
+
+/* ... and the elements from column to column of its tensors: 1 planar, `channels` interleaved. */
+inline uint32_t tensor_x_step(const DecodeTensorFormat& format) { return format.layout == 1 ? format.channels : 1u; }
 
 struct DecodeTensorRecord {
 	DecodeImage img;                  // the entry's image; data = the region's `out`
@@ -95,7 +112,26 @@ WV_FN float tensor_through_half(float v)
 #endif
 }
 
-/* The sink: every form a texel leaves the decoder in becomes s[0 .. 3], the regions call's texel as binary32, then one routine.
+/* A texel in each form it leaves the decoder in, made what the regions call would have stored as the entry's data type
+ * (store_texel_at's three routes), as binary32: a packed U8 pixel and four halves as s[0 .. 3]; of an F16 or F32 entry's floats,
+ * component c from the swizzle's sources (swizzle_sources; a U8 entry's floats are packed with pack_texel_u8 and go the first
+ * way).  Only a pixel's s is known to hold numbers alone.  (tensor_from_source is per component, the loop its callers': with
+ * the loop in here the compiler lays one build of astc_decode_tensors out differently.) */
+WV_FN void tensor_from_pixel(uint32_t px, float s[4])
+{
+	s[0] = (float)(px & 0xFFu); s[1] = (float)((px >> 8) & 0xFFu); s[2] = (float)((px >> 16) & 0xFFu); s[3] = (float)(px >> 24);    // v_cvt_f32_ubyte0..3
+}
+WV_FN void tensor_from_halves(uint64_t px, float s[4])
+{
+	for (int c = 0; c < 4; c++) s[c] = tensor_widen_half((uint16_t)(px >> (16 * c)));
+}
+WV_FN float tensor_from_source(const DecodeImage& img, const float src[7], int c)
+{
+	const float v = src[img.swz[c]];
+	return img.data_type == 1 ? tensor_through_half(v) : v;
+}
+
+/* The sink: the texel made s[0 .. 3] by the routines above, then one routine.
  * kType / kLayout: astcenc_amd_tensor_type / _layout. */
 template <uint32_t kType, uint32_t kLayout>
 struct TensorStore {
@@ -141,18 +177,18 @@ struct TensorStore {
 
 	WV_FN void pixel(const DecodeImage& img, int, size_t at, uint32_t px) const
 	{
-		const float s[4] = { (float)(px & 0xFFu), (float)((px >> 8) & 0xFFu), (float)((px >> 16) & 0xFFu), (float)(px >> 24) };    // v_cvt_f32_ubyte0..3
+		float s[4];
+		tensor_from_pixel(px, s);
 		this->template put<true>(img, at, s);
 	}
 	WV_FN void halves(const DecodeImage& img, int, size_t at, uint64_t px) const
 	{
 		float s[4];
-		for (int c = 0; c < 4; c++) s[c] = tensor_widen_half((uint16_t)(px >> (16 * c)));
+		tensor_from_halves(px, s);
 		this->template put<false>(img, at, s);
 	}
 	WV_FN void texel(const DecodeImage& img, int lane, size_t at, float r, float g, float b, float a) const
 	{
-		// (store_texel_at's three routes, into registers)
 		if (img.data_type == 0)
 		{
 			pixel(img, lane, at, pack_texel_u8(img, r, g, b, a));
@@ -160,30 +196,21 @@ struct TensorStore {
 		}
 		float src[7], s[4];
 		swizzle_sources(r, g, b, a, src);
-		for (int c = 0; c < 4; c++)
-		{
-			const float v = src[img.swz[c]];
-			s[c] = img.data_type == 1 ? tensor_through_half(v) : v;
-		}
+		for (int c = 0; c < 4; c++) s[c] = tensor_from_source(img, src, c);
 		this->template put<false>(img, at, s);
 	}
 	WV_FN void trip_end(int, int, int) const {}
 };
 
-inline size_t decode_tensors_bytes(uint32_t count)
-{
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeTensorRecord);
-}
+inline size_t decode_tensors_bytes(uint32_t count) { return decode_table_bytes<DecodeTensorRecord>(count); }
 
 /* Writes the table of `count` regions over the images `images` (prepared, `data` unused) and their streams; returns the runs
  * of all regions (the caller has made sure they fit 32 bits). */
 inline uint32_t decode_tensors_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format,
                                      const DecodeTensorLaunch* regions, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, decode_tensors_bytes(count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	DecodeTensorRecord* rec = reinterpret_cast<DecodeTensorRecord*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	DecodeTensorRecord* rec = decode_table_begin<DecodeTensorRecord>(out, decode_tensors_bytes(count), count, first);
 	uint32_t runs = 0;
 	for (uint32_t i = 0; i < count; i++)
 	{
@@ -197,15 +224,8 @@ inline uint32_t decode_tensors_build(void* out, const DecodeImage* images, const
 		r.win.w.row_texels = g.row_pitch;
 		r.win.w.slice_texels = g.slice_pitch;
 		r.win.flags = g.flags;
-		r.win.x_step = format.layout == 1 ? format.channels : 1u;
-		r.fmt.type = format.type; r.fmt.layout = format.layout; r.fmt.channels = format.channels;
-		for (int c = 0; c < 4; c++)
-		{
-			// (channels the format does not use: computed and dropped, so they are given harmless factors)
-			r.fmt.scale[c] = (uint32_t)c < format.channels ? format.scale[c] : 0.0f;
-			r.fmt.bias[c] = (uint32_t)c < format.channels ? format.bias[c] : 0.0f;
-		}
-		r.fmt.plane = g.plane_pitch;
+		r.win.x_step = tensor_x_step(format);
+		r.fmt = tensor_params(format, g.plane_pitch);
 		uint32_t rows, layers;
 		decode_region_cover(g.x, g.size_x, r.img.block_x, r.bx0, r.cols);
 		decode_region_cover(g.y, g.size_y, r.img.block_y, r.by0, rows);
@@ -215,10 +235,7 @@ inline uint32_t decode_tensors_build(void* out, const DecodeImage* images, const
 		first[i] = runs;
 		runs += r.runs_xy * layers;
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = runs;
-	return runs;
+	return decode_table_finish(out, count, runs);
 }
 
 /* Run `local` of the region of `rec` (all 64 lanes call this; `local` is uniform), as decode_region_run; kType / kLayout are

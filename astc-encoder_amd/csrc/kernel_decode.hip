@@ -7,10 +7,7 @@
 #include "wave_decode.h"
 #include "decode_regions.h"
 #include "decode_tensors.h"
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "decode_kernels.h"
 
 namespace astcd {
 
@@ -41,15 +38,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
 astc_decompress_set(const ImageSetTable* __restrict__ set, uint32_t run0)
 {
 	__shared__ DecodeBatch batch;
-	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
-	const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
-	const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
-	const __attribute__((address_space(4))) uint32_t* first = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
-	const uint32_t r = run0 + blockIdx.x;
-	const uint32_t e = image_set_find(first, count, r);
-	const DecodeSetEntry rec = image_set_record<DecodeSetEntry>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
-		t + image_set_records_offset(count) + (size_t)e * sizeof(DecodeSetEntry)));
-	const uint32_t local = r - first[e];
+	uint32_t local;
+	const DecodeSetEntry rec = decode_table_item<DecodeSetEntry>(set, run0 + blockIdx.x, local);
 	const uint32_t bz = local / rec.runs_xy;
 	const uint32_t in_layer = local - bz * rec.runs_xy;
 	const uint32_t by = in_layer / rec.runs_x;
@@ -65,16 +55,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
 astc_decode_regions(const ImageSetTable* __restrict__ set, uint32_t run0)
 {
 	__shared__ DecodeBatch batch;
-	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
-	const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
-	const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
-	const __attribute__((address_space(4))) uint32_t* first = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
-	const uint32_t r = run0 + blockIdx.x;
-	const uint32_t g = image_set_find(first, count, r);
-	const DecodeRegionRecord rec = image_set_record<DecodeRegionRecord>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
-		t + image_set_records_offset(count) + (size_t)g * sizeof(DecodeRegionRecord)));
+	uint32_t local;
+	const DecodeRegionRecord rec = decode_table_item<DecodeRegionRecord>(set, run0 + blockIdx.x, local);
 	DecodeStore store;
-	decode_region_run(rec, r - first[g], batch, store);
+	decode_region_run(rec, local, batch, store);
 }
 
 /* Windows decoded into tensors (astcenc_amd_decompress_tensors_device): astc_decode_regions with the tensor policies of
@@ -85,15 +69,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
 astc_decode_tensors(const ImageSetTable* __restrict__ set, uint32_t run0)
 {
 	__shared__ DecodeBatch batch;
-	typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
-	const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
-	const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
-	const __attribute__((address_space(4))) uint32_t* first = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(t + image_set_first_offset());
-	const uint32_t r = run0 + blockIdx.x;
-	const uint32_t g = image_set_find(first, count, r);
-	const DecodeTensorRecord rec = image_set_record<DecodeTensorRecord>(reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(
-		t + image_set_records_offset(count) + (size_t)g * sizeof(DecodeTensorRecord)));
-	decode_tensor_run<kType, kLayout>(rec, r - first[g], batch);
+	uint32_t local;
+	const DecodeTensorRecord rec = decode_table_item<DecodeTensorRecord>(set, run0 + blockIdx.x, local);
+	decode_tensor_run<kType, kLayout>(rec, local, batch);
 }
 
 size_t astc_decode_tables_bytes() { return sizeof(DecodeTables); }
@@ -103,38 +81,13 @@ void astc_decode_tables_build(void* out, uint32_t block_x, uint32_t block_y, uin
 	decode_tables_build(*static_cast<DecodeTables*>(out), (int)block_x, (int)block_y, (int)block_z);
 }
 
-static DecodeImage decode_image(const DecodeLaunch& d)
-{
-	DecodeImage img;
-	img.data = d.d_image;
-	img.tabs = static_cast<const DecodeTables*>(d.d_tables);
-	img.dim_x = d.dim_x; img.dim_y = d.dim_y; img.dim_z = d.dim_z;
-	img.data_type = d.data_type;
-	for (int i = 0; i < 4; i++) img.swz[i] = d.swz[i];
-	img.block_x = d.block_x; img.block_y = d.block_y; img.block_z = d.block_z;
-	img.blocks_x = (d.dim_x + d.block_x - 1) / d.block_x;
-	img.blocks_y = (d.dim_y + d.block_y - 1) / d.block_y;
-	img.blocks_z = (d.dim_z + d.block_z - 1) / d.block_z;
-	img.profile = d.profile;
-	decode_image_prepare(img);
-	return img;
-}
-
-// (ASTCENC_AMD_DECODE_GRID_LIMIT: a smaller limit for tests/test_decode.py, which cannot allocate a 262 144-row image)
-static uint32_t decode_grid_limit_from_env()
-{
-	const char* e = getenv("ASTCENC_AMD_DECODE_GRID_LIMIT");
-	const long v = e ? strtol(e, nullptr, 10) : 0;
-	return (uint32_t)(v >= 1 && v < 65535 ? v : 0);
-}
-
 int astc_decode_launch(const DecodeLaunch& d)
 {
-	const DecodeImage img = decode_image(d);
+	const DecodeImage img = decode_image_of(d, d.d_image);
 	// Grid y / z hold block rows / layers of blocks, at most 65535 each: a taller stream (more than 262 140 texel rows at the
 	// smallest footprint, or as many slices) is covered by several launches, each told where its rows and layers start.  The
 	// image record stays the whole image's, so every address is formed from the real dimensions.
-	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 65535u; }();
+	static const uint32_t limit = decode_grid_limit(65535u);
 	const uint32_t runs = (img.blocks_x + (uint32_t)DECODE_BATCH - 1u) / (uint32_t)DECODE_BATCH;
 	for (uint32_t layer0 = 0; layer0 < img.blocks_z; layer0 += limit)
 	{
@@ -148,45 +101,26 @@ int astc_decode_launch(const DecodeLaunch& d)
 	return (int)hipGetLastError();
 }
 
-size_t astc_decode_set_bytes(uint32_t count)
-{
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(DecodeSetEntry);
-}
+size_t astc_decode_set_bytes(uint32_t count) { return decode_table_bytes<DecodeSetEntry>(count); }
 
 uint32_t astc_decode_set_build(void* out, const DecodeLaunch* entries, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, astc_decode_set_bytes(count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	DecodeSetEntry* rec = reinterpret_cast<DecodeSetEntry*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	DecodeSetEntry* rec = decode_table_begin<DecodeSetEntry>(out, astc_decode_set_bytes(count), count, first);
 	uint32_t runs = 0;
 	for (uint32_t e = 0; e < count; e++)
 	{
-		rec[e].img = decode_image(entries[e]);
+		rec[e].img = decode_image_of(entries[e], entries[e].d_image);
 		rec[e].blocks = entries[e].d_blocks;
 		rec[e].runs_x = (rec[e].img.blocks_x + (uint32_t)DECODE_BATCH - 1u) / (uint32_t)DECODE_BATCH;
 		rec[e].runs_xy = rec[e].runs_x * rec[e].img.blocks_y;
 		first[e] = runs;
 		runs += rec[e].runs_xy * rec[e].img.blocks_z;
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = runs;
-	return runs;
+	return decode_table_finish(out, count, runs);
 }
 
-int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream)
-{
-	// grid x: at most 2^32 - 1 work-items in all, i.e. 2^26 - 1 wavefronts of 64 (or the test limit above)
-	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 0xFFFFFFFFu / 64u; }();
-	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);
-	for (uint32_t run0 = 0; run0 < runs; run0 += limit)
-	{
-		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
-		hipLaunchKernelGGL(astc_decompress_set, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
-	}
-	return (int)hipGetLastError();
-}
+int astc_decode_set_launch(const void* d_table, uint32_t runs, void* stream) { return decode_table_launch(astc_decompress_set, d_table, runs, stream); }
 
 unsigned long long astc_decode_region_runs(const DecodeRegionLaunch& r, uint32_t block_x, uint32_t block_y, uint32_t block_z)
 {
@@ -197,59 +131,25 @@ size_t astc_decode_regions_bytes(uint32_t count) { return decode_regions_bytes(c
 
 uint32_t astc_decode_regions_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeRegionLaunch* regions, uint32_t count)
 {
-	std::vector<DecodeImage> images(entry_count);
-	std::vector<const uint8_t*> streams(entry_count);
-	for (uint32_t e = 0; e < entry_count; e++)
-	{
-		images[e] = decode_image(entries[e]);
-		streams[e] = entries[e].d_blocks;
-	}
-	return decode_regions_build(out, images.data(), streams.data(), regions, count);
+	const DecodeEntries of(entries, entry_count);
+	return decode_regions_build(out, of.images.data(), of.streams.data(), regions, count);
 }
 
-int astc_decode_regions_launch(const void* d_table, uint32_t runs, void* stream)
-{
-	// (the grid of astc_decode_set_launch, and its test limit)
-	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 0xFFFFFFFFu / 64u; }();
-	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);
-	for (uint32_t run0 = 0; run0 < runs; run0 += limit)
-	{
-		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
-		hipLaunchKernelGGL(astc_decode_regions, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
-	}
-	return (int)hipGetLastError();
-}
+int astc_decode_regions_launch(const void* d_table, uint32_t runs, void* stream) { return decode_table_launch(astc_decode_regions, d_table, runs, stream); }
 
 size_t astc_decode_tensors_bytes(uint32_t count) { return decode_tensors_bytes(count); }
 
 uint32_t astc_decode_tensors_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format,
                                    const DecodeTensorLaunch* regions, uint32_t count)
 {
-	std::vector<DecodeImage> images(entry_count);
-	std::vector<const uint8_t*> streams(entry_count);
-	for (uint32_t e = 0; e < entry_count; e++)
-	{
-		images[e] = decode_image(entries[e]);
-		streams[e] = entries[e].d_blocks;
-	}
-	return decode_tensors_build(out, images.data(), streams.data(), format, regions, count);
+	const DecodeEntries of(entries, entry_count);
+	return decode_tensors_build(out, of.images.data(), of.streams.data(), format, regions, count);
 }
 
 int astc_decode_tensors_launch(const void* d_table, uint32_t runs, uint32_t type, uint32_t layout, void* stream)
 {
-	typedef void (*Kernel)(const ImageSetTable*, uint32_t);
-	static const Kernel kernels[3][2] = { { astc_decode_tensors<0, 0>, astc_decode_tensors<0, 1> }, { astc_decode_tensors<1, 0>, astc_decode_tensors<1, 1> },
-	                                      { astc_decode_tensors<2, 0>, astc_decode_tensors<2, 1> } };
-	if (type > 2 || layout > 1) return (int)hipErrorInvalidValue;
-	// (the grid of astc_decode_set_launch, and its test limit)
-	static const uint32_t limit = []() { const uint32_t v = decode_grid_limit_from_env(); return v ? v : 0xFFFFFFFFu / 64u; }();
-	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);
-	for (uint32_t run0 = 0; run0 < runs; run0 += limit)
-	{
-		const uint32_t n = runs - run0 < limit ? runs - run0 : limit;
-		hipLaunchKernelGGL(kernels[type][layout], dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), set, run0);
-	}
-	return (int)hipGetLastError();
+	static const DecodeTableKernel builds[3][2] = DECODE_TENSOR_BUILDS(astc_decode_tensors);
+	return decode_table_launch(builds, type, layout, d_table, runs, stream);
 }
 
 } // namespace astcd

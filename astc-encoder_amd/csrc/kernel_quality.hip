@@ -16,9 +16,7 @@
 #define ASTC_ENABLE_HDR 1
 #include "backend.h"
 #include "wave_quality.h"
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <cstring>
+#include "decode_kernels.h"
 
 namespace astcd {
 
@@ -36,9 +34,6 @@ struct QualitySetEntry {
 	uint32_t pad;
 };
 
-typedef const __attribute__((address_space(4))) uint8_t* constant_bytes;
-typedef const __attribute__((address_space(4))) uint32_t* constant_words;
-
 /* Run run0 + blockIdx.x of the set; its sums go to slot blockIdx.x of the partials (quantity i at partials[i * stride + slot]).
  * set == null: the set is the one entry `one`. */
 template <bool HDR>
@@ -50,15 +45,7 @@ astc_quality_set(const ImageSetTable* __restrict__ set, QualitySetEntry one, uin
 	const uint32_t r = run0 + blockIdx.x;
 	QualitySetEntry rec = one;
 	uint32_t local = r;
-	if (set)
-	{
-		const constant_bytes t = (constant_bytes)reinterpret_cast<uintptr_t>(set);
-		const uint32_t count = reinterpret_cast<const __attribute__((address_space(4))) ImageSetTable*>(t)->count;
-		const constant_words first = reinterpret_cast<constant_words>(t + image_set_first_offset());
-		const uint32_t e = image_set_find(first, count, r);
-		rec = image_set_record<QualitySetEntry>(reinterpret_cast<constant_words>(t + image_set_records_offset(count) + (size_t)e * sizeof(QualitySetEntry)));
-		local = r - first[e];
-	}
+	if (set) rec = decode_table_item<QualitySetEntry>(set, r, local);
 	const uint32_t bz = local / rec.runs_xy;
 	const uint32_t in_layer = local - bz * rec.runs_xy;
 	const uint32_t by = in_layer / rec.runs_x;
@@ -120,35 +107,19 @@ astc_quality_finish(const ImageSetTable* __restrict__ set, uint32_t total, uint3
 	}
 }
 
-size_t astc_quality_set_bytes(uint32_t count)
-{
-	return (size_t)image_set_records_offset(count) + (size_t)count * sizeof(QualitySetEntry);
-}
+size_t astc_quality_set_bytes(uint32_t count) { return decode_table_bytes<QualitySetEntry>(count); }
 
 size_t astc_quality_scratch_doubles() { return (size_t)QUALITY_MAX_RUNS * METRIC_SUMS_HDR; }
 
 uint32_t astc_quality_set_build(void* out, const QualityLaunch* entries, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	memset(t, 0, astc_quality_set_bytes(count));
-	uint32_t* first = reinterpret_cast<uint32_t*>(t + image_set_first_offset());
-	QualitySetEntry* rec = reinterpret_cast<QualitySetEntry*>(t + image_set_records_offset(count));
+	uint32_t* first;
+	QualitySetEntry* rec = decode_table_begin<QualitySetEntry>(out, astc_quality_set_bytes(count), count, first);
 	uint32_t runs = 0;
 	for (uint32_t e = 0; e < count; e++)
 	{
 		const DecodeLaunch& d = entries[e].decode;
-		DecodeImage& img = rec[e].img;
-		img.data = nullptr;
-		img.tabs = static_cast<const DecodeTables*>(d.d_tables);
-		img.dim_x = d.dim_x; img.dim_y = d.dim_y; img.dim_z = d.dim_z;
-		img.data_type = d.data_type;
-		for (int i = 0; i < 4; i++) img.swz[i] = d.swz[i];
-		img.block_x = d.block_x; img.block_y = d.block_y; img.block_z = d.block_z;
-		img.blocks_x = (d.dim_x + d.block_x - 1) / d.block_x;
-		img.blocks_y = (d.dim_y + d.block_y - 1) / d.block_y;
-		img.blocks_z = (d.dim_z + d.block_z - 1) / d.block_z;
-		img.profile = d.profile;
-		decode_image_prepare(img);
+		const DecodeImage& img = rec[e].img = decode_image_of(d, nullptr);
 		rec[e].blocks = d.d_blocks;
 		rec[e].original = entries[e].d_original;
 		rec[e].original_type = entries[e].original_type;
@@ -158,21 +129,14 @@ uint32_t astc_quality_set_build(void* out, const QualityLaunch* entries, uint32_
 		first[e] = runs;
 		runs += rec[e].runs_xy * img.blocks_z;
 	}
-	ImageSetTable* h = reinterpret_cast<ImageSetTable*>(t);
-	h->count = count;
-	h->total = runs;
-	return runs;
+	return decode_table_finish(out, count, runs);
 }
 
 int astc_quality_set_launch(const void* h_table, const void* d_table, double* d_partials, double* d_sums, int hdr, int fstop_lo, int fstop_hi, void* stream)
 {
-	// (ASTCENC_AMD_DECODE_GRID_LIMIT, kernel_decode.hip: the decoder's test limit on a launch is the limit on a piece here)
-	static const uint32_t piece_runs = []()
-	{
-		const char* e = getenv("ASTCENC_AMD_DECODE_GRID_LIMIT");
-		const long v = e ? strtol(e, nullptr, 10) : 0;
-		return (uint32_t)(v >= 1 && v < (long)QUALITY_MAX_RUNS ? v : (long)QUALITY_MAX_RUNS);
-	}();
+	// (the decoder's test limit on a launch is the limit on a piece here; the loop below cuts its launches where entries and
+	//  pieces end and queues a finish pass behind each, so it is not decode_table_launch's)
+	static const uint32_t piece_runs = decode_grid_limit(QUALITY_MAX_RUNS, (long)QUALITY_MAX_RUNS);
 	const ImageSetTable* h = static_cast<const ImageSetTable*>(h_table);
 	const uint32_t* first = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(h_table) + image_set_first_offset());
 	const ImageSetTable* set = static_cast<const ImageSetTable*>(d_table);       // (null for a set of one entry)

@@ -1,35 +1,11 @@
 // SPDX-License-Identifier: Apache-2.0
-// What the two samplers' entry points share (astcenc_sample.cpp, astcenc_lod.cpp): the checks of the format, of the sampler's
-// filter and address modes, of the entries' block counts and of a grid's points, coordinates and output, with the sample call's
-// error codes and log lines.  `fn` names the entry point in the log.
+// What the two samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp): the checks of the
+// sampler's filter and address modes, of the footprint, of the entries' block counts and of a grid's points and coordinates, with
+// the sample call's error codes and log lines.  `fn` names the entry point in the log.
 #pragma once
 #include "regions_internal.h"
 
-#include <cmath>
-
 namespace astcd {
-
-/* The format's type, layout and channels. */
-inline astcenc_error check_sample_format(const char* fn, const astcenc_amd_tensor_format* format)
-{
-	if (!format)
-	{
-		backend_log("%s: format is null", fn);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if ((int)format->type < ASTCENC_AMD_TENSOR_F32 || (int)format->type > ASTCENC_AMD_TENSOR_BF16 ||
-	    (int)format->layout < ASTCENC_AMD_TENSOR_PLANAR || (int)format->layout > ASTCENC_AMD_TENSOR_INTERLEAVED)
-	{
-		backend_log("%s: format: type %d, layout %d: not a tensor type / layout", fn, (int)format->type, (int)format->layout);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if (format->channels < 1 || format->channels > 4)
-	{
-		backend_log("%s: format: %u channels: 1 to 4 can be had", fn, format->channels);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	return ASTCENC_SUCCESS;
-}
 
 /* The sampler's filter and address modes. */
 inline astcenc_error check_sample_modes(const char* fn, int filter, int address_x, int address_y)
@@ -47,27 +23,13 @@ inline astcenc_error check_sample_modes(const char* fn, int filter, int address_
 	return ASTCENC_SUCCESS;
 }
 
-/* The context's footprint is 2D and the (checked) format's factors are finite; fmt: the format for the backend. */
-inline astcenc_error check_sample_factors(const char* fn, const astcenc_context* ctx, const astcenc_amd_tensor_format* format, DecodeTensorFormat& fmt)
+/* The context's footprint is 2D. */
+inline astcenc_error check_sample_footprint(const char* fn, const astcenc_context* ctx)
 {
-	if (ctx->config.block_z > 1)
-	{
-		backend_log("%s: the context's footprint %ux%ux%u is 3D: images of 2D footprints are sampled", fn, ctx->config.block_x, ctx->config.block_y,
-		            ctx->config.block_z);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	memset(&fmt, 0, sizeof(fmt));
-	fmt.type = (uint32_t)format->type; fmt.layout = (uint32_t)format->layout; fmt.channels = format->channels;
-	for (unsigned int c = 0; c < format->channels; c++)
-	{
-		if (!std::isfinite(format->scale[c]) || !std::isfinite(format->bias[c]))
-		{
-			backend_log("%s: format: scale %g, bias %g of channel %u: not finite", fn, (double)format->scale[c], (double)format->bias[c], c);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		fmt.scale[c] = format->scale[c]; fmt.bias[c] = format->bias[c];
-	}
-	return ASTCENC_SUCCESS;
+	if (ctx->config.block_z <= 1) return ASTCENC_SUCCESS;
+	backend_log("%s: the context's footprint %ux%ux%u is 3D: images of 2D footprints are sampled", fn, ctx->config.block_x, ctx->config.block_y,
+	            ctx->config.block_z);
+	return ASTCENC_ERR_BAD_PARAM;
 }
 
 /* Every entry as the windowed decoders check it, and no entry of 2^32 - 1 blocks or more (a tap's block is a 32-bit index in the
@@ -103,8 +65,6 @@ struct SampleGridShape {
 
 inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, SampleGridShape& g)
 {
-	const bool planar = format->layout == ASTCENC_AMD_TENSOR_PLANAR;
-	const size_t element = format->type == ASTCENC_AMD_TENSOR_F32 ? 4 : 2;
 	if (g.out_x == 0 || g.out_y == 0 || g.out_x > 65535 || g.out_y > 65535)
 	{
 		backend_log("%s: grid %u of %u: %u x %u points: either size is 1 to 65535", fn, i, grid_count, g.out_x, g.out_y);
@@ -115,45 +75,21 @@ inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned 
 		backend_log("%s: grid %u of %u: coord_row_pitch %zu: even and at least %zu floats", fn, i, grid_count, g.coord_row_pitch, 2u * (size_t)g.out_x);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
-	// pitches in elements, every product in 64 bits: the tensor's extent in bytes must fit them too
+	// (the coordinates' extent in bytes fits 64 bits too: reported with the output's products)
 	bool overflow = false;
-	const size_t tight_row = mul_safe(g.out_x, planar ? 1 : format->channels, overflow);
-	const size_t row_pitch = g.row_pitch ? g.row_pitch : tight_row;
-	const size_t tight_plane = mul_safe(row_pitch, g.out_y, overflow);
-	const size_t plane_pitch = g.plane_pitch ? g.plane_pitch : tight_plane;
-	(void)mul_safe(planar ? mul_safe(plane_pitch, format->channels, overflow) : tight_plane, element, overflow);
 	const size_t coord_row_pitch = g.coord_row_pitch ? g.coord_row_pitch : 2u * (size_t)g.out_x;
 	(void)mul_safe(mul_safe(coord_row_pitch, g.out_y, overflow), sizeof(float), overflow);
-	if (overflow || row_pitch < tight_row || (planar && plane_pitch < tight_plane))
-	{
-		backend_log("%s: grid %u of %u: row_pitch %zu, plane_pitch %zu: the output needs at least %zu and %zu elements", fn, i, grid_count, g.row_pitch,
-		            g.plane_pitch, tight_row, tight_plane);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if (!planar && g.plane_pitch != 0)
-	{
-		backend_log("%s: grid %u of %u: plane_pitch %zu: the interleaved layout has no planes", fn, i, grid_count, g.plane_pitch);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	// (a null buffer: what the other device calls return for one)
-	if (!g.out || !g.coords)
-	{
-		backend_log("%s: grid %u of %u: %s is null", fn, i, grid_count, !g.out ? "out" : "coords");
-		return ASTCENC_ERR_BAD_CONTEXT;
-	}
-	if (reinterpret_cast<uintptr_t>(g.out) % element != 0)
-	{
-		backend_log("%s: grid %u of %u: out %p is not aligned to the element size %zu", fn, i, grid_count, g.out, element);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
+	TensorPitches pitches = { g.row_pitch, 0, g.plane_pitch };
+	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.coords ? "coords" : nullptr);
+	if (status != ASTCENC_SUCCESS) return status;
 	if (reinterpret_cast<uintptr_t>(g.coords) % 8 != 0)
 	{
 		backend_log("%s: grid %u of %u: coords %p is not aligned to a pair of floats (8 bytes)", fn, i, grid_count, static_cast<const void*>(g.coords));
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	g.coord_row_pitch = coord_row_pitch;
-	g.row_pitch = row_pitch;
-	g.plane_pitch = planar ? plane_pitch : 0;
+	g.row_pitch = pitches.row;
+	g.plane_pitch = pitches.plane;
 	return ASTCENC_SUCCESS;
 }
 

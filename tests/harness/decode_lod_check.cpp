@@ -26,6 +26,8 @@
 #define ASTC_ENABLE_HDR 1
 #include "backend.h"
 #include "decode_lod.h"
+#define DECODE_CHECK_ITEM "grid"
+#include "decode_check_common.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
@@ -34,37 +36,10 @@
 #include <set>
 #include <vector>
 
-using namespace astcd;
-
-static uint64_t g_x = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { g_x ^= g_x << 13; g_x ^= g_x >> 7; g_x ^= g_x << 17; return (uint32_t)(g_x >> 16); }
-static float rnd_unit() { return (float)(rnd() & 0xFFFFFFu) / 16777216.0f; }
-
-static long g_checked = 0, g_bad = 0;
 static unsigned long long g_decoded = 0, g_batches = 0, g_passes = 0, g_tiles = 0;
 static unsigned g_pairs_seen = 0;              // bit (address_x * 4 + address_y)
 static uint32_t g_most_levels = 0;             // the most distinct levels a tile had
 static bool g_blended = false, g_single = false;
-
-static void fail(const char* what, const char* tag, long grid, long at)
-{
-	if (++g_bad <= 20) fprintf(stderr, "%s: %s (grid %ld, at %ld)\n", tag, what, grid, at);
-}
-
-static DecodeImage make_image(int bx, int by, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, int profile, uint32_t dtype, const DecodeTables* tabs)
-{
-	DecodeImage img;
-	memset(&img, 0, sizeof(img));
-	img.dim_x = dim_x; img.dim_y = dim_y; img.dim_z = dim_z;
-	img.data_type = dtype;
-	for (uint32_t i = 0; i < 4; i++) img.swz[i] = i;
-	img.block_x = bx; img.block_y = by; img.block_z = 1;
-	img.blocks_x = (dim_x + bx - 1) / bx; img.blocks_y = (dim_y + by - 1) / by; img.blocks_z = dim_z;
-	img.profile = (uint32_t)profile;
-	decode_image_prepare(img);
-	img.tabs = tabs;
-	return img;
-}
 
 /* A chain: per level the image, its stream and what the decoder writes for the whole of it. */
 struct Chain {
@@ -73,27 +48,7 @@ struct Chain {
 	uint32_t levels() const { return (uint32_t)images.size(); }
 };
 
-/* The model (include/astcenc_amd.h), one operation at a time: component c of a whole level's texel, widened to binary64 ... */
-static double source_value(const uint8_t* texel, uint32_t dtype, uint32_t c)
-{
-	if (dtype == 0) return (double)texel[c];
-	if (dtype == 1)
-	{
-		uint16_t h;
-		memcpy(&h, texel + 2 * c, 2);
-		// exact widening, written out: sign, exponent, mantissa
-		const uint32_t e = (h >> 10) & 31u, m = h & 0x3FFu;
-		double v;
-		if (e == 31) v = m ? __builtin_nan("") : __builtin_inf();
-		else if (e != 0) v = __builtin_ldexp((double)(m | 0x400u), (int)e - 25);
-		else v = __builtin_ldexp((double)m, -24);
-		return (h & 0x8000u) ? -v : v;
-	}
-	float f;
-	memcpy(&f, texel + 4 * c, 4);
-	return (double)f;
-}
-
+/* The model (include/astcenc_amd.h), one operation at a time: a texel's component widened (source_value, decode_check_common.h) ... */
 /* ... the taps of a binary64 level coordinate along an axis: indices before addressing and weights in tap order, zero weights
  * left out ... */
 struct Tap { int64_t i; double w; };
@@ -200,34 +155,6 @@ static float model_point(const Chain& ch, const DecodeLodSampler& smp, uint32_t 
 	return (float)sum;
 }
 
-/* ... scaled and shifted with two roundings, and the bits it is stored as (type 0 F32, 1 F16, 2 BF16). */
-static uint32_t model_bits(float s, float scale, float bias, uint32_t type)
-{
-	volatile float t = s * scale;
-	volatile float yv = t + bias;
-	const float y = yv;
-	uint32_t u;
-	memcpy(&u, &y, 4);
-	const bool nan = (u & 0x7FFFFFFFu) > 0x7F800000u;
-	if (type == 0) return nan ? 0x7FC00000u : u;
-	if (type == 2) return nan ? 0x7FC0u : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-	if (nan) return 0x7E00u;
-	// binary16, round to nearest even, from the integer fields
-	const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
-	if (a >= 0x7F800000u) return sign | 0x7C00u;
-	const int e = (int)(a >> 23) - 127;
-	if (e > 15) return sign | 0x7C00u;
-	uint64_t m = (a & 0x7FFFFFu) | (a >> 23 ? 0x800000u : 0u);
-	const int ee = a >> 23 ? e : -126;
-	int shift = ee >= -14 ? 13 : 13 + (-14 - ee);
-	if (shift > 40) return sign;
-	const uint64_t q = m >> shift, rem = m & (((uint64_t)1 << shift) - 1u), half = (uint64_t)1 << (shift - 1);
-	uint64_t r = q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u);
-	const uint32_t out = ee >= -14 ? (uint32_t)(((uint64_t)(ee + 14) << 10) + r) : (uint32_t)r;
-	return out >= 0x7C00u ? sign | 0x7C00u : sign | out;
-}
-
-struct Format { uint32_t type, layout, channels; };
 struct Grid { uint32_t z, ox, oy; std::vector<float> uv; std::vector<float> lod; bool has_lod; float bias; };       // uv: ox * oy pairs, row by row
 
 template <class Fn>

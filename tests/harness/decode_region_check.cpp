@@ -15,22 +15,11 @@
 #define ASTC_ENABLE_HDR 1
 #include "backend.h"
 #include "decode_regions.h"
+#include "decode_check_common.h"
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
 #include <vector>
-
-using namespace astcd;
-
-static uint64_t g_x = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { g_x ^= g_x << 13; g_x ^= g_x >> 7; g_x ^= g_x << 17; return (uint32_t)(g_x >> 16); }
-
-static long g_checked = 0, g_bad = 0;
-
-static void fail(const char* what, const char* tag, long region, long at)
-{
-	if (++g_bad <= 20) fprintf(stderr, "%s: %s (region %ld, at %ld)\n", tag, what, region, at);
-}
 
 /* The decoder's store, counting the trips of the texel phase. */
 struct CountingStore : DecodeStore {
@@ -39,22 +28,6 @@ struct CountingStore : DecodeStore {
 };
 
 struct Window { uint32_t x, y, z, sx, sy, sz; };
-
-static DecodeImage make_image(int bx, int by, int bz, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, int profile, uint32_t dtype, const uint32_t swz[4],
-                              const DecodeTables* tabs)
-{
-	DecodeImage img;
-	memset(&img, 0, sizeof(img));
-	img.dim_x = dim_x; img.dim_y = dim_y; img.dim_z = dim_z;
-	img.data_type = dtype;
-	for (int i = 0; i < 4; i++) img.swz[i] = swz[i];
-	img.block_x = bx; img.block_y = by; img.block_z = bz;
-	img.blocks_x = (dim_x + bx - 1) / bx; img.blocks_y = (dim_y + by - 1) / by; img.blocks_z = (dim_z + bz - 1) / bz;
-	img.profile = (uint32_t)profile;
-	decode_image_prepare(img);
-	img.tabs = tabs;
-	return img;
-}
 
 static void check(int bx, int by, int bz, int profile, uint32_t dtype, const uint32_t swz[4])
 {

@@ -17,99 +17,13 @@
 #define ASTC_ENABLE_HDR 1
 #include "backend.h"
 #include "decode_tensors.h"
+#include "decode_check_common.h"
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-using namespace astcd;
-
-static uint64_t g_x = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { g_x ^= g_x << 13; g_x ^= g_x >> 7; g_x ^= g_x << 17; return (uint32_t)(g_x >> 16); }
-
-static long g_checked = 0, g_bad = 0;
-
-static void fail(const char* what, const char* tag, long region, long at)
-{
-	if (++g_bad <= 20) fprintf(stderr, "%s: %s (region %ld, at %ld)\n", tag, what, region, at);
-}
-
 struct Window { uint32_t x, y, z, sx, sy, sz; };
-
-static DecodeImage make_image(int bx, int by, int bz, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, int profile, uint32_t dtype, const uint32_t swz[4],
-                              const DecodeTables* tabs)
-{
-	DecodeImage img;
-	memset(&img, 0, sizeof(img));
-	img.dim_x = dim_x; img.dim_y = dim_y; img.dim_z = dim_z;
-	img.data_type = dtype;
-	for (int i = 0; i < 4; i++) img.swz[i] = swz[i];
-	img.block_x = bx; img.block_y = by; img.block_z = bz;
-	img.blocks_x = (dim_x + bx - 1) / bx; img.blocks_y = (dim_y + by - 1) / by; img.blocks_z = (dim_z + bz - 1) / bz;
-	img.profile = (uint32_t)profile;
-	decode_image_prepare(img);
-	img.tabs = tabs;
-	return img;
-}
-
-/* The model (include/astcenc_amd.h), one operation at a time: component c of the whole image's texel as binary32 ... */
-static float source_value(const uint8_t* texel, uint32_t dtype, uint32_t c)
-{
-	if (dtype == 0) return (float)texel[c];
-	if (dtype == 1)
-	{
-		uint16_t h;
-		memcpy(&h, texel + 2 * c, 2);
-		// exact widening, written out: sign, exponent, mantissa
-		const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
-		uint32_t bits;
-		if (e == 31) bits = sign | 0x7F800000u | (m << 13);
-		else if (e != 0) bits = sign | ((e + 112u) << 23) | (m << 13);
-		else
-		{
-			float f = (float)m * (1.0f / 16777216.0f);          // m * 2^-24, exact
-			memcpy(&bits, &f, 4);
-			bits |= sign;
-		}
-		float f;
-		memcpy(&f, &bits, 4);
-		return f;
-	}
-	float f;
-	memcpy(&f, texel + 4 * c, 4);
-	return f;
-}
-
-/* ... scaled and shifted with two roundings, and the bits it is stored as (type 0 F32, 1 F16, 2 BF16). */
-static uint32_t model_bits(float s, float scale, float bias, uint32_t type)
-{
-	volatile float t = s * scale;
-	volatile float yv = t + bias;
-	const float y = yv;
-	uint32_t u;
-	memcpy(&u, &y, 4);
-	const bool nan = (u & 0x7FFFFFFFu) > 0x7F800000u;
-	if (type == 0) return nan ? 0x7FC00000u : u;
-	if (type == 2) return nan ? 0x7FC0u : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-	if (nan) return 0x7E00u;
-	// binary16, round to nearest even, from the integer fields
-	const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
-	if (a >= 0x7F800000u) return sign | 0x7C00u;
-	const int e = (int)(a >> 23) - 127;
-	if (e > 15) return sign | 0x7C00u;
-	uint64_t m = (a & 0x7FFFFFu) | (a >> 23 ? 0x800000u : 0u);       // 24-bit significand, value m * 2^(e - 23) (subnormal floats: e = -126 by the next line)
-	const int ee = a >> 23 ? e : -126;
-	// result in units of 2^-24 (the binary16 subnormal step) when below 2^-14, else normal with 10 fraction bits
-	int shift = ee >= -14 ? 13 : 13 + (-14 - ee);
-	if (shift > 40) return sign;
-	const uint64_t q = m >> shift, rem = m & (((uint64_t)1 << shift) - 1u), half = (uint64_t)1 << (shift - 1);
-	uint64_t r = q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u);
-	// r holds the implicit bit at 1 << 10 for normals: adding the biased exponent - 1 folds a mantissa carry into the exponent
-	const uint32_t out = ee >= -14 ? (uint32_t)(((uint64_t)(ee + 14) << 10) + r) : (uint32_t)r;
-	return out >= 0x7C00u ? sign | 0x7C00u : sign | out;
-}
-
-struct Format { uint32_t type, layout, channels; };
 
 static void check_format(const char* image_tag, const DecodeImage& img, const std::vector<uint8_t>& blocks, const std::vector<uint8_t>& whole,
                          const std::vector<Window>& windows, DecodeBatch& batch, const Format& f, uint32_t flip0)
@@ -195,7 +109,7 @@ static void check_format(const char* image_tag, const DecodeImage& img, const st
 					const uint32_t xo = (r.flags & 1u) ? r.size_x - 1u - x : x, yo = (r.flags & 2u) ? r.size_y - 1u - j : j;
 					for (uint32_t c = 0; c < f.channels; c++)
 					{
-						const uint32_t bits = model_bits(source_value(texel, dtype, c), format.scale[c], format.bias[c], f.type);
+						const uint32_t bits = model_bits((float)source_value(texel, dtype, c), format.scale[c], format.bias[c], f.type);
 						const size_t at = planar ? c * r.plane_pitch + k * r.slice_pitch + yo * r.row_pitch + xo : k * r.slice_pitch + yo * r.row_pitch + (size_t)xo * f.channels + c;
 						memcpy(want.data() + guard + at * eb, &bits, eb);
 					}
