@@ -4,7 +4,8 @@
 The rest of the GPU suite runs with ASTCENC_AMD_JIT=off (tests/conftest.py), i.e. on the library's generic builds; by default
 a user's context runs a build compiled for it, with its records as constants.  This module puts those builds through
   (a) every footprint (14 2D, 10 3D) x preset x profile,
-  (b) the per-call input paths the records do not hold (swizzles, f16 / f32 input, tiny and partial images, thin volumes),
+  (b) the per-call input paths the records do not hold (swizzles, f16 / f32 input, texels outside the format's range under LDR
+      and HDR -- tests/input_cases.py --, tiny and partial images, thin volumes),
   (c) the records that turn into literals (channel weights, flags, alpha-scale radius, hand-edited search limits),
   (d) several device slots,
   (e) a deliberately wrong build against the self-check that gates every adoption,
@@ -30,6 +31,7 @@ import numpy as np
 import pytest
 
 import images
+import input_cases
 from jit_builds import apply_tweak, is_jit, prewarm
 from test_gpu_parity import FLAGS_AND_SWIZZLES, LIVE, low_m_image
 from test_multi_device import _Devices
@@ -51,6 +53,8 @@ TAIL_FOOTPRINTS = [(10, 8), (12, 12), (5, 4, 4), (5, 5, 5), (6, 5, 5)]
 # one footprint per tail class, for the per-call paths of (b): 20, 30, 64, 50, 80, 144, 80 (3D), 125 texels
 PATH_FOOTPRINTS = [(5, 4), (6, 5), (8, 8), (10, 5), (10, 8), (12, 12), (5, 4, 4), (5, 5, 5)]
 RECORD_FOOTPRINTS = [(6, 6), (6, 5), (10, 8)]
+# ... of which these take the out-of-range content of tests/input_cases.py under the HDR profile as well
+HDR_PATH_FOOTPRINTS = [(5, 4), (8, 8), (10, 8)]
 
 
 def _matrix_contexts():
@@ -217,15 +221,19 @@ def _path_images(block):
         partial = np.ascontiguousarray(u8[:block[2] + 1, :2 * block[1] + 1, :3 * block[0] + 1])
         thin = [("fewer slices than the block is deep", np.ascontiguousarray(u8[:block[2] - 2]), A.SWZ_RGBA)]
     wide = u8.astype(np.float32) / np.float32(255.0) * np.float32(1.5) - np.float32(0.25)         # -0.25 .. 1.25
+    ba01 = input_cases.SWIZZLES["ba01"]
+    spoilt = [("%s %s B,A,0,1" % (cls, dtype), input_cases.content(input_cases.Case(cls, dtype, "ba01"), block), ba01)
+              for cls in ("nonfinite", "tiny") for dtype in ("f16", "f32")]                       # (tests/input_cases.py)
     return [("B,G,R,1", u8, bgr1), ("R,R,R,G", u8, rrrg), ("f16", wide.astype(np.float16), A.SWZ_RGBA), ("f32", wide, A.SWZ_RGBA),
             ("f16 swizzled", wide.astype(np.float16), bgr1), ("1x1", tiny[0], A.SWZ_RGBA), ("3x2", tiny[1], A.SWZ_RGBA),
-            ("one partial block column and row", partial, A.SWZ_RGBA)] + thin
+            ("one partial block column and row", partial, A.SWZ_RGBA)] + spoilt + thin
 
 
 @pytest.mark.parametrize("block", PATH_FOOTPRINTS, ids=lambda b: "x".join(map(str, b)))
 def test_per_call_input_paths(product, ref, jit_sync, block):
-    """(b) swizzled RGBA8, f16 / f32 with values outside [0, 1], images smaller than a block, a partial last column and row, a
-    volume thinner than the block: properties of the call, not of the records -- the self-check never sees them."""
+    """(b) swizzled RGBA8, f16 / f32 with values outside [0, 1], non-finite and subnormal texels, images smaller than a block, a
+    partial last column and row, a volume thinner than the block: properties of the call, not of the records -- the self-check
+    never sees them."""
     ctx = (A.PRF_LDR, block, A.PRE_MEDIUM, 0)
     assert is_jit(jit_sync["names"][_key(ctx)]), ("refused", ctx)
     bad = []
@@ -235,6 +243,26 @@ def test_per_call_input_paths(product, ref, jit_sync, block):
         assert is_jit(used), (ctx, name, used)
         if n:
             bad.append((name, n, "generic build: %d" % n_generic))
+    assert not bad, (ctx, bad)
+    if block in HDR_PATH_FOOTPRINTS:
+        _hdr_input_paths(product, ref, jit_sync, block)
+
+
+def _hdr_input_paths(product, ref, jit_sync, block):
+    """... and under the HDR profile, where the loader converts to LNS: values above the largest half, negatives, subnormals,
+    NaN and infinities (tests/input_cases.py), as F16 and F32, through the identity and a swizzle with constants."""
+    ctx = (A.PRF_HDR, block, A.PRE_MEDIUM, 0)
+    assert is_jit(jit_sync["names"][_key(ctx)]), ("refused", ctx)
+    bad = []
+    for cls in ("huge", "nonfinite"):
+        for dtype in ("f16", "f32"):
+            for swz in ("rgba", "ba01"):
+                name = "%s %s %s" % (cls, dtype, swz)
+                n, n_generic, used = _run(product, ref, ctx, input_cases.image(cls, dtype), input_cases.SWIZZLES[swz])
+                print("%-30s %-34s %s" % (ctx, name, used))
+                assert is_jit(used), (ctx, name, used)
+                if n:
+                    bad.append((name, n, "generic build: %d" % n_generic))
     assert not bad, (ctx, bad)
 
 
