@@ -28,11 +28,8 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 	}
 	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
 	if (status != ASTCENC_SUCCESS) return status;
-	if ((int)sampler->mip_filter != ASTCENC_AMD_MIP_NEAREST && (int)sampler->mip_filter != ASTCENC_AMD_MIP_LINEAR)
-	{
-		backend_log("%s: sampler: mip_filter %d: not a mip filter", fn, (int)sampler->mip_filter);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
+	status = check_mip_level_filter(fn, (int)sampler->mip_filter);
+	if (status != ASTCENC_SUCCESS) return status;
 	status = check_sample_footprint(fn, ctx);
 	if (status != ASTCENC_SUCCESS) return status;
 	DecodeTensorFormat fmt;
@@ -48,17 +45,8 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 	for (unsigned int i = 0; i < grid_count; i++)
 	{
 		const astcenc_amd_lod_grid& g = grids[i];
-		if (g.level_count == 0 || g.level_count > 32)
-		{
-			backend_log("%s: grid %u of %u: %u levels: a chain has 1 to 32", fn, i, grid_count, g.level_count);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		if ((unsigned long long)g.first_entry + g.level_count > entry_count)
-		{
-			backend_log("%s: grid %u of %u: levels are entries %u to %llu, the call has %u entries", fn, i, grid_count, g.first_entry,
-			            (unsigned long long)g.first_entry + g.level_count - 1, entry_count);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
+		status = check_lod_chain(fn, i, grid_count, g.first_entry, g.level_count, entry_count);
+		if (status != ASTCENC_SUCCESS) return status;
 		for (unsigned int l = 0; l < g.level_count; l++)
 		{
 			const astcenc_amd_image_set_entry& en = entries[g.first_entry + l];
@@ -76,32 +64,14 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 				return ASTCENC_ERR_BAD_PARAM;
 			}
 		}
-		if (!std::isfinite(g.lod_bias))
-		{
-			backend_log("%s: grid %u of %u: lod_bias %g: not finite", fn, i, grid_count, (double)g.lod_bias);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		if (g.lod_row_pitch != 0 && g.lod_row_pitch < g.out_x)
-		{
-			backend_log("%s: grid %u of %u: lod_row_pitch %zu: at least %u floats", fn, i, grid_count, g.lod_row_pitch, g.out_x);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
+		status = check_lod_pitch(fn, i, grid_count, g.lod_bias, g.lod_row_pitch, g.out_x);
+		if (status != ASTCENC_SUCCESS) return status;
 		SampleGridShape shape = { g.out_x, g.out_y, g.coords, g.coord_row_pitch, g.out, g.row_pitch, g.plane_pitch };
 		status = check_sample_grid(fn, i, grid_count, format, shape);
 		if (status != ASTCENC_SUCCESS) return status;
-		const size_t lod_row_pitch = g.lod_row_pitch ? g.lod_row_pitch : g.out_x;
-		bool overflow = false;
-		(void)mul_safe(mul_safe(lod_row_pitch, g.out_y, overflow), sizeof(float), overflow);
-		if (overflow)
-		{
-			backend_log("%s: grid %u of %u: lod_row_pitch %zu: the levels of detail do not fit 64 bits", fn, i, grid_count, g.lod_row_pitch);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		if (reinterpret_cast<uintptr_t>(g.lod) % 4 != 0)
-		{
-			backend_log("%s: grid %u of %u: lod %p is not aligned to a float (4 bytes)", fn, i, grid_count, static_cast<const void*>(g.lod));
-			return ASTCENC_ERR_BAD_PARAM;
-		}
+		size_t lod_row_pitch = g.lod_row_pitch;
+		status = check_lod_buffer(fn, i, grid_count, g.lod, lod_row_pitch, g.out_x, g.out_y);
+		if (status != ASTCENC_SUCCESS) return status;
 		DecodeLodLaunch& l = launches[i];
 		l.first_entry = g.first_entry; l.level_count = g.level_count;
 		l.z = g.z;

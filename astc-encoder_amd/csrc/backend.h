@@ -269,6 +269,19 @@ struct DecompressLodJob {
 	void*    stream;
 };
 int backend_decompress_lod(Backend* b, const DecompressLodJob& job);
+/* astcenc_amd_sample_cube_tensors_device: the same with the cube sampler and the grids as DecodeCubeLaunch. */
+struct DecodeCubeSampler;
+struct DecodeCubeLaunch;
+struct DecompressCubeJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	const DecodeCubeSampler* sampler;
+	const DecodeCubeLaunch* grids;
+	uint32_t grid_count;
+	void*    stream;
+};
+int backend_decompress_cube(Backend* b, const DecompressCubeJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -513,6 +526,30 @@ size_t astc_decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count);
 uint32_t astc_decode_lod_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
                                const DecodeLodLaunch* grids, uint32_t count);
 int astc_decode_lod_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
+/* Cube maps sampled by direction at a level of detail per point (astcenc_amd_sample_cube_tensors_device; decode_cube.h,
+ * kernel_decode_cube.hip): the call's format and sampler and one DecodeCubeLaunch per grid, checked by the entry point -- as the
+ * lod call's, and: every level square, no larger than 65536, with layers 6 cube .. 6 cube + 5; the directions aligned to a float,
+ * their pitch at least 3 out_x.  Work items, table and launch as the lod call's. */
+struct DecodeCubeSampler {
+	uint32_t filter;                      // astcenc_amd_sample_filter
+	uint32_t mip_filter;                  // astcenc_amd_mip_level_filter
+};
+struct DecodeCubeLaunch {
+	uint32_t first_entry, level_count;    // level l is entry first_entry + l
+	uint32_t cube;                        // layers 6 cube .. 6 cube + 5 of every level
+	uint32_t out_x, out_y;                // points per row, rows of points
+	const float* d_dirs;                  // point (i, j): d_dirs[j * dir_row_pitch + 3 i], dx, dy, dz
+	size_t   dir_row_pitch;               // floats
+	const float* d_lod;                   // point (i, j): d_lod[j * lod_row_pitch + i]; null: 0 everywhere
+	size_t   lod_row_pitch;               // floats
+	float    lod_bias;
+	void*    d_out;                       // element (c = 0, j = 0, i = 0)
+	size_t   row_pitch, plane_pitch;
+};
+size_t astc_decode_cube_bytes(const DecodeCubeLaunch* grids, uint32_t count);
+uint32_t astc_decode_cube_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeCubeSampler& sampler,
+                                const DecodeCubeLaunch* grids, uint32_t count);
+int astc_decode_cube_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

@@ -11,7 +11,10 @@
 // has a level as its l0 or as its l1, never both).  After the last pass the lane blends (binary64, two products and a sum, one
 // rounding) and stores through TensorStore::put.  A level of weight zero is not among a lane's levels: none of its blocks is read.
 //
-// Included by kernel_decode_lod.hip and tests/harness/decode_lod_check.cpp only.
+// The level walk (lod_walk_tile) takes how a lane reads its point and forms its taps in a level as a parameter: decode_cube.h runs
+// it over directions and cube faces.
+//
+// Included by kernel_decode_lod.hip, decode_cube.h and tests/harness/decode_lod_check.cpp only.
 //
 // Layout: ImageSetTable (count = grids, total = tiles), first[count], padding, DecodeLodRecord[count], then the DecodeLodLevel
 // records of grid 0's levels, of grid 1's ...; a grid's record holds the byte offset of its first level record from the table's start.
@@ -135,9 +138,13 @@ WV_FN LodLevels lod_levels(uint32_t mip_filter, uint32_t level_count, float lamb
 	return r;
 }
 
-/* What a lane keeps of its point across the level passes. */
-struct LodPoint {
-	float    u, v;
+/* What a lane keeps of its point across the level passes; `at` is where the point lies, in the form its call samples a level
+ * from (LodUV here, decode_cube.h has a direction's). */
+struct LodUV { float u, v; };
+
+template <class At>
+struct LodPointOf {
+	At       at;
 	uint32_t l0, l1;                  // its levels; l1 = LOD_NO_LEVEL: one level
 	double   g;                       // the weight of l1
 	float    s0[4], s1[4];            // the samples of l0 and l1, binary32
@@ -152,21 +159,44 @@ struct LodPoint {
 #define LOD_POINT(l) lod_lanes[l]
 #endif
 
-/* What a tile did, for the harness: level passes, batches run, blocks decoded, the distinct levels as a mask, and whether a
- * point blended two levels / had g = 0 under MIP_LINEAR. */
-struct LodTileCount { uint32_t passes, batches, blocks, level_mask, blended, single; };
+/* How the lod call's lanes read a point and form its taps in a level (lod_walk_tile's `how`): the pair (u, v), valid within
+ * 2^14, sampled at (u W_l, v H_l) of slice z under the record's address modes. */
+struct LodUVPoints {
+	typedef LodUV At;
+	WV_FN static At none() { const At a = { 0.0f, 0.0f }; return a; }
+	WV_FN static At read(const DecodeLodRecord& rec, uint32_t i, uint32_t j)
+	{
+		// (coords is aligned to 8 bytes and the pitch is even: one 8-byte load)
+		const float* uv = static_cast<const float*>(__builtin_assume_aligned(rec.coords + (size_t)j * rec.coord_row + 2u * (size_t)i, 8));
+		const At a = { uv[0], uv[1] };
+		return a;
+	}
+	WV_FN static bool valid(const At& a, float lambda) { return lod_valid(a.u, a.v, lambda); }
+	__attribute__((always_inline)) WV_FN static void taps(SamplePoint& P, const DecodeLodRecord& rec, const DecodeLodLevel& lv, const At& a)
+	{
+		// (exact products: 24 bits by 17)
+		sample_point_taps(P, lv.img, rec.z, rec.filter, rec.address_x, rec.address_y, (double)a.u * (double)lv.img.dim_x, (double)a.v * (double)lv.img.dim_y);
+	}
+};
 
-/* Tile `local` of the grid of `rec` (all 64 lanes call this; `local` is uniform); kType / kLayout are the record's.  level(l):
- * the DecodeLodLevel of the grid's level l, l uniform -- the kernel reads it with scalar loads. */
-template <uint32_t kType, uint32_t kLayout, class LevelOf>
-WV_FN LodTileCount decode_lod_tile(const DecodeLodRecord& rec, const LevelOf level, uint32_t local, DecodeBatch& batch, SampleTile& tile)
+/* What a tile did, for the harness: level passes, batches run, blocks decoded, the distinct levels as a mask, and whether a
+ * point blended two levels / had g = 0 under MIP_LINEAR, and the most blocks one pass decoded. */
+struct LodTileCount { uint32_t passes, batches, blocks, level_mask, blended, single, most; };
+
+/* The level walk of a tile, shared with decode_cube.h: tile `local` of the grid of `rec` (all 64 lanes call this; `local` is
+ * uniform); kType / kLayout are the record's.  level(l): the DecodeLodLevel of the grid's level l, l uniform -- the kernel reads it
+ * with scalar loads.  Points: how a lane reads its point (read, valid, none) and forms its taps in a level (taps); Rec: its
+ * record, with the fields of DecodeLodRecord that are used here. */
+template <uint32_t kType, uint32_t kLayout, class Points, class Rec, class LevelOf>
+WV_FN LodTileCount lod_walk_tile(const Rec& rec, const LevelOf level, uint32_t local, DecodeBatch& batch, SampleTile& tile)
 {
+	typedef LodPointOf<typename Points::At> LodPoint;
 	const uint32_t tw_log2 = rec.tw_log2, tw_mask = (1u << tw_log2) - 1u, th_log2 = 6u - tw_log2;
 	const uint32_t tile_y = local / rec.tiles_x, tile_x = local - tile_y * rec.tiles_x;
 	const uint32_t i0 = tile_x << tw_log2, j0 = tile_y << th_log2;
 	SAMPLE_POINTS_DECL;
 	LOD_POINTS_DECL;
-	LodTileCount did = { 0u, 0u, 0u, 0u, 0u, 0u };
+	LodTileCount did = { 0u, 0u, 0u, 0u, 0u, 0u, 0u };
 
 	// ---- the levels of every point ----
 	WV_FOR64(l, 64)
@@ -174,20 +204,18 @@ WV_FN LodTileCount decode_lod_tile(const DecodeLodRecord& rec, const LevelOf lev
 		LodPoint& Q = LOD_POINT(l);
 		const uint32_t i = i0 + ((uint32_t)l & tw_mask), j = j0 + ((uint32_t)l >> tw_log2);
 		Q.live = i < rec.out_x && j < rec.out_y ? 1u : 0u;
-		Q.u = 0.0f; Q.v = 0.0f;
+		Q.at = Points::none();
 		Q.l0 = LOD_NO_LEVEL; Q.l1 = LOD_NO_LEVEL; Q.g = 0.0;
 		for (int c = 0; c < 4; c++) { Q.s0[c] = 0.0f; Q.s1[c] = 0.0f; }
 		if (Q.live)
 		{
-			// (coords is aligned to 8 bytes and the pitch is even: one 8-byte load)
-			const float* uv = static_cast<const float*>(__builtin_assume_aligned(rec.coords + (size_t)j * rec.coord_row + 2u * (size_t)i, 8));
-			const float u = uv[0], v = uv[1];
+			const typename Points::At at = Points::read(rec, i, j);
 			const float lambda = (rec.lod ? rec.lod[(size_t)j * rec.lod_row + (size_t)i] : 0.0f) + rec.lod_bias;
-			if (lod_valid(u, v, lambda))
+			if (Points::valid(at, lambda))
 			{
 				const LodLevels lv = lod_levels(rec.mip_filter, rec.level_count, lambda);
 				Q.live = 3u;
-				Q.u = u; Q.v = v;
+				Q.at = at;
 				Q.l0 = lv.l0; Q.l1 = lv.l1; Q.g = lv.g;
 #if !WV_DEVICE
 				if (lv.l0 >= rec.level_count || (lv.l1 != LOD_NO_LEVEL && lv.l1 >= rec.level_count)) __builtin_trap();
@@ -219,11 +247,15 @@ WV_FN LodTileCount decode_lod_tile(const DecodeLodRecord& rec, const LevelOf lev
 			const LodPoint& Q = LOD_POINT(l);
 			P.live = Q.live;
 			sample_point_clear(P);
-			// (exact products: 24 bits by 17)
-			if (Q.l0 == m || Q.l1 == m)
-				sample_point_taps(P, lv.img, rec.z, rec.filter, rec.address_x, rec.address_y, (double)Q.u * (double)lv.img.dim_x, (double)Q.v * (double)lv.img.dim_y);
+			if (Q.l0 == m || Q.l1 == m) Points::taps(P, rec, lv, Q.at);
 		}
+#if !WV_DEVICE
+		const uint32_t blocks_before = done.blocks;
+#endif
 		sample_batches(lv.img, lv.blocks, batch, tile, SAMPLE_POINTS_ARG, done);
+#if !WV_DEVICE
+		if (done.blocks - blocks_before > did.most) did.most = done.blocks - blocks_before;
+#endif
 		WV_FOR64(l, 64)
 		{
 			const SamplePoint& P = SAMPLE_POINT(l);
@@ -268,6 +300,13 @@ WV_FN LodTileCount decode_lod_tile(const DecodeLodRecord& rec, const LevelOf lev
 	}
 	WV_SYNC();
 	return did;
+}
+
+/* The lod call's tile. */
+template <uint32_t kType, uint32_t kLayout, class LevelOf>
+WV_FN LodTileCount decode_lod_tile(const DecodeLodRecord& rec, const LevelOf level, uint32_t local, DecodeBatch& batch, SampleTile& tile)
+{
+	return lod_walk_tile<kType, kLayout, LodUVPoints>(rec, level, local, batch, tile);
 }
 
 } } // namespace astcd::ASTC_VARIANT

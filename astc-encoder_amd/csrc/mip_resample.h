@@ -125,7 +125,8 @@ ASTC_MIP_FN unsigned int mip_resample_source(long long i, unsigned int s, unsign
  * Unfolding the neighbour with the face frames of the GL table (P' = sg s A + (s - (2 kk + 1)) M_f + W, x' = (P' . S_f' + s - 1)
  * / 2, y' likewise) makes each of x' and y' one of p, s - 1 - p, kk, s - 1 - kk, so the 24 (face, side) pairs fit a table of
  * bytes: bits 0-2 the neighbour, bits 3-4 the form of x', bits 5-6 that of y' (bit 0 of a form: mirrored, s - 1 - v; bit 1:
- * v = kk instead of p).  tests/mip_cube_model.py works the frames out in full and tests/test_mip_cube_cpu.py compares. */
+ * v = kk instead of p).  tests/mip_cube_model.py works the frames out in full and tests/test_mip_cube_cpu.py compares.
+ * (decode_cube.h maps the taps of the cube sampler through this function too: its indices lie in [-1, s].) */
 struct MipCubeTexel {
 	unsigned int face, x, y;
 };

@@ -1,7 +1,8 @@
 // SPDX-License-Identifier: Apache-2.0
-// What the two samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp): the checks of the
-// sampler's filter and address modes, of the footprint, of the entries' block counts and of a grid's points and coordinates, with
-// the sample call's error codes and log lines.  `fn` names the entry point in the log.
+// What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_cube.cpp): the
+// checks of the sampler's filter and address modes, of the footprint, of the entries' block counts, of a grid's points and
+// coordinates (or directions), of a chain and of the levels of detail, with the sample and lod calls' error codes and log lines.
+// `fn` names the entry point in the log.
 #pragma once
 #include "regions_internal.h"
 
@@ -88,6 +89,106 @@ inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned 
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	g.coord_row_pitch = coord_row_pitch;
+	g.row_pitch = pitches.row;
+	g.plane_pitch = pitches.plane;
+	return ASTCENC_SUCCESS;
+}
+
+/* The mip filter between levels (astcenc_lod.cpp, astcenc_cube.cpp). */
+inline astcenc_error check_mip_level_filter(const char* fn, int mip_filter)
+{
+	if (mip_filter == ASTCENC_AMD_MIP_NEAREST || mip_filter == ASTCENC_AMD_MIP_LINEAR) return ASTCENC_SUCCESS;
+	backend_log("%s: sampler: mip_filter %d: not a mip filter", fn, mip_filter);
+	return ASTCENC_ERR_BAD_PARAM;
+}
+
+/* The chain of grid i: 1 .. 32 levels, all of them entries of the call. */
+inline astcenc_error check_lod_chain(const char* fn, unsigned int i, unsigned int grid_count, unsigned int first_entry, unsigned int level_count, unsigned int entry_count)
+{
+	if (level_count == 0 || level_count > 32)
+	{
+		backend_log("%s: grid %u of %u: %u levels: a chain has 1 to 32", fn, i, grid_count, level_count);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if ((unsigned long long)first_entry + level_count > entry_count)
+	{
+		backend_log("%s: grid %u of %u: levels are entries %u to %llu, the call has %u entries", fn, i, grid_count, first_entry,
+		            (unsigned long long)first_entry + level_count - 1, entry_count);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	return ASTCENC_SUCCESS;
+}
+
+/* lod_bias and the lod buffer's pitch of grid i, before the grid's other buffers are looked at ... */
+inline astcenc_error check_lod_pitch(const char* fn, unsigned int i, unsigned int grid_count, float lod_bias, size_t lod_row_pitch, unsigned int out_x)
+{
+	if (!std::isfinite(lod_bias))
+	{
+		backend_log("%s: grid %u of %u: lod_bias %g: not finite", fn, i, grid_count, (double)lod_bias);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (lod_row_pitch != 0 && lod_row_pitch < out_x)
+	{
+		backend_log("%s: grid %u of %u: lod_row_pitch %zu: at least %u floats", fn, i, grid_count, lod_row_pitch, out_x);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	return ASTCENC_SUCCESS;
+}
+
+/* ... and its extent and alignment after them; the pitch comes back resolved. */
+inline astcenc_error check_lod_buffer(const char* fn, unsigned int i, unsigned int grid_count, const float* lod, size_t& lod_row_pitch, unsigned int out_x, unsigned int out_y)
+{
+	const size_t resolved = lod_row_pitch ? lod_row_pitch : out_x;
+	bool overflow = false;
+	(void)mul_safe(mul_safe(resolved, out_y, overflow), sizeof(float), overflow);
+	if (overflow)
+	{
+		backend_log("%s: grid %u of %u: lod_row_pitch %zu: the levels of detail do not fit 64 bits", fn, i, grid_count, lod_row_pitch);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (reinterpret_cast<uintptr_t>(lod) % 4 != 0)
+	{
+		backend_log("%s: grid %u of %u: lod %p is not aligned to a float (4 bytes)", fn, i, grid_count, static_cast<const void*>(lod));
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	lod_row_pitch = resolved;
+	return ASTCENC_SUCCESS;
+}
+
+/* The points, the directions and the output of grid i of grid_count (astcenc_cube.cpp): check_sample_grid with triples of floats
+ * in the place of pairs -- aligned to a float, any pitch of at least 3 out_x. */
+struct CubeGridShape {
+	unsigned int out_x, out_y;
+	const float* dirs;
+	size_t dir_row_pitch;
+	void* out;
+	size_t row_pitch, plane_pitch;
+};
+
+inline astcenc_error check_cube_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, CubeGridShape& g)
+{
+	if (g.out_x == 0 || g.out_y == 0 || g.out_x > 65535 || g.out_y > 65535)
+	{
+		backend_log("%s: grid %u of %u: %u x %u points: either size is 1 to 65535", fn, i, grid_count, g.out_x, g.out_y);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (g.dir_row_pitch != 0 && g.dir_row_pitch < 3u * (size_t)g.out_x)
+	{
+		backend_log("%s: grid %u of %u: dir_row_pitch %zu: at least %zu floats", fn, i, grid_count, g.dir_row_pitch, 3u * (size_t)g.out_x);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	bool overflow = false;
+	const size_t dir_row_pitch = g.dir_row_pitch ? g.dir_row_pitch : 3u * (size_t)g.out_x;
+	(void)mul_safe(mul_safe(dir_row_pitch, g.out_y, overflow), sizeof(float), overflow);
+	TensorPitches pitches = { g.row_pitch, 0, g.plane_pitch };
+	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.dirs ? "dirs" : nullptr);
+	if (status != ASTCENC_SUCCESS) return status;
+	if (reinterpret_cast<uintptr_t>(g.dirs) % 4 != 0)
+	{
+		backend_log("%s: grid %u of %u: dirs %p is not aligned to a float (4 bytes)", fn, i, grid_count, static_cast<const void*>(g.dirs));
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	g.dir_row_pitch = dir_row_pitch;
 	g.row_pitch = pitches.row;
 	g.plane_pitch = pitches.plane;
 	return ASTCENC_SUCCESS;

@@ -105,7 +105,7 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
                "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
                "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device",
-               "astcenc_amd_sample_lod_tensors_device"]
+               "astcenc_amd_sample_lod_tensors_device", "astcenc_amd_sample_cube_tensors_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
@@ -370,6 +370,36 @@ class LodGrid(C.Structure):
                 ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
 
 
+def _check_chain(level_count, lod_bias):
+    """What lod_grid and cube_grid reject of a chain's length and of the bias."""
+    import math
+    if not 1 <= level_count <= MAX_MIP_LEVELS:
+        raise ValueError("level_count %r: a chain has 1 .. %d levels" % (level_count, MAX_MIP_LEVELS))
+    if not math.isfinite(lod_bias):
+        raise ValueError("lod_bias %r is not finite" % (lod_bias,))
+
+
+def _lod_buffer(lod, out_x, out_y, device, other):
+    """(pointer, lod_row_pitch) of a float32 torch tensor [out_y, out_x] of levels of detail, or (None, 0) for None; ValueError
+    for what lod_grid's comment lists.  `device` is that of the points' tensor, which `other` names."""
+    if lod is None:
+        return None, 0
+    import torch
+    if lod.dtype != torch.float32:
+        raise ValueError("lod is %s: float32" % lod.dtype)
+    lshape, lst = tuple(lod.shape), tuple(lod.stride())
+    if lod.dim() != 2 or lshape != (out_y, out_x):
+        raise ValueError("lod has shape %r: [H, W] = [%u, %u]" % (lshape, out_y, out_x))
+    if (lst[1] != 1 and lshape[1] > 1) or lst[0] < 0 or (lst[0] == 0 and lshape[0] > 1):
+        raise ValueError("the columns of lod must be adjacent floats and its rows apart (strides %r)" % (lst,))
+    if lod.device != device:
+        raise ValueError("lod is on %s, %s on %s" % (lod.device, other, device))
+    lod_row_pitch = lst[0] if lshape[0] > 1 else 0
+    if lod_row_pitch != 0 and lod_row_pitch < lshape[1]:
+        raise ValueError("the rows of lod overlap (strides %r)" % (lst,))
+    return lod.data_ptr(), lod_row_pitch
+
+
 def lod_grid(first_entry, level_count, z, coords, lod, out_view, lod_bias=0.0, layout=TENSOR_PLANAR, type=None):
     """LodGrid of slice `z` of the chain entries[first_entry : first_entry + level_count]: `coords` is a float32 torch tensor
     [H, W, 2] of NORMALISED (u, v) pairs, `lod` a float32 torch tensor [H, W] of levels of detail or None (0 everywhere), `out_view`
@@ -379,33 +409,59 @@ def lod_grid(first_entry, level_count, z, coords, lod, out_view, lod_bias=0.0, l
     whose columns are not adjacent floats, whose rows overlap or alias or have a negative stride, or which lives on another device
     than `coords`.  Or explicit tuples: coords = (ptr, out_x, out_y, coord_row_pitch), lod = (ptr, lod_row_pitch) or None, out_view =
     (ptr, row_pitch, plane_pitch)."""
-    import math
-    if not 1 <= level_count <= MAX_MIP_LEVELS:
-        raise ValueError("level_count %r: a chain has 1 .. %d levels" % (level_count, MAX_MIP_LEVELS))
-    if not math.isfinite(lod_bias):
-        raise ValueError("lod_bias %r is not finite" % (lod_bias,))
+    _check_chain(level_count, lod_bias)
     if isinstance(coords, tuple):
         g = sample_grid(first_entry, z, coords, out_view)
         lptr, lod_row_pitch = lod if lod is not None else (None, 0)
     else:
         g = sample_grid(first_entry, z, coords, out_view, layout=layout, type=type)
-        lptr, lod_row_pitch = None, 0
-        if lod is not None:
-            import torch
-            if lod.dtype != torch.float32:
-                raise ValueError("lod is %s: float32" % lod.dtype)
-            lshape, lst = tuple(lod.shape), tuple(lod.stride())
-            if lod.dim() != 2 or lshape != (g.out_y, g.out_x):
-                raise ValueError("lod has shape %r: [H, W] = [%u, %u]" % (lshape, g.out_y, g.out_x))
-            if (lst[1] != 1 and lshape[1] > 1) or lst[0] < 0 or (lst[0] == 0 and lshape[0] > 1):
-                raise ValueError("the columns of lod must be adjacent floats and its rows apart (strides %r)" % (lst,))
-            if lod.device != coords.device:
-                raise ValueError("lod is on %s, coords on %s" % (lod.device, coords.device))
-            lod_row_pitch = lst[0] if lshape[0] > 1 else 0
-            if lod_row_pitch != 0 and lod_row_pitch < lshape[1]:
-                raise ValueError("the rows of lod overlap (strides %r)" % (lst,))
-            lptr = lod.data_ptr()
+        lptr, lod_row_pitch = _lod_buffer(lod, g.out_x, g.out_y, coords.device, "coords")
     return LodGrid(first_entry, level_count, z, g.out_x, g.out_y, g.coords, g.coord_row_pitch, lptr, lod_row_pitch, lod_bias, g.out, g.row_pitch, g.plane_pitch)
+
+
+class CubeSampler(C.Structure):
+    """struct astcenc_amd_cube_sampler (include/astcenc_amd.h): SAMPLE_* filter within a level, MIP_NEAREST / MIP_LINEAR between
+    levels."""
+    _fields_ = [("filter", C.c_int), ("mip_filter", C.c_int)]
+
+
+class CubeGrid(C.Structure):
+    """struct astcenc_amd_cube_grid (include/astcenc_amd.h)."""
+    _fields_ = [("first_entry", C.c_uint), ("level_count", C.c_uint), ("cube", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint),
+                ("dirs", C.c_void_p), ("dir_row_pitch", C.c_size_t), ("lod", C.c_void_p), ("lod_row_pitch", C.c_size_t), ("lod_bias", C.c_float),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
+
+
+def cube_grid(first_entry, level_count, cube, dirs, lod, out_view, lod_bias=0.0, layout=TENSOR_PLANAR, type=None):
+    """CubeGrid of cube `cube` of the chain entries[first_entry : first_entry + level_count]: `dirs` is a float32 torch tensor
+    [H, W, 3] of directions (dx, dy, dz), `lod` a float32 torch tensor [H, W] or None, `out_view` the torch view [C, H, W] for
+    TENSOR_PLANAR or [H, W, C] for TENSOR_INTERLEAVED; pointers and pitches come from the strides.  ValueError for what the call
+    cannot express: directions that are not float32, not [H, W, 3], whose triples are not adjacent or not three floats apart or
+    whose rows overlap; everything lod_grid rejects of `lod`, `out_view`, level_count and lod_bias.  Or explicit tuples: dirs =
+    (ptr, out_x, out_y, dir_row_pitch), lod = (ptr, lod_row_pitch) or None, out_view = (ptr, row_pitch, plane_pitch)."""
+    _check_chain(level_count, lod_bias)
+    if isinstance(dirs, tuple):
+        dptr, out_x, out_y, dir_row_pitch = dirs
+        optr, row_pitch, plane_pitch = out_view
+        lptr, lod_row_pitch = lod if lod is not None else (None, 0)
+        return CubeGrid(first_entry, level_count, cube, out_x, out_y, dptr, dir_row_pitch, lptr, lod_row_pitch, lod_bias, optr, row_pitch, plane_pitch)
+    import torch
+    if dirs.dtype != torch.float32:
+        raise ValueError("dirs is %s: float32 triples" % dirs.dtype)
+    dshape, dst = tuple(dirs.shape), tuple(dirs.stride())
+    if dirs.dim() != 3 or dshape[2] != 3:
+        raise ValueError("dirs has shape %r: [H, W, 3]" % (dshape,))
+    if dst[2] != 1 or (dst[1] != 3 and dshape[1] > 1) or dst[0] < 0 or (dst[0] == 0 and dshape[0] > 1):
+        raise ValueError("the triples of dirs must be adjacent floats, three floats apart, its rows apart (strides %r)" % (dst,))
+    dir_row_pitch = dst[0] if dshape[0] > 1 else 0
+    if dir_row_pitch != 0 and dir_row_pitch < 3 * dshape[1]:
+        raise ValueError("the rows of dirs overlap (strides %r)" % (dst,))
+    # (the output's checks are scaled_region's: a window of 1 x 1 stands in for the one this call does not have)
+    r = scaled_region(first_entry, (0, 0, 0), (1, 1), out_view, layout=layout, type=type)
+    if (r.out_x, r.out_y) != (dshape[1], dshape[0]):
+        raise ValueError("out_view is %u x %u points, dirs %u x %u" % (r.out_x, r.out_y, dshape[1], dshape[0]))
+    lptr, lod_row_pitch = _lod_buffer(lod, r.out_x, r.out_y, dirs.device, "dirs")
+    return CubeGrid(first_entry, level_count, cube, r.out_x, r.out_y, dirs.data_ptr(), dir_row_pitch, lptr, lod_row_pitch, lod_bias, r.out, r.row_pitch, r.plane_pitch)
 
 
 class ErrorSums(C.Structure):
@@ -553,6 +609,10 @@ class Library:
             L.astcenc_amd_sample_lod_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(LodSampler),
                                                                 C.POINTER(LodGrid), C.c_uint, C.c_void_p]
             L.astcenc_amd_sample_lod_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_sample_cube_tensors_device"):
+            L.astcenc_amd_sample_cube_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(CubeSampler),
+                                                                 C.POINTER(CubeGrid), C.c_uint, C.c_void_p]
+            L.astcenc_amd_sample_cube_tensors_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_sample_tensors_device"):
             L.astcenc_amd_sample_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(Sampler),
                                                             C.POINTER(SampleGrid), C.c_uint, C.c_void_p]
@@ -798,6 +858,19 @@ class Library:
         garr = (LodGrid * len(grids))(*grids) if grids else None
         return self.lib.astcenc_amd_sample_lod_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
                                                               C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_cube_tensors_device(self, ctx, entries, format, sampler, grids, stream=None):
+        """astcenc_amd_sample_cube_tensors_device: cube maps (one level or a mip chain) among the compressed images `entries`
+        sampled by direction at a level of detail per point into tensors of `format`.  sampler: a CubeSampler, or a (filter,
+        mip_filter) tuple of SAMPLE_* / MIP_NEAREST, MIP_LINEAR constants.  grids: CubeGrid, or (first_entry, level_count, cube,
+        dirs, lod, out_view[, lod_bias]) tuples (see cube_grid; the view is read with the format's layout and must have its type)."""
+        arr, n, s = self._set_args(entries, stream)
+        if sampler is not None and not isinstance(sampler, CubeSampler):
+            sampler = CubeSampler(*sampler)
+        grids = [g if isinstance(g, CubeGrid) else cube_grid(*g, layout=format.layout, type=format.type) for g in grids]
+        garr = (CubeGrid * len(grids))(*grids) if grids else None
+        return self.lib.astcenc_amd_sample_cube_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
+                                                               C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

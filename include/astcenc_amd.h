@@ -363,7 +363,8 @@ struct astcenc_amd_sample_grid {
  *   window without flips, for U8, F16 and F32 entries.
  *
  *   Out of scope: anisotropy; sampling along z (z selects an array slice); 3D footprints; gradients with respect to coordinates or texels.
- *   Mip level selection and trilinear filtering are astcenc_amd_sample_lod_tensors_device's, below.
+ *   Mip level selection and trilinear filtering are astcenc_amd_sample_lod_tensors_device's, below; cube maps sampled by
+ *   direction are astcenc_amd_sample_cube_tensors_device's.
  *
  *   - Entries, z inside the image, device ownership (of `coords` too), the null / zero-count cases, the format, pitches below the
  *     tight ones, a plane_pitch with INTERLEAVED, the alignment of `out`, a null `out` and the stream are checked as in
@@ -448,7 +449,8 @@ struct astcenc_amd_lod_grid {
  *   the bytes are those astcenc_amd_sample_tensors_device writes for that entry at (u * W_l, v * H_l).
  *
  *   Out of scope: level selection from coordinate derivatives (a log2 cannot be given a bit-exact contract: the caller supplies
- *   lambda); anisotropy; cube maps; sampling along z; 3D footprints; gradients.
+ *   lambda); anisotropy; sampling along z; 3D footprints; gradients.
+ *   Cube maps sampled by direction, seamless across faces, are astcenc_amd_sample_cube_tensors_device's, below.
  *
  *   - Everything astcenc_amd_sample_tensors_device checks is checked here with the same error codes -- the entries, the format,
  *     the sampler's filter and address modes, out_x and out_y, `coords` and its pitch, `out` and its pitches, device ownership,
@@ -468,6 +470,95 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_lod_tensors_device(
 	const struct astcenc_amd_tensor_format* format,
 	const struct astcenc_amd_lod_sampler* sampler,
 	const struct astcenc_amd_lod_grid* grids, unsigned int grid_count,
+	void* hip_stream);
+
+/* Compressed cube maps sampled by direction at a level of detail per point straight into tensors: the environment lookup of a
+ * texture unit -- "the filtered texel in direction d at level of detail lambda" for a buffer of directions: the reflection
+ * vectors of a probe lookup, the view rays of a sky box, the normals of an environment-lighting pass of a neural-texture
+ * trainer -- with every level staying compressed and no seam along the cube's edges: a bilinear tap that leaves a face reads
+ * the neighbouring face, by the "Cube edges" rule the mip filters generate the chain with (ASTCENC_AMD_MIP_EDGE_CUBE, further
+ * down).  A chain is level_count consecutive entries as in astcenc_amd_sample_lod_tensors_device; a chain of one level with a
+ * NULL `lod` is a cube without mips.
+ *
+ * The sampler holds for the whole call.  A cube has no address modes: its edges are its neighbours'. */
+struct astcenc_amd_cube_sampler {
+	enum astcenc_amd_sample_filter filter;          /* NEAREST or BILINEAR within a level */
+	enum astcenc_amd_mip_level_filter mip_filter;   /* MIP_NEAREST or MIP_LINEAR between levels */
+};
+
+struct astcenc_amd_cube_grid {
+	unsigned int first_entry, level_count;  /* entries[first_entry + l] is level l; 1 <= level_count <= 32 */
+	unsigned int cube;                      /* layers 6 * cube .. 6 * cube + 5 of every level: +X, -X, +Y, -Y, +Z, -Z */
+	unsigned int out_x, out_y;              /* points per row / rows of points, each 1 .. 65535 */
+	const float* dirs;                      /* device pointer: point (i, j) is the triple at dirs[j * dir_row_pitch + 3 * i], dx, dy, dz;
+	                                           any length but zero */
+	size_t dir_row_pitch;                   /* in floats; 0 = 3 * out_x */
+	const float* lod;                       /* device pointer: point (i, j) has lod[j * lod_row_pitch + i]; NULL: 0 everywhere */
+	size_t lod_row_pitch;                   /* in floats; 0 = out_x */
+	float lod_bias;                         /* added to every point's lod; finite */
+	void* out;                              /* device pointer: element (c = 0, j = 0, i = 0) */
+	size_t row_pitch, plane_pitch;          /* in ELEMENTS of the format's type; 0 = tightly packed */
+};
+
+/* Sample grids[0 .. grid_count) into tensors of `format` (astcenc_amd_decompress_tensors_device's).  For point (i, j) of a grid,
+ * 0 <= i < out_x, 0 <= j < out_y, with d = (dx, dy, dz) read from `dirs` and lod from `lod`, and channel c < format->channels
+ * (reals are IEEE binary64 below unless said otherwise; "one operation" is one IEEE operation, round to nearest even, never
+ * fused; the division is a true division):
+ *
+ *   Levels.  Level l is the image of entries[first_entry + l]: dim_x == dim_y == s_l <= 65536, dim_z % 6 == 0 and
+ *     6 * cube + 5 < dim_z.  Layer 6 * cube + f is face f, in the face order and with the face frames (M_f, S_f, T_f) of the
+ *     "Cube edges" table below.  The levels of a chain may have any sizes and data types.
+ *   Validity.  lambda' = lod + lod_bias, one binary32 addition; lod = +0.0 when `lod` is NULL.  A point is VALID when dx, dy and
+ *     dz are finite, not all three are zero (zeros of either sign), and lambda' is not a NaN.  There is no magnitude limit:
+ *     subnormals widen exactly, and the quotient below is at most 1 in magnitude.  An invalid point has s[c] = +0.0 for every
+ *     channel and then goes through "Arithmetic, storage" like any other.
+ *   Face.  With a = |dx|, b = |dy|, c = |dz|: the major axis is x when a >= b and a >= c; otherwise y when b >= c; otherwise z.
+ *     The face is f = 2 * axis + (1 when the major component is negative, else 0).  ma = |major component|, widened to binary64.
+ *     sc = d . S_f and tc = d . T_f, each one component with a sign, so exact:
+ *         f  face  sc   tc          f  face  sc   tc          f  face  sc   tc
+ *         0  +X    -dz  -dy         2  +Y    +dx  +dz         4  +Z    +dx  -dy
+ *         1  -X    +dz  -dy         3  -Y    +dx  -dz         5  -Z    -dx  -dy
+ *   Face coordinates.  p = sc / ma and q = tc / ma, one division each (they do not depend on the level).  Per level, with
+ *     h = s_l * 0.5 (exact): x = p * h + h and y = q * h + h, each one product and then one sum.  So x and y lie in [0, s_l].
+ *   Taps.  NEAREST: one tap of weight 1, texel (min(floor(x), s - 1), min(floor(y), s - 1)) of face f.
+ *     BILINEAR: the sample call's axis rule on x and on y: t = x - 0.5, i0 = floor(t), fr = t - i0, tap 0 is index i0 with
+ *     weight 1.0 - fr, tap 1 is index i0 + 1 with weight fr.  The tap indices lie in [-1, s].  Each tap (ix, iy) reads the texel
+ *     the "Cube edges" rule names for face f of a cube of s x s faces:
+ *       - both indices inside [0, s): texel (ix, iy) of face f;
+ *       - one index outside (it is -1 or s): the neighbouring face's texel at depth 0 from the shared edge, at the same place
+ *         along the edge (the rule's overshoot k = 0);
+ *       - both outside (the corner, where no face lies): the face's own corner texel (clamp(ix), clamp(iy)).  The three texels
+ *         that meet at a cube corner are not averaged, as in the mip filter.
+ *     A tap of weight 0 (tap 1 when fr = 0) is not part of any sum, and its block is not read.
+ *   Source, sums.  Those of astcenc_amd_sample_tensors_device, the texel being (x', y', layer 6 * cube + f') of the level's entry.
+ *   Level of detail, blend.  Those of astcenc_amd_sample_lod_tensors_device: lambda_c, the one level of MIP_NEAREST, the two
+ *     levels and g of MIP_LINEAR, the level of weight zero that is not read, one rounding to binary32 per level and one after
+ *     the blend.
+ *   Arithmetic, storage, placement.  Those of astcenc_amd_sample_tensors_device.
+ *
+ *   Consequence: for s a power of two the direction s M_f + (2x + 1 - s) S_f + (2y + 1 - s) T_f -- the centre of texel (x, y)
+ *   of face f in the doubled integer units of "Cube edges" -- reproduces that texel under either filter: the division and the
+ *   product are exact, so the face coordinate is (x + 0.5, y + 0.5).  Scaling a direction by a power of two changes nothing as
+ *   long as no component overflows or leaves the subnormal range inexactly.
+ *
+ *   Out of scope: level selection from derivatives; anisotropy; solid-angle weighting; 3D footprints; gradients.
+ *
+ *   - Everything astcenc_amd_sample_lod_tensors_device checks is checked here with its error codes -- the entries, the format,
+ *     the filters, out_x and out_y, the chain, lod, lod_bias and their pitch, `out` and its pitches, device ownership (of `dirs`
+ *     too), the context's footprint, the work items -- everything before anything is launched; a failure returns its error with
+ *     nothing written, and the log callback names the index: "grid i of n".
+ *   - Also ASTCENC_ERR_BAD_PARAM: a level that is not square; a level whose dim_z % 6 != 0; a `cube` beyond a level's layers; a
+ *     level with s above 65536; a `dirs` not aligned to 4 bytes; a non-zero dir_row_pitch below 3 * out_x; a `dirs` not on the
+ *     device of entry 0's blocks.  A null `dirs`: ASTCENC_ERR_BAD_CONTEXT.  Directions and levels of detail are data: none of
+ *     them is an error.
+ *   - Work items are the lod call's tiles of 64 points and its pass per distinct level; a pass decodes every block its points'
+ *     taps reach once, on whichever faces they lie. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_cube_tensors_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_cube_sampler* sampler,
+	const struct astcenc_amd_cube_grid* grids, unsigned int grid_count,
 	void* hip_stream);
 
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
