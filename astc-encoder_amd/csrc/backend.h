@@ -282,6 +282,19 @@ struct DecompressCubeJob {
 	void*    stream;
 };
 int backend_decompress_cube(Backend* b, const DecompressCubeJob& job);
+/* astcenc_amd_sample_volume_tensors_device: the same with the volume sampler and the grids as DecodeVolumeLaunch. */
+struct DecodeVolumeSampler;
+struct DecodeVolumeLaunch;
+struct DecompressVolumeJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	const DecodeVolumeSampler* sampler;
+	const DecodeVolumeLaunch* grids;
+	uint32_t grid_count;
+	void*    stream;
+};
+int backend_decompress_volume(Backend* b, const DecompressVolumeJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -550,6 +563,30 @@ size_t astc_decode_cube_bytes(const DecodeCubeLaunch* grids, uint32_t count);
 uint32_t astc_decode_cube_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeCubeSampler& sampler,
                                 const DecodeCubeLaunch* grids, uint32_t count);
 int astc_decode_cube_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
+/* Volumes sampled at (u, v, w) at a level of detail per point (astcenc_amd_sample_volume_tensors_device; decode_volume.h,
+ * kernel_decode_volume.hip): the call's format and sampler and one DecodeVolumeLaunch per grid, checked by the entry point -- as
+ * the lod call's without a slice, and: any footprint, 2D or 3D; every level no larger than 65536 along x, y and z and of fewer
+ * than 2^32 - 1 blocks, layers of block_z slices counted; the triples aligned to a float, their pitch at least 3 out_x.  Work
+ * items, table and launch as the lod call's. */
+struct DecodeVolumeSampler {
+	uint32_t filter, address_x, address_y, address_z;    // astcenc_amd_sample_filter / _address
+	uint32_t mip_filter;                                 // astcenc_amd_mip_level_filter
+};
+struct DecodeVolumeLaunch {
+	uint32_t first_entry, level_count;    // level l is entry first_entry + l
+	uint32_t out_x, out_y;                // points per row, rows of points
+	const float* d_coords;                // point (i, j): d_coords[j * coord_row_pitch + 3 i], u, v, w
+	size_t   coord_row_pitch;             // floats
+	const float* d_lod;                   // point (i, j): d_lod[j * lod_row_pitch + i]; null: 0 everywhere
+	size_t   lod_row_pitch;               // floats
+	float    lod_bias;
+	void*    d_out;                       // element (c = 0, j = 0, i = 0)
+	size_t   row_pitch, plane_pitch;
+};
+size_t astc_decode_volume_bytes(const DecodeVolumeLaunch* grids, uint32_t count);
+uint32_t astc_decode_volume_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeVolumeSampler& sampler,
+                                  const DecodeVolumeLaunch* grids, uint32_t count);
+int astc_decode_volume_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

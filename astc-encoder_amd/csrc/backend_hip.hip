@@ -1727,6 +1727,25 @@ int backend_decompress_cube(Backend* b, const DecompressCubeJob& job)
 		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_cube_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
 }
 
+/* (as backend_decompress_lod: a grid's buffers are the output, the triples and, unless null, the levels of detail) */
+int backend_decompress_volume(Backend* b, const DecompressVolumeJob& job)
+{
+	std::vector<uint8_t> used(job.entry_count, 0);
+	for (uint32_t i = 0; i < job.grid_count; i++)
+		for (uint32_t l = 0; l < job.grids[i].level_count; l++) used[job.grids[i].first_entry + l] = 1;
+	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample volume tensors",
+		[&](uint32_t i)
+		{
+			const DecodeVolumeLaunch& g = job.grids[i / 3u];
+			return i % 3u == 0u || (i % 3u == 2u && !g.d_lod) ? static_cast<const void*>(g.d_out) : i % 3u == 1u ? static_cast<const void*>(g.d_coords) : static_cast<const void*>(g.d_lod);
+		},
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_volume_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_volume_bytes(job.grids, job.grid_count);
+		},
+		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_volume_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
+}
+
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial
  * sums has a fixed size (rc 1 when it cannot be had, nothing launched), the totals come back once the stream has run. */
 static int compare_blocks_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const QualitySetJob& job)

@@ -179,6 +179,7 @@ __attribute__((always_inline)) WV_FN void cube_point_taps(SamplePoint& P, const 
 /* How the cube call's lanes read a point and form its taps in a level (lod_walk_tile's Points). */
 struct CubePoints {
 	typedef CubeAt At;
+	typedef SamplePoint Point;
 	WV_FN static At none() { const At a = { 0.0, 0.0, 0xFFFFFFFFu }; return a; }
 	/* (an invalid direction comes back with the face 0xFFFFFFFF) */
 	WV_FN static At read(const DecodeCubeRecord& rec, uint32_t i, uint32_t j)

@@ -12,9 +12,9 @@
 // rounding) and stores through TensorStore::put.  A level of weight zero is not among a lane's levels: none of its blocks is read.
 //
 // The level walk (lod_walk_tile) takes how a lane reads its point and forms its taps in a level as a parameter: decode_cube.h runs
-// it over directions and cube faces.
+// it over directions and cube faces, decode_volume.h over triples and eight taps.
 //
-// Included by kernel_decode_lod.hip, decode_cube.h and tests/harness/decode_lod_check.cpp only.
+// Included by kernel_decode_lod.hip, decode_cube.h, decode_volume.h and tests/harness/decode_lod_check.cpp only.
 //
 // Layout: ImageSetTable (count = grids, total = tiles), first[count], padding, DecodeLodRecord[count], then the DecodeLodLevel
 // records of grid 0's levels, of grid 1's ...; a grid's record holds the byte offset of its first level record from the table's start.
@@ -163,6 +163,7 @@ struct LodPointOf {
  * 2^14, sampled at (u W_l, v H_l) of slice z under the record's address modes. */
 struct LodUVPoints {
 	typedef LodUV At;
+	typedef SamplePoint Point;
 	WV_FN static At none() { const At a = { 0.0f, 0.0f }; return a; }
 	WV_FN static At read(const DecodeLodRecord& rec, uint32_t i, uint32_t j)
 	{
@@ -183,18 +184,24 @@ struct LodUVPoints {
  * point blended two levels / had g = 0 under MIP_LINEAR, and the most blocks one pass decoded. */
 struct LodTileCount { uint32_t passes, batches, blocks, level_mask, blended, single, most; };
 
-/* The level walk of a tile, shared with decode_cube.h: tile `local` of the grid of `rec` (all 64 lanes call this; `local` is
- * uniform); kType / kLayout are the record's.  level(l): the DecodeLodLevel of the grid's level l, l uniform -- the kernel reads it
- * with scalar loads.  Points: how a lane reads its point (read, valid, none) and forms its taps in a level (taps); Rec: its
- * record, with the fields of DecodeLodRecord that are used here. */
+/* The level walk of a tile, shared with decode_cube.h and decode_volume.h: tile `local` of the grid of `rec` (all 64 lanes call
+ * this; `local` is uniform); kType / kLayout are the record's.  level(l): the DecodeLodLevel of the grid's level l, l uniform -- the kernel reads it
+ * with scalar loads.  Points: how a lane reads its point (read, valid, none) and forms its taps in a level (taps), and what it
+ * keeps of the point in a level (Point: SamplePoint, or decode_volume.h's eight taps, whose sample_point_clear, sample_batches and
+ * sample_point_sums are overloads on that type); Rec: its record, with the fields of DecodeLodRecord that are used here. */
 template <uint32_t kType, uint32_t kLayout, class Points, class Rec, class LevelOf>
 WV_FN LodTileCount lod_walk_tile(const Rec& rec, const LevelOf level, uint32_t local, DecodeBatch& batch, SampleTile& tile)
 {
 	typedef LodPointOf<typename Points::At> LodPoint;
+	typedef typename Points::Point Point;
 	const uint32_t tw_log2 = rec.tw_log2, tw_mask = (1u << tw_log2) - 1u, th_log2 = 6u - tw_log2;
 	const uint32_t tile_y = local / rec.tiles_x, tile_x = local - tile_y * rec.tiles_x;
 	const uint32_t i0 = tile_x << tw_log2, j0 = tile_y << th_log2;
-	SAMPLE_POINTS_DECL;
+#if WV_DEVICE
+	Point point_regs;
+#else
+	Point point_lanes[SAMPLE_POINTS];
+#endif
 	LOD_POINTS_DECL;
 	LodTileCount did = { 0u, 0u, 0u, 0u, 0u, 0u, 0u };
 
@@ -243,7 +250,7 @@ WV_FN LodTileCount lod_walk_tile(const Rec& rec, const LevelOf level, uint32_t l
 		const DecodeLodLevel lv = level(m);
 		WV_FOR64(l, 64)
 		{
-			SamplePoint& P = SAMPLE_POINT(l);
+			Point& P = SAMPLE_POINT(l);
 			const LodPoint& Q = LOD_POINT(l);
 			P.live = Q.live;
 			sample_point_clear(P);
@@ -258,7 +265,7 @@ WV_FN LodTileCount lod_walk_tile(const Rec& rec, const LevelOf level, uint32_t l
 #endif
 		WV_FOR64(l, 64)
 		{
-			const SamplePoint& P = SAMPLE_POINT(l);
+			const Point& P = SAMPLE_POINT(l);
 			LodPoint& Q = LOD_POINT(l);
 			if (Q.l0 != m && Q.l1 != m) continue;
 			float s[4];

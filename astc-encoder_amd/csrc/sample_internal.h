@@ -1,5 +1,6 @@
 // SPDX-License-Identifier: Apache-2.0
-// What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_cube.cpp): the
+// What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_cube.cpp,
+// astcenc_volume.cpp): the
 // checks of the sampler's filter and address modes, of the footprint, of the entries' block counts, of a grid's points and
 // coordinates (or directions), of a chain and of the levels of detail, with the sample and lod calls' error codes and log lines.
 // `fn` names the entry point in the log.
@@ -155,8 +156,9 @@ inline astcenc_error check_lod_buffer(const char* fn, unsigned int i, unsigned i
 	return ASTCENC_SUCCESS;
 }
 
-/* The points, the directions and the output of grid i of grid_count (astcenc_cube.cpp): check_sample_grid with triples of floats
- * in the place of pairs -- aligned to a float, any pitch of at least 3 out_x. */
+/* The points, the triples of floats (the cube call's directions, the volume call's coordinates) and the output of grid i of
+ * grid_count: check_sample_grid with triples in the place of pairs -- aligned to a float, any pitch of at least 3 out_x.  `what`
+ * and `what_pitch` name the buffer and its pitch in the log. */
 struct CubeGridShape {
 	unsigned int out_x, out_y;
 	const float* dirs;
@@ -165,7 +167,8 @@ struct CubeGridShape {
 	size_t row_pitch, plane_pitch;
 };
 
-inline astcenc_error check_cube_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, CubeGridShape& g)
+inline astcenc_error check_triple_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, CubeGridShape& g, const char* what,
+                                       const char* what_pitch)
 {
 	if (g.out_x == 0 || g.out_y == 0 || g.out_x > 65535 || g.out_y > 65535)
 	{
@@ -174,23 +177,58 @@ inline astcenc_error check_cube_grid(const char* fn, unsigned int i, unsigned in
 	}
 	if (g.dir_row_pitch != 0 && g.dir_row_pitch < 3u * (size_t)g.out_x)
 	{
-		backend_log("%s: grid %u of %u: dir_row_pitch %zu: at least %zu floats", fn, i, grid_count, g.dir_row_pitch, 3u * (size_t)g.out_x);
+		backend_log("%s: grid %u of %u: %s %zu: at least %zu floats", fn, i, grid_count, what_pitch, g.dir_row_pitch, 3u * (size_t)g.out_x);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	bool overflow = false;
 	const size_t dir_row_pitch = g.dir_row_pitch ? g.dir_row_pitch : 3u * (size_t)g.out_x;
 	(void)mul_safe(mul_safe(dir_row_pitch, g.out_y, overflow), sizeof(float), overflow);
 	TensorPitches pitches = { g.row_pitch, 0, g.plane_pitch };
-	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.dirs ? "dirs" : nullptr);
+	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.dirs ? what : nullptr);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (reinterpret_cast<uintptr_t>(g.dirs) % 4 != 0)
 	{
-		backend_log("%s: grid %u of %u: dirs %p is not aligned to a float (4 bytes)", fn, i, grid_count, static_cast<const void*>(g.dirs));
+		backend_log("%s: grid %u of %u: %s %p is not aligned to a float (4 bytes)", fn, i, grid_count, what, static_cast<const void*>(g.dirs));
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	g.dir_row_pitch = dir_row_pitch;
 	g.row_pitch = pitches.row;
 	g.plane_pitch = pitches.plane;
+	return ASTCENC_SUCCESS;
+}
+
+inline astcenc_error check_cube_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, CubeGridShape& g)
+{
+	return check_triple_grid(fn, i, grid_count, format, g, "dirs", "dir_row_pitch");
+}
+
+/* The volume call's third address mode (astcenc_volume.cpp), after check_sample_modes has seen the other two. */
+inline astcenc_error check_volume_address_z(const char* fn, int address_z)
+{
+	if (address_z >= ASTCENC_AMD_ADDRESS_CLAMP && address_z <= ASTCENC_AMD_ADDRESS_BORDER) return ASTCENC_SUCCESS;
+	backend_log("%s: sampler: address mode %d along z: not an address mode", fn, address_z);
+	return ASTCENC_ERR_BAD_PARAM;
+}
+
+/* check_sample_entries for any footprint (astcenc_volume.cpp): the blocks of an entry are counted in layers of block_z slices. */
+inline astcenc_error check_volume_entries(const char* fn, astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                          std::vector<DecompressDeviceJob>& jobs)
+{
+	const astcenc_error entries_status = check_window_entries(fn, ctx, entries, entry_count, jobs);
+	if (entries_status != ASTCENC_SUCCESS) return entries_status;
+	for (unsigned int e = 0; e < entry_count; e++)
+	{
+		const astcenc_amd_image_set_entry& en = entries[e];
+		// (each factor is below 2^32 and the first product below 2^64; the second is formed only while it fits)
+		const unsigned long long plane = (unsigned long long)((en.dim_x + ctx->config.block_x - 1) / ctx->config.block_x) *
+		                                 ((en.dim_y + ctx->config.block_y - 1) / ctx->config.block_y);
+		const unsigned long long layers = ((unsigned long long)en.dim_z + ctx->config.block_z - 1) / ctx->config.block_z;
+		if (plane >= 0xFFFFFFFFull || plane * layers >= 0xFFFFFFFFull)
+		{
+			backend_log("%s: entry %u of %u: %llu x %llu blocks: an image of 2^32 - 1 blocks or more cannot be sampled", fn, e, entry_count, plane, layers);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+	}
 	return ASTCENC_SUCCESS;
 }
 

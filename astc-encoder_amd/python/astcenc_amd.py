@@ -105,7 +105,8 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_compress_block_list_set_device", "astcenc_amd_compress_images_adaptive_device",
                "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
                "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device",
-               "astcenc_amd_sample_lod_tensors_device", "astcenc_amd_sample_cube_tensors_device"]
+               "astcenc_amd_sample_lod_tensors_device", "astcenc_amd_sample_cube_tensors_device",
+               "astcenc_amd_sample_volume_tensors_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
@@ -371,7 +372,7 @@ class LodGrid(C.Structure):
 
 
 def _check_chain(level_count, lod_bias):
-    """What lod_grid and cube_grid reject of a chain's length and of the bias."""
+    """What lod_grid, cube_grid and volume_grid reject of a chain's length and of the bias."""
     import math
     if not 1 <= level_count <= MAX_MIP_LEVELS:
         raise ValueError("level_count %r: a chain has 1 .. %d levels" % (level_count, MAX_MIP_LEVELS))
@@ -462,6 +463,52 @@ def cube_grid(first_entry, level_count, cube, dirs, lod, out_view, lod_bias=0.0,
         raise ValueError("out_view is %u x %u points, dirs %u x %u" % (r.out_x, r.out_y, dshape[1], dshape[0]))
     lptr, lod_row_pitch = _lod_buffer(lod, r.out_x, r.out_y, dirs.device, "dirs")
     return CubeGrid(first_entry, level_count, cube, r.out_x, r.out_y, dirs.data_ptr(), dir_row_pitch, lptr, lod_row_pitch, lod_bias, r.out, r.row_pitch, r.plane_pitch)
+
+
+class VolumeSampler(C.Structure):
+    """struct astcenc_amd_volume_sampler (include/astcenc_amd.h): SAMPLE_* filter within a level (SAMPLE_BILINEAR is linear on all
+    three axes), ADDRESS_* mode per axis, MIP_NEAREST / MIP_LINEAR between levels."""
+    _fields_ = [("filter", C.c_int), ("address_x", C.c_int), ("address_y", C.c_int), ("address_z", C.c_int), ("mip_filter", C.c_int)]
+
+
+class VolumeGrid(C.Structure):
+    """struct astcenc_amd_volume_grid (include/astcenc_amd.h)."""
+    _fields_ = [("first_entry", C.c_uint), ("level_count", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint),
+                ("coords", C.c_void_p), ("coord_row_pitch", C.c_size_t), ("lod", C.c_void_p), ("lod_row_pitch", C.c_size_t), ("lod_bias", C.c_float),
+                ("out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t)]
+
+
+def volume_grid(first_entry, level_count, coords, lod, out_view, lod_bias=0.0, layout=TENSOR_PLANAR, type=None):
+    """VolumeGrid of the chain entries[first_entry : first_entry + level_count]: `coords` is a float32 torch tensor [H, W, 3] of
+    NORMALISED (u, v, w) triples -- [1, N, 3] is a list of ray-march samples -- `lod` a float32 torch tensor [H, W] or None,
+    `out_view` the torch view [C, H, W] for TENSOR_PLANAR or [H, W, C] for TENSOR_INTERLEAVED; pointers and pitches come from the
+    strides.  ValueError for what the call cannot express: coordinates that are not float32, not [H, W, 3], whose triples are not
+    adjacent or not three floats apart or whose rows overlap; everything lod_grid rejects of `lod`, `out_view`, level_count and
+    lod_bias.  Or explicit tuples: coords = (ptr, out_x, out_y, coord_row_pitch), lod = (ptr, lod_row_pitch) or None, out_view =
+    (ptr, row_pitch, plane_pitch)."""
+    _check_chain(level_count, lod_bias)
+    if isinstance(coords, tuple):
+        cptr, out_x, out_y, coord_row_pitch = coords
+        optr, row_pitch, plane_pitch = out_view
+        lptr, lod_row_pitch = lod if lod is not None else (None, 0)
+        return VolumeGrid(first_entry, level_count, out_x, out_y, cptr, coord_row_pitch, lptr, lod_row_pitch, lod_bias, optr, row_pitch, plane_pitch)
+    import torch
+    if coords.dtype != torch.float32:
+        raise ValueError("coords is %s: float32 triples" % coords.dtype)
+    cshape, cst = tuple(coords.shape), tuple(coords.stride())
+    if coords.dim() != 3 or cshape[2] != 3:
+        raise ValueError("coords has shape %r: [H, W, 3]" % (cshape,))
+    if cst[2] != 1 or (cst[1] != 3 and cshape[1] > 1) or cst[0] < 0 or (cst[0] == 0 and cshape[0] > 1):
+        raise ValueError("the triples of coords must be adjacent floats, three floats apart, its rows apart (strides %r)" % (cst,))
+    coord_row_pitch = cst[0] if cshape[0] > 1 else 0
+    if coord_row_pitch != 0 and coord_row_pitch < 3 * cshape[1]:
+        raise ValueError("the rows of coords overlap (strides %r)" % (cst,))
+    # (the output's checks are scaled_region's: a window of 1 x 1 stands in for the one this call does not have)
+    r = scaled_region(first_entry, (0, 0, 0), (1, 1), out_view, layout=layout, type=type)
+    if (r.out_x, r.out_y) != (cshape[1], cshape[0]):
+        raise ValueError("out_view is %u x %u points, coords %u x %u" % (r.out_x, r.out_y, cshape[1], cshape[0]))
+    lptr, lod_row_pitch = _lod_buffer(lod, r.out_x, r.out_y, coords.device, "coords")
+    return VolumeGrid(first_entry, level_count, r.out_x, r.out_y, coords.data_ptr(), coord_row_pitch, lptr, lod_row_pitch, lod_bias, r.out, r.row_pitch, r.plane_pitch)
 
 
 class ErrorSums(C.Structure):
@@ -613,6 +660,10 @@ class Library:
             L.astcenc_amd_sample_cube_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(CubeSampler),
                                                                  C.POINTER(CubeGrid), C.c_uint, C.c_void_p]
             L.astcenc_amd_sample_cube_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_sample_volume_tensors_device"):
+            L.astcenc_amd_sample_volume_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(VolumeSampler),
+                                                                   C.POINTER(VolumeGrid), C.c_uint, C.c_void_p]
+            L.astcenc_amd_sample_volume_tensors_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_sample_tensors_device"):
             L.astcenc_amd_sample_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(Sampler),
                                                             C.POINTER(SampleGrid), C.c_uint, C.c_void_p]
@@ -871,6 +922,20 @@ class Library:
         garr = (CubeGrid * len(grids))(*grids) if grids else None
         return self.lib.astcenc_amd_sample_cube_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
                                                                C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_volume_tensors_device(self, ctx, entries, format, sampler, grids, stream=None):
+        """astcenc_amd_sample_volume_tensors_device: volumes (one level or a mip chain, 2D or 3D footprints) among the compressed
+        images `entries` sampled at normalised (u, v, w) at a level of detail per point into tensors of `format`.  sampler: a
+        VolumeSampler, or a (filter, address_x, address_y, address_z, mip_filter) tuple of SAMPLE_* / ADDRESS_* / MIP_NEAREST,
+        MIP_LINEAR constants.  grids: VolumeGrid, or (first_entry, level_count, coords, lod, out_view[, lod_bias]) tuples (see
+        volume_grid; the view is read with the format's layout and must have its type)."""
+        arr, n, s = self._set_args(entries, stream)
+        if sampler is not None and not isinstance(sampler, VolumeSampler):
+            sampler = VolumeSampler(*sampler)
+        grids = [g if isinstance(g, VolumeGrid) else volume_grid(*g, layout=format.layout, type=format.type) for g in grids]
+        garr = (VolumeGrid * len(grids))(*grids) if grids else None
+        return self.lib.astcenc_amd_sample_volume_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
+                                                                 C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):

@@ -362,9 +362,10 @@ struct astcenc_amd_sample_grid {
  *   writes, with either filter and any address mode, bit for bit what astcenc_amd_decompress_tensors_device writes for that
  *   window without flips, for U8, F16 and F32 entries.
  *
- *   Out of scope: anisotropy; sampling along z (z selects an array slice); 3D footprints; gradients with respect to coordinates or texels.
+ *   Out of scope: anisotropy; gradients with respect to coordinates or texels.
  *   Mip level selection and trilinear filtering are astcenc_amd_sample_lod_tensors_device's, below; cube maps sampled by
- *   direction are astcenc_amd_sample_cube_tensors_device's.
+ *   direction are astcenc_amd_sample_cube_tensors_device's; sampling along z (here z selects an array slice) and contexts of
+ *   3D footprints are astcenc_amd_sample_volume_tensors_device's.
  *
  *   - Entries, z inside the image, device ownership (of `coords` too), the null / zero-count cases, the format, pitches below the
  *     tight ones, a plane_pitch with INTERLEAVED, the alignment of `out`, a null `out` and the stream are checked as in
@@ -449,8 +450,9 @@ struct astcenc_amd_lod_grid {
  *   the bytes are those astcenc_amd_sample_tensors_device writes for that entry at (u * W_l, v * H_l).
  *
  *   Out of scope: level selection from coordinate derivatives (a log2 cannot be given a bit-exact contract: the caller supplies
- *   lambda); anisotropy; sampling along z; 3D footprints; gradients.
- *   Cube maps sampled by direction, seamless across faces, are astcenc_amd_sample_cube_tensors_device's, below.
+ *   lambda); anisotropy; gradients.
+ *   Cube maps sampled by direction, seamless across faces, are astcenc_amd_sample_cube_tensors_device's, below; sampling along
+ *   z and contexts of 3D footprints are astcenc_amd_sample_volume_tensors_device's.
  *
  *   - Everything astcenc_amd_sample_tensors_device checks is checked here with the same error codes -- the entries, the format,
  *     the sampler's filter and address modes, out_x and out_y, `coords` and its pitch, `out` and its pitches, device ownership,
@@ -541,7 +543,8 @@ struct astcenc_amd_cube_grid {
  *   product are exact, so the face coordinate is (x + 0.5, y + 0.5).  Scaling a direction by a power of two changes nothing as
  *   long as no component overflows or leaves the subnormal range inexactly.
  *
- *   Out of scope: level selection from derivatives; anisotropy; solid-angle weighting; 3D footprints; gradients.
+ *   Out of scope: level selection from derivatives; anisotropy; solid-angle weighting; gradients.  Contexts of 3D footprints
+ *   are sampled by astcenc_amd_sample_volume_tensors_device, below (volumes, not cubes).
  *
  *   - Everything astcenc_amd_sample_lod_tensors_device checks is checked here with its error codes -- the entries, the format,
  *     the filters, out_x and out_y, the chain, lod, lod_bias and their pitch, `out` and its pitches, device ownership (of `dirs`
@@ -559,6 +562,92 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_cube_tensors_device(
 	const struct astcenc_amd_tensor_format* format,
 	const struct astcenc_amd_cube_sampler* sampler,
 	const struct astcenc_amd_cube_grid* grids, unsigned int grid_count,
+	void* hip_stream);
+
+/* Compressed volumes sampled at (u, v, w) at a level of detail per point straight into tensors: the 3D lookup of a texture unit
+ * -- "the filtered texel at (u, v, w) at level of detail lambda" for a buffer of triples: the samples of a ray marcher through a
+ * CT or simulation volume, a fog or density grid, a 3D colour LUT, the feature grid of a neural field -- with every level staying
+ * compressed, whether the context's footprint is 2D (the slices are compressed one by one) or one of the ten 3D footprints.  A
+ * chain is level_count consecutive entries as in astcenc_amd_sample_lod_tensors_device -- what
+ * astcenc_amd_compress_mip_chain_volume_device writes -- and a chain of one level with a NULL `lod` is a volume without mips.
+ *
+ * The sampler holds for the whole call. */
+struct astcenc_amd_volume_sampler {
+	enum astcenc_amd_sample_filter filter;          /* NEAREST, or BILINEAR = linear on all three axes (trilinear, 8 taps) */
+	enum astcenc_amd_sample_address address_x, address_y, address_z;
+	enum astcenc_amd_mip_level_filter mip_filter;   /* MIP_NEAREST or MIP_LINEAR between levels */
+};
+
+struct astcenc_amd_volume_grid {
+	unsigned int first_entry, level_count;  /* entries[first_entry + l] is level l; 1 <= level_count <= 32 */
+	unsigned int out_x, out_y;              /* points per row / rows of points, each 1 .. 65535 */
+	const float* coords;                    /* device pointer: point (i, j) is the triple at coords[j * coord_row_pitch + 3 * i], u, v, w,
+	                                           NORMALISED: the volume is [0, 1) x [0, 1) x [0, 1) at every level; 4-byte aligned */
+	size_t coord_row_pitch;                 /* in floats; 0 = 3 * out_x; otherwise >= 3 * out_x */
+	const float* lod;                       /* device pointer: point (i, j) has lod[j * lod_row_pitch + i]; NULL: 0 everywhere */
+	size_t lod_row_pitch;                   /* in floats; 0 = out_x */
+	float lod_bias;                         /* added to every point's lod; finite */
+	void* out;                              /* device pointer: element (c = 0, j = 0, i = 0) */
+	size_t row_pitch, plane_pitch;          /* in ELEMENTS of the format's type; 0 = tightly packed */
+};
+
+/* Sample grids[0 .. grid_count) into tensors of `format` (astcenc_amd_decompress_tensors_device's).  For point (i, j) of a grid,
+ * 0 <= i < out_x, 0 <= j < out_y, with (u, v, w) read from `coords` and lod from `lod`, and channel c < format->channels (reals
+ * are IEEE binary64 below unless said otherwise; "one operation" is one IEEE operation, round to nearest even, never fused):
+ *
+ *   Levels.  Level l is the image of entries[first_entry + l], W_l x H_l x D_l texels (dim_x, dim_y, dim_z).  The levels of a
+ *     chain may have any sizes, none above 65536 along any axis, and each level has its entry's data_type and swizzle.  With a
+ *     2D footprint the slices of an entry are block layers of depth 1, as everywhere in this interface; with a 3D footprint the
+ *     blocks are block_z slices deep and the last layer may be partial.
+ *   Validity.  lambda' = lod + lod_bias, one binary32 addition; lod = +0.0 when `lod` is NULL.  A point is VALID when u, v and w
+ *     are finite and no larger than 2^14 in magnitude (2^14 itself is valid) and lambda' is not a NaN.  An invalid point has
+ *     s[c] = +0.0 for every channel and then goes through "Arithmetic, storage" like any other.
+ *   Level of detail.  That of astcenc_amd_sample_lod_tensors_device: lambda_c, the one level of MIP_NEAREST, the two levels and
+ *     g of MIP_LINEAR, the level of weight zero that is not part of the sum and none of whose blocks is read.
+ *   Within a level.  x = (double)u * (double)W_l, y = (double)v * (double)H_l and z = (double)w * (double)D_l: exact products
+ *     (24 bits by 17).  On each of the three axes on its own, the "Taps" rule of astcenc_amd_sample_tensors_device with the
+ *     level's size along that axis: NEAREST has one tap, index floor(x), weight 1; BILINEAR has t = x - 0.5, i0 = floor(t),
+ *     f = t - i0, tap 0 of index i0 and weight 1.0 - f and tap 1 of index i0 + 1 and weight f.  So BILINEAR is linear on all
+ *     three axes: up to 2 x 2 x 2 = 8 taps.  Each tap index goes through the sample call's "Addressing" with its own axis's
+ *     mode (address_x, address_y, address_z) and size.  A BORDER tap outside on ANY of the three axes has the value +0.0 in
+ *     every channel, IS part of the sums, and its block is not read.  A tap of weight 0 on any axis (tap 1 when f = 0) is not
+ *     part of any sum and its block is not read.
+ *   Source.  v(kx, ky, kz)[c] is component c of the texel astcenc_amd_decompress_regions_device writes for (kx, ky, kz) of the
+ *     level's entry, widened to binary64, as in the sample call.
+ *   Sums.  For every (y tap, z tap): a row r(ky, kz) = wx0 * v(kx0, ky, kz)[c] [+ wx1 * v(kx1, ky, kz)[c]].  For every z tap: a
+ *     plane p(kz) = wy0 * r(ky0, kz) [+ wy1 * r(ky1, kz)].  Then acc = wz0 * p(kz0) [+ wz1 * p(kz1)].  The bracketed term is
+ *     there when the axis has two taps.  A sum starts as its first product; every product and every sum is one operation.
+ *     s_l[c] = (float)acc: one rounding to binary32 per level.
+ *   Blend.  That of astcenc_amd_sample_lod_tensors_device: one level, s[c] = s_l[c]; two levels,
+ *     s[c] = (float)((1.0 - g) * (double)s_l0[c] + g * (double)s_l1[c]), one rounding after the blend.
+ *   Arithmetic, storage, placement.  Those of astcenc_amd_sample_tensors_device.
+ *
+ *   Consequences: where the z axis has one tap -- under NEAREST, and under BILINEAR where w * D_l - 0.5 is an integer, the
+ *   remaining weight then being exactly 1.0 and 1.0 * p being p -- the level's sample is the sample call's for slice kz of that
+ *   entry at (x, y); on a context of a 2D footprint, a grid all of whose points have one z tap of the same kz in every level
+ *   they use writes the bytes astcenc_amd_sample_lod_tensors_device writes for z = kz.  Where W_l, H_l and D_l are powers of
+ *   two, the texel centres ((kx + 0.5) / W_l, (ky + 0.5) / H_l, (kz + 0.5) / D_l) of a level selected with weight 1 reproduce,
+ *   with either filter and any address modes, what astcenc_amd_decompress_tensors_device writes for those texels.
+ *
+ *   Out of scope: level selection from derivatives; anisotropy; gradients.
+ *
+ *   - Everything astcenc_amd_sample_lod_tensors_device checks is checked here with its error codes -- the entries, the format,
+ *     the filters and address_x / address_y, out_x and out_y, the chain, lod, lod_bias and their pitch, `out` and its pitches,
+ *     device ownership (of `coords` and `lod` too), the work items -- everything before anything is launched; a failure returns
+ *     its error with nothing written, and the log callback names the index: "grid i of n".  There is no slice to check and no
+ *     footprint is refused: all 2D and all 3D footprints are sampled.
+ *   - Also ASTCENC_ERR_BAD_PARAM: an address_z that is not an address mode; a `coords` not aligned to 4 bytes; a non-zero
+ *     coord_row_pitch below 3 * out_x; a level with dim_x, dim_y or dim_z above 65536; an entry of 2^32 - 1 blocks or more,
+ *     counted as ceil(dim_x / block_x) * ceil(dim_y / block_y) * ceil(dim_z / block_z).  A null `coords`:
+ *     ASTCENC_ERR_BAD_CONTEXT.  Coordinates and levels of detail are data: none of them is an error.
+ *   - Work items are the lod call's tiles of 64 points and its pass per distinct level; a pass decodes every block its points'
+ *     taps reach once, at most 512 of them, so with a 3D footprint the taps of a point that share a block cost one decode. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_volume_tensors_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_volume_sampler* sampler,
+	const struct astcenc_amd_volume_grid* grids, unsigned int grid_count,
 	void* hip_stream);
 
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
