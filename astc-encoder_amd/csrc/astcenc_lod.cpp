@@ -19,71 +19,17 @@ astcenc_error astcenc_amd_sample_lod_tensors_device(astcenc_context* ctx, const 
 	const char* fn = "astcenc_amd_sample_lod_tensors_device";
 	if (grid_count == 0) return ASTCENC_SUCCESS;
 	if (!ctx || !grids || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
-	astcenc_error status = check_tensor_format(fn, format);
-	if (status != ASTCENC_SUCCESS) return status;
-	if (!sampler)
-	{
-		backend_log("%s: sampler is null", fn);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_mip_level_filter(fn, (int)sampler->mip_filter);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_sample_footprint(fn, ctx);
-	if (status != ASTCENC_SUCCESS) return status;
 	DecodeTensorFormat fmt;
-	status = check_tensor_factors(fn, format, fmt);
-	if (status != ASTCENC_SUCCESS) return status;
-
 	std::vector<DecompressDeviceJob> jobs;
-	status = check_sample_entries(fn, ctx, entries, entry_count, jobs);
+	astcenc_error status = check_lod_call(fn, ctx, entries, entry_count, format, sampler, fmt, jobs);
 	if (status != ASTCENC_SUCCESS) return status;
 
 	std::vector<DecodeLodLaunch> launches(grid_count);
 	unsigned long long tiles = 0;
 	for (unsigned int i = 0; i < grid_count; i++)
 	{
-		const astcenc_amd_lod_grid& g = grids[i];
-		status = check_lod_chain(fn, i, grid_count, g.first_entry, g.level_count, entry_count);
+		status = check_lod_grid(fn, i, grid_count, entries, entry_count, format, grids[i], grids[i].out, "out", launches[i], tiles);
 		if (status != ASTCENC_SUCCESS) return status;
-		for (unsigned int l = 0; l < g.level_count; l++)
-		{
-			const astcenc_amd_image_set_entry& en = entries[g.first_entry + l];
-			if (g.z >= en.dim_z)
-			{
-				backend_log("%s: grid %u of %u: slice %u is not inside the %u x %u x %u image of entry %u (level %u)", fn, i, grid_count, g.z, en.dim_x, en.dim_y,
-				            en.dim_z, g.first_entry + l, l);
-				return ASTCENC_ERR_BAD_PARAM;
-			}
-			// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
-			if (en.dim_x > 65536 || en.dim_y > 65536)
-			{
-				backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u texels: a level is at most 65536 along x and y", fn, i, grid_count, g.first_entry + l, l,
-				            en.dim_x, en.dim_y);
-				return ASTCENC_ERR_BAD_PARAM;
-			}
-		}
-		status = check_lod_pitch(fn, i, grid_count, g.lod_bias, g.lod_row_pitch, g.out_x);
-		if (status != ASTCENC_SUCCESS) return status;
-		SampleGridShape shape = { g.out_x, g.out_y, g.coords, g.coord_row_pitch, g.out, g.row_pitch, g.plane_pitch };
-		status = check_sample_grid(fn, i, grid_count, format, shape);
-		if (status != ASTCENC_SUCCESS) return status;
-		size_t lod_row_pitch = g.lod_row_pitch;
-		status = check_lod_buffer(fn, i, grid_count, g.lod, lod_row_pitch, g.out_x, g.out_y);
-		if (status != ASTCENC_SUCCESS) return status;
-		DecodeLodLaunch& l = launches[i];
-		l.first_entry = g.first_entry; l.level_count = g.level_count;
-		l.z = g.z;
-		l.out_x = g.out_x; l.out_y = g.out_y;
-		l.d_coords = g.coords;
-		l.coord_row_pitch = shape.coord_row_pitch;
-		l.d_lod = g.lod;
-		l.lod_row_pitch = lod_row_pitch;
-		l.lod_bias = g.lod_bias;
-		l.d_out = g.out;
-		l.row_pitch = shape.row_pitch; l.plane_pitch = shape.plane_pitch;
-		if (!add_sample_tiles(fn, i, grid_count, g.out_x, g.out_y, tiles)) return ASTCENC_ERR_BAD_PARAM;
 	}
 
 	DecodeLodSampler smp;

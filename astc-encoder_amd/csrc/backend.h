@@ -269,6 +269,18 @@ struct DecompressLodJob {
 	void*    stream;
 };
 int backend_decompress_lod(Backend* b, const DecompressLodJob& job);
+/* astcenc_amd_sample_lod_grad_device: the same with the grids as DecodeLodGradLaunch. */
+struct DecodeLodGradLaunch;
+struct DecompressLodGradJob {
+	const DecompressDeviceJob* entries;
+	uint32_t entry_count;
+	const DecodeTensorFormat* format;
+	const DecodeLodSampler* sampler;
+	const DecodeLodGradLaunch* grids;
+	uint32_t grid_count;
+	void*    stream;
+};
+int backend_decompress_lod_grad(Backend* b, const DecompressLodGradJob& job);
 /* astcenc_amd_sample_cube_tensors_device: the same with the cube sampler and the grids as DecodeCubeLaunch. */
 struct DecodeCubeSampler;
 struct DecodeCubeLaunch;
@@ -539,6 +551,21 @@ size_t astc_decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count);
 uint32_t astc_decode_lod_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
                                const DecodeLodLaunch* grids, uint32_t count);
 int astc_decode_lod_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
+/* The gradients of that call (astcenc_amd_sample_lod_grad_device; decode_lod_grad.h, kernel_decode_lod_grad.hip): the forward
+ * call's launch with grad_out and its pitches in the place of the output -- it is read -- and the two buffers that are written,
+ * checked by the entry point: grad_coords aligned to a pair, its pitch even, grad_lod (when given) aligned to a float, the
+ * pitches resolved and at least the tight ones.  Work items, table and launch as the lod call's. */
+struct DecodeLodGradLaunch {
+	DecodeLodLaunch lod;                  // d_out, row_pitch, plane_pitch: grad_out's
+	float*   d_grad_coords;               // point (i, j): the pair at d_grad_coords[j * grad_coord_row_pitch + 2 i]
+	size_t   grad_coord_row_pitch;        // floats
+	float*   d_grad_lod;                  // point (i, j): d_grad_lod[j * grad_lod_row_pitch + i]; null: not wanted
+	size_t   grad_lod_row_pitch;          // floats
+};
+size_t astc_decode_lod_grad_bytes(const DecodeLodGradLaunch* grids, uint32_t count);
+uint32_t astc_decode_lod_grad_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                    const DecodeLodGradLaunch* grids, uint32_t count);
+int astc_decode_lod_grad_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* Cube maps sampled by direction at a level of detail per point (astcenc_amd_sample_cube_tensors_device; decode_cube.h,
  * kernel_decode_cube.hip): the call's format and sampler and one DecodeCubeLaunch per grid, checked by the entry point -- as the
  * lod call's, and: every level square, no larger than 65536, with layers 6 cube .. 6 cube + 5; the directions aligned to a float,

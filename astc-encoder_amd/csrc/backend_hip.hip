@@ -1708,6 +1708,29 @@ int backend_decompress_lod(Backend* b, const DecompressLodJob& job)
 		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_lod_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
 }
 
+/* (as backend_decompress_lod, with five buffers a grid: grad_out, the coordinates, the levels of detail, grad_coords and grad_lod;
+ *  grad_out stands in for a null lod, grad_coords for a null grad_lod) */
+int backend_decompress_lod_grad(Backend* b, const DecompressLodGradJob& job)
+{
+	std::vector<uint8_t> used(job.entry_count, 0);
+	for (uint32_t i = 0; i < job.grid_count; i++)
+		for (uint32_t l = 0; l < job.grids[i].lod.level_count; l++) used[job.grids[i].lod.first_entry + l] = 1;
+	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample lod grad",
+		[&](uint32_t i)
+		{
+			const DecodeLodGradLaunch& g = job.grids[i / 5u];
+			const void* const buffers[5] = { g.lod.d_out, g.lod.d_coords, g.lod.d_lod ? static_cast<const void*>(g.lod.d_lod) : g.lod.d_out, g.d_grad_coords,
+			                                 g.d_grad_lod ? g.d_grad_lod : g.d_grad_coords };
+			return buffers[i % 5u];
+		},
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? astc_decode_lod_grad_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count)
+			           : astc_decode_lod_grad_bytes(job.grids, job.grid_count);
+		},
+		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_lod_grad_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 5u);
+}
+
 /* (as backend_decompress_lod: a grid's buffers are the output, the directions and, unless null, the levels of detail) */
 int backend_decompress_cube(Backend* b, const DecompressCubeJob& job)
 {

@@ -14,7 +14,7 @@
 // The level walk (lod_walk_tile) takes how a lane reads its point and forms its taps in a level as a parameter: decode_cube.h runs
 // it over directions and cube faces, decode_volume.h over triples and eight taps.
 //
-// Included by kernel_decode_lod.hip, decode_cube.h, decode_volume.h and tests/harness/decode_lod_check.cpp only.
+// Included by kernel_decode_lod.hip, decode_cube.h, decode_volume.h, decode_lod_grad.h and tests/harness/decode_lod_check.cpp only.
 //
 // Layout: ImageSetTable (count = grids, total = tiles), first[count], padding, DecodeLodRecord[count], then the DecodeLodLevel
 // records of grid 0's levels, of grid 1's ...; a grid's record holds the byte offset of its first level record from the table's start.
@@ -64,6 +64,36 @@ inline size_t decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count)
 	return decode_lod_levels_offset(count) + levels * sizeof(DecodeLodLevel);
 }
 
+/* The record of grid `g` and the records of its levels, which start `level_at` bytes into the table `t` (decode_lod_grad.h
+ * fills the forward half of its records with this too). */
+inline void decode_lod_record(DecodeLodRecord& r, uint8_t* t, size_t level_at, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format,
+                              const DecodeLodSampler& sampler, const DecodeLodLaunch& g)
+{
+	r.coords = g.d_coords;
+	r.coord_row = g.coord_row_pitch;
+	r.lod = g.d_lod;
+	r.lod_row = g.lod_row_pitch;
+	r.out = g.d_out;
+	r.row = g.row_pitch;
+	r.levels = level_at;
+	r.level_count = g.level_count;
+	r.z = g.z;
+	r.out_x = g.out_x; r.out_y = g.out_y;
+	r.filter = sampler.filter; r.address_x = sampler.address_x; r.address_y = sampler.address_y; r.mip_filter = sampler.mip_filter;
+	r.tw_log2 = decode_sample_tw_log2(g.out_y);
+	r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
+	r.x_step = tensor_x_step(format);
+	r.lod_bias = g.lod_bias;
+	r.fmt = tensor_params(format, g.plane_pitch);
+	for (uint32_t l = 0; l < g.level_count; l++)
+	{
+		DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at + (size_t)l * sizeof(DecodeLodLevel));
+		lv.img = images[g.first_entry + l];
+		lv.img.data = nullptr;
+		lv.blocks = streams[g.first_entry + l];
+	}
+}
+
 /* Writes the table of `count` grids over the images `images` (prepared, 2D footprints, `data` unused) and their streams;
  * returns the tiles of all grids (the caller has made sure they fit 32 bits). */
 inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
@@ -77,31 +107,8 @@ inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uin
 	for (uint32_t i = 0; i < count; i++)
 	{
 		const DecodeLodLaunch& g = grids[i];
-		DecodeLodRecord& r = rec[i];
-		r.coords = g.d_coords;
-		r.coord_row = g.coord_row_pitch;
-		r.lod = g.d_lod;
-		r.lod_row = g.lod_row_pitch;
-		r.out = g.d_out;
-		r.row = g.row_pitch;
-		r.levels = level_at;
-		r.level_count = g.level_count;
-		r.z = g.z;
-		r.out_x = g.out_x; r.out_y = g.out_y;
-		r.filter = sampler.filter; r.address_x = sampler.address_x; r.address_y = sampler.address_y; r.mip_filter = sampler.mip_filter;
-		r.tw_log2 = decode_sample_tw_log2(g.out_y);
-		r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
-		r.x_step = tensor_x_step(format);
-		r.lod_bias = g.lod_bias;
-		r.fmt = tensor_params(format, g.plane_pitch);
-		for (uint32_t l = 0; l < g.level_count; l++)
-		{
-			DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at);
-			lv.img = images[g.first_entry + l];
-			lv.img.data = nullptr;
-			lv.blocks = streams[g.first_entry + l];
-			level_at += sizeof(DecodeLodLevel);
-		}
+		decode_lod_record(rec[i], t, level_at, images, streams, format, sampler, g);
+		level_at += (size_t)g.level_count * sizeof(DecodeLodLevel);
 		first[i] = tiles;
 		tiles += (uint32_t)decode_sample_tiles(g.out_x, g.out_y);
 	}

@@ -130,7 +130,7 @@ struct TensorPitches { size_t row, slice, plane; };
 
 inline astcenc_error check_output_tensor(const char* fn, const char* noun, unsigned int i, unsigned int count, const astcenc_amd_tensor_format* format,
                                          unsigned int size_x, unsigned int size_y, unsigned int size_z, TensorPitches& p, const void* out,
-                                         bool overflow = false, const char* also_null = nullptr)
+                                         bool overflow = false, const char* also_null = nullptr, const char* out_name = "out")
 {
 	const bool planar = format->layout == ASTCENC_AMD_TENSOR_PLANAR;
 	const size_t element = format->type == ASTCENC_AMD_TENSOR_F32 ? 4 : 2;
@@ -160,12 +160,12 @@ inline astcenc_error check_output_tensor(const char* fn, const char* noun, unsig
 	// (a null buffer: what the other device calls return for one)
 	if (!out || also_null)
 	{
-		backend_log("%s: %s %u of %u: %s is null", fn, noun, i, count, !out ? "out" : also_null);
+		backend_log("%s: %s %u of %u: %s is null", fn, noun, i, count, !out ? out_name : also_null);
 		return ASTCENC_ERR_BAD_CONTEXT;
 	}
 	if (reinterpret_cast<uintptr_t>(out) % element != 0)
 	{
-		backend_log("%s: %s %u of %u: out %p is not aligned to the element size %zu", fn, noun, i, count, out, element);
+		backend_log("%s: %s %u of %u: %s %p is not aligned to the element size %zu", fn, noun, i, count, out_name, out, element);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	p.row = row_pitch; p.slice = slice_pitch; p.plane = planar ? plane_pitch : 0;

@@ -1,8 +1,9 @@
 // SPDX-License-Identifier: Apache-2.0
-// What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_cube.cpp,
-// astcenc_volume.cpp): the
+// What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_lod_grad.cpp,
+// astcenc_cube.cpp, astcenc_volume.cpp): the
 // checks of the sampler's filter and address modes, of the footprint, of the entries' block counts, of a grid's points and
-// coordinates (or directions), of a chain and of the levels of detail, with the sample and lod calls' error codes and log lines.
+// coordinates (or directions), of a chain and of the levels of detail, with the sample and lod calls' error codes and log lines;
+// the lod call's checks as a whole (check_lod_call, check_lod_grid), which its gradient repeats, and those of the gradients' buffers.
 // `fn` names the entry point in the log.
 #pragma once
 #include "regions_internal.h"
@@ -65,7 +66,8 @@ struct SampleGridShape {
 	size_t row_pitch, plane_pitch;
 };
 
-inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, SampleGridShape& g)
+inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, SampleGridShape& g,
+                                       const char* out_name = "out")
 {
 	if (g.out_x == 0 || g.out_y == 0 || g.out_x > 65535 || g.out_y > 65535)
 	{
@@ -82,7 +84,8 @@ inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned 
 	const size_t coord_row_pitch = g.coord_row_pitch ? g.coord_row_pitch : 2u * (size_t)g.out_x;
 	(void)mul_safe(mul_safe(coord_row_pitch, g.out_y, overflow), sizeof(float), overflow);
 	TensorPitches pitches = { g.row_pitch, 0, g.plane_pitch };
-	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.coords ? "coords" : nullptr);
+	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.coords ? "coords" : nullptr,
+	                                                 out_name);
 	if (status != ASTCENC_SUCCESS) return status;
 	if (reinterpret_cast<uintptr_t>(g.coords) % 8 != 0)
 	{
@@ -153,6 +156,114 @@ inline astcenc_error check_lod_buffer(const char* fn, unsigned int i, unsigned i
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	lod_row_pitch = resolved;
+	return ASTCENC_SUCCESS;
+}
+
+/* The running sum of the call's tiles after grid i; false (logged) past 2^32 - 1. */
+inline bool add_sample_tiles(const char* fn, unsigned int i, unsigned int grid_count, unsigned int out_x, unsigned int out_y, unsigned long long& tiles)
+{
+	tiles += astc_decode_sample_tiles(out_x, out_y);
+	if (tiles <= 0xFFFFFFFFull) return true;
+	backend_log("%s: grid %u of %u: more than 2^32 - 1 tiles of points in all", fn, i, grid_count);
+	return false;
+}
+
+/* What the lod call and its gradient check before their grids (astcenc_lod.cpp, astcenc_lod_grad.cpp): the format, the sampler,
+ * the footprint and the entries; `fmt` and `jobs` come back filled. */
+inline astcenc_error check_lod_call(const char* fn, astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                    const astcenc_amd_tensor_format* format, const astcenc_amd_lod_sampler* sampler, DecodeTensorFormat& fmt,
+                                    std::vector<DecompressDeviceJob>& jobs)
+{
+	astcenc_error status = check_tensor_format(fn, format);
+	if (status != ASTCENC_SUCCESS) return status;
+	if (!sampler)
+	{
+		backend_log("%s: sampler is null", fn);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = check_mip_level_filter(fn, (int)sampler->mip_filter);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = check_sample_footprint(fn, ctx);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = check_tensor_factors(fn, format, fmt);
+	if (status != ASTCENC_SUCCESS) return status;
+	return check_sample_entries(fn, ctx, entries, entry_count, jobs);
+}
+
+/* ... and of grid i, an astcenc_amd_lod_grid or an astcenc_amd_lod_grad_grid: the chain, the slice and the size of every level,
+ * the levels of detail, the points, the coordinates and the tensor `out` (the forward call's output or the gradient call's
+ * grad_out, named `out_name` in the log); the launch comes back filled and the grid's tiles are added to `tiles`. */
+template <class Grid>
+inline astcenc_error check_lod_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                    const astcenc_amd_tensor_format* format, const Grid& g, void* out, const char* out_name, DecodeLodLaunch& l, unsigned long long& tiles)
+{
+	astcenc_error status = check_lod_chain(fn, i, grid_count, g.first_entry, g.level_count, entry_count);
+	if (status != ASTCENC_SUCCESS) return status;
+	for (unsigned int lv = 0; lv < g.level_count; lv++)
+	{
+		const astcenc_amd_image_set_entry& en = entries[g.first_entry + lv];
+		if (g.z >= en.dim_z)
+		{
+			backend_log("%s: grid %u of %u: slice %u is not inside the %u x %u x %u image of entry %u (level %u)", fn, i, grid_count, g.z, en.dim_x, en.dim_y,
+			            en.dim_z, g.first_entry + lv, lv);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+		// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
+		if (en.dim_x > 65536 || en.dim_y > 65536)
+		{
+			backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u texels: a level is at most 65536 along x and y", fn, i, grid_count, g.first_entry + lv, lv,
+			            en.dim_x, en.dim_y);
+			return ASTCENC_ERR_BAD_PARAM;
+		}
+	}
+	status = check_lod_pitch(fn, i, grid_count, g.lod_bias, g.lod_row_pitch, g.out_x);
+	if (status != ASTCENC_SUCCESS) return status;
+	SampleGridShape shape = { g.out_x, g.out_y, g.coords, g.coord_row_pitch, out, g.row_pitch, g.plane_pitch };
+	status = check_sample_grid(fn, i, grid_count, format, shape, out_name);
+	if (status != ASTCENC_SUCCESS) return status;
+	size_t lod_row_pitch = g.lod_row_pitch;
+	status = check_lod_buffer(fn, i, grid_count, g.lod, lod_row_pitch, g.out_x, g.out_y);
+	if (status != ASTCENC_SUCCESS) return status;
+	l.first_entry = g.first_entry; l.level_count = g.level_count;
+	l.z = g.z;
+	l.out_x = g.out_x; l.out_y = g.out_y;
+	l.d_coords = g.coords;
+	l.coord_row_pitch = shape.coord_row_pitch;
+	l.d_lod = g.lod;
+	l.lod_row_pitch = lod_row_pitch;
+	l.lod_bias = g.lod_bias;
+	l.d_out = out;
+	l.row_pitch = shape.row_pitch; l.plane_pitch = shape.plane_pitch;
+	return add_sample_tiles(fn, i, grid_count, g.out_x, g.out_y, tiles) ? ASTCENC_SUCCESS : ASTCENC_ERR_BAD_PARAM;
+}
+
+/* A buffer of the gradient call that is written, `name` with its pitch `pitch_name`: `per_point` floats a point (2: grad_coords,
+ * aligned to 8 bytes, an even pitch; 1: grad_lod, aligned to 4 bytes); the pitch comes back resolved. */
+inline astcenc_error check_grad_buffer(const char* fn, unsigned int i, unsigned int grid_count, const char* name, const char* pitch_name, const float* buffer,
+                                       size_t& row_pitch, unsigned int per_point, unsigned int out_x, unsigned int out_y)
+{
+	const size_t tight = (size_t)per_point * out_x;
+	if ((per_point == 2 && (row_pitch & 1u) != 0) || (row_pitch != 0 && row_pitch < tight))
+	{
+		backend_log("%s: grid %u of %u: %s %zu: %sat least %zu floats", fn, i, grid_count, pitch_name, row_pitch, per_point == 2 ? "even and " : "", tight);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	const size_t resolved = row_pitch ? row_pitch : tight;
+	bool overflow = false;
+	(void)mul_safe(mul_safe(resolved, out_y, overflow), sizeof(float), overflow);
+	if (overflow)
+	{
+		backend_log("%s: grid %u of %u: %s %zu: the gradients do not fit 64 bits", fn, i, grid_count, pitch_name, row_pitch);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (reinterpret_cast<uintptr_t>(buffer) % (4u * per_point) != 0)
+	{
+		backend_log("%s: grid %u of %u: %s %p is not aligned to %u bytes", fn, i, grid_count, name, static_cast<const void*>(buffer), 4u * per_point);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	row_pitch = resolved;
 	return ASTCENC_SUCCESS;
 }
 
@@ -230,15 +341,6 @@ inline astcenc_error check_volume_entries(const char* fn, astcenc_context* ctx, 
 		}
 	}
 	return ASTCENC_SUCCESS;
-}
-
-/* The running sum of the call's tiles after grid i; false (logged) past 2^32 - 1. */
-inline bool add_sample_tiles(const char* fn, unsigned int i, unsigned int grid_count, unsigned int out_x, unsigned int out_y, unsigned long long& tiles)
-{
-	tiles += astc_decode_sample_tiles(out_x, out_y);
-	if (tiles <= 0xFFFFFFFFull) return true;
-	backend_log("%s: grid %u of %u: more than 2^32 - 1 tiles of points in all", fn, i, grid_count);
-	return false;
 }
 
 } // namespace astcd

@@ -106,7 +106,7 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
                "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device",
                "astcenc_amd_sample_lod_tensors_device", "astcenc_amd_sample_cube_tensors_device",
-               "astcenc_amd_sample_volume_tensors_device"]
+               "astcenc_amd_sample_volume_tensors_device", "astcenc_amd_sample_lod_grad_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
@@ -420,6 +420,37 @@ def lod_grid(first_entry, level_count, z, coords, lod, out_view, lod_bias=0.0, l
     return LodGrid(first_entry, level_count, z, g.out_x, g.out_y, g.coords, g.coord_row_pitch, lptr, lod_row_pitch, lod_bias, g.out, g.row_pitch, g.plane_pitch)
 
 
+class LodGradGrid(C.Structure):
+    """struct astcenc_amd_lod_grad_grid (include/astcenc_amd.h)."""
+    _fields_ = [("first_entry", C.c_uint), ("level_count", C.c_uint), ("z", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint),
+                ("coords", C.c_void_p), ("coord_row_pitch", C.c_size_t), ("lod", C.c_void_p), ("lod_row_pitch", C.c_size_t), ("lod_bias", C.c_float),
+                ("grad_out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t),
+                ("grad_coords", C.c_void_p), ("grad_coord_row_pitch", C.c_size_t), ("grad_lod", C.c_void_p), ("grad_lod_row_pitch", C.c_size_t)]
+
+
+def lod_grad_grid(first_entry, level_count, z, coords, lod, grad_out, grad_coords, grad_lod=None, lod_bias=0.0, layout=TENSOR_PLANAR, type=None):
+    """LodGradGrid of the forward grid lod_grid(first_entry, level_count, z, coords, lod, <out>): `grad_out` is the torch view of the
+    upstream gradient, of the forward output's shape and type ([C, H, W] or [H, W, C]); `grad_coords` a float32 torch tensor
+    [H, W, 2] and `grad_lod` a float32 torch tensor [H, W] or None (not wanted), which are written.  ValueError for everything
+    lod_grid rejects -- of `grad_out` what it rejects of the output, of `grad_coords` what it rejects of `coords`, of `grad_lod`
+    what it rejects of `lod` -- and for a `grad_coords` of another H, W or on another device than `coords`.  Or explicit tuples:
+    coords = (ptr, out_x, out_y, coord_row_pitch), lod = (ptr, lod_row_pitch) or None, grad_out = (ptr, row_pitch, plane_pitch),
+    grad_coords = (ptr, grad_coord_row_pitch), grad_lod = (ptr, grad_lod_row_pitch) or None."""
+    g = lod_grid(first_entry, level_count, z, coords, lod, grad_out, lod_bias=lod_bias, layout=layout, type=type)
+    if isinstance(coords, tuple):
+        gcptr, grad_coord_row_pitch = grad_coords
+        glptr, grad_lod_row_pitch = grad_lod if grad_lod is not None else (None, 0)
+    else:
+        # (the pairs of gradients are laid out as pairs of coordinates are: sample_grid's checks, with a view that passes them as the output)
+        w = sample_grid(first_entry, z, grad_coords, grad_out, layout=layout, type=type)
+        if grad_coords.device != coords.device:
+            raise ValueError("grad_coords is on %s, coords on %s" % (grad_coords.device, coords.device))
+        gcptr, grad_coord_row_pitch = w.coords, w.coord_row_pitch
+        glptr, grad_lod_row_pitch = _lod_buffer(grad_lod, g.out_x, g.out_y, coords.device, "coords")
+    return LodGradGrid(first_entry, level_count, z, g.out_x, g.out_y, g.coords, g.coord_row_pitch, g.lod, g.lod_row_pitch, lod_bias, g.out, g.row_pitch, g.plane_pitch,
+                       gcptr, grad_coord_row_pitch, glptr, grad_lod_row_pitch)
+
+
 class CubeSampler(C.Structure):
     """struct astcenc_amd_cube_sampler (include/astcenc_amd.h): SAMPLE_* filter within a level, MIP_NEAREST / MIP_LINEAR between
     levels."""
@@ -656,6 +687,10 @@ class Library:
             L.astcenc_amd_sample_lod_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(LodSampler),
                                                                 C.POINTER(LodGrid), C.c_uint, C.c_void_p]
             L.astcenc_amd_sample_lod_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_sample_lod_grad_device"):
+            L.astcenc_amd_sample_lod_grad_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(LodSampler),
+                                                             C.POINTER(LodGradGrid), C.c_uint, C.c_void_p]
+            L.astcenc_amd_sample_lod_grad_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_sample_cube_tensors_device"):
             L.astcenc_amd_sample_cube_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(CubeSampler),
                                                                  C.POINTER(CubeGrid), C.c_uint, C.c_void_p]
@@ -909,6 +944,28 @@ class Library:
         garr = (LodGrid * len(grids))(*grids) if grids else None
         return self.lib.astcenc_amd_sample_lod_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
                                                               C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_lod_grad_device(self, ctx, entries, format, sampler, grids, stream=None):
+        """astcenc_amd_sample_lod_grad_device: the gradients of sample_lod_tensors_device with respect to the coordinates and the
+        levels of detail, for upstream gradients of `format`'s type and layout.  sampler as there.  grids: LodGradGrid, or
+        (first_entry, level_count, z, coords, lod, grad_out, grad_coords[, grad_lod[, lod_bias]]) tuples (see lod_grad_grid)."""
+        arr, n, s = self._set_args(entries, stream)
+        if sampler is not None and not isinstance(sampler, LodSampler):
+            sampler = LodSampler(*sampler)
+        grids = [g if isinstance(g, LodGradGrid) else lod_grad_grid(*g, layout=format.layout, type=format.type) for g in grids]
+        garr = (LodGradGrid * len(grids))(*grids) if grids else None
+        return self.lib.astcenc_amd_sample_lod_grad_device(ctx, arr, n, C.byref(format) if format is not None else None,
+                                                           C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_lod(self, ctx, entries, format, sampler, first_entry, level_count, z, coords, lod=None, lod_bias=0.0):
+        """The lod call as a differentiable torch operation: samples slice `z` of the chain entries[first_entry : first_entry +
+        level_count] at `coords` (float32 [H, W, 2]) and `lod` (float32 [H, W] or None) into a new tensor of `format` -- [C, H, W]
+        or [H, W, C] -- on torch's current stream; its backward is sample_lod_grad_device and returns gradients for `coords` and
+        `lod` only (the texels are compressed and fixed).  AstcError when either call fails."""
+        entries = [e if isinstance(e, ImageSetEntry) else image_set_entry(*e) for e in entries]
+        if not isinstance(sampler, LodSampler):
+            sampler = LodSampler(*sampler)
+        return _sample_lod_function().apply(coords, lod, self, ctx, entries, format, sampler, first_entry, level_count, z, lod_bias)
 
     def sample_cube_tensors_device(self, ctx, entries, format, sampler, grids, stream=None):
         """astcenc_amd_sample_cube_tensors_device: cube maps (one level or a mip chain) among the compressed images `entries`
@@ -1352,6 +1409,49 @@ class Library:
             return out
         finally:
             self.context_free(ctx)
+
+
+_SAMPLE_LOD_FUNCTION = None
+
+
+def _sample_lod_function():
+    """The torch.autograd.Function behind Library.sample_lod, made on first use: torch is imported lazily in this module."""
+    global _SAMPLE_LOD_FUNCTION
+    if _SAMPLE_LOD_FUNCTION is not None:
+        return _SAMPLE_LOD_FUNCTION
+    import torch
+    dtypes = {TENSOR_F32: torch.float32, TENSOR_F16: torch.float16, TENSOR_BF16: torch.bfloat16}
+
+    class SampleLod(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coords, lod, lib, ctx, entries, format, sampler, first_entry, level_count, z, lod_bias):
+            coords = coords.detach().contiguous()
+            lod = lod.detach().contiguous() if lod is not None else None
+            h, w = coords.shape[0], coords.shape[1]
+            shape = (format.channels, h, w) if format.layout == TENSOR_PLANAR else (h, w, format.channels)
+            out = torch.empty(shape, dtype=dtypes[format.type], device=coords.device)
+            err = lib.sample_lod_tensors_device(ctx, entries, format, sampler, [(first_entry, level_count, z, coords, lod, out, lod_bias)])
+            if err != SUCCESS:
+                raise AstcError(err, "astcenc_amd_sample_lod_tensors_device")
+            fctx.save_for_backward(coords, *([lod] if lod is not None else []))
+            fctx.call = (lib, ctx, entries, format, sampler, first_entry, level_count, z, lod_bias)
+            return out
+
+        @staticmethod
+        def backward(fctx, grad_out):
+            lib, ctx, entries, format, sampler, first_entry, level_count, z, lod_bias = fctx.call
+            saved = fctx.saved_tensors
+            coords, lod = saved[0], saved[1] if len(saved) > 1 else None
+            grad_out = grad_out.contiguous()
+            grad_coords = torch.empty_like(coords)
+            grad_lod = torch.empty_like(lod) if lod is not None and fctx.needs_input_grad[1] else None
+            err = lib.sample_lod_grad_device(ctx, entries, format, sampler, [(first_entry, level_count, z, coords, lod, grad_out, grad_coords, grad_lod, lod_bias)])
+            if err != SUCCESS:
+                raise AstcError(err, "astcenc_amd_sample_lod_grad_device")
+            return (grad_coords, grad_lod) + (None,) * 9
+
+    _SAMPLE_LOD_FUNCTION = SampleLod
+    return SampleLod
 
 
 def torch_stream(stream):

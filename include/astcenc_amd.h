@@ -450,7 +450,8 @@ struct astcenc_amd_lod_grid {
  *   the bytes are those astcenc_amd_sample_tensors_device writes for that entry at (u * W_l, v * H_l).
  *
  *   Out of scope: level selection from coordinate derivatives (a log2 cannot be given a bit-exact contract: the caller supplies
- *   lambda); anisotropy; gradients.
+ *   lambda); anisotropy.  Gradients with respect to the coordinates and the levels of detail are
+ *   astcenc_amd_sample_lod_grad_device's, below; gradients with respect to texels are out of scope (the texels are compressed).
  *   Cube maps sampled by direction, seamless across faces, are astcenc_amd_sample_cube_tensors_device's, below; sampling along
  *   z and contexts of 3D footprints are astcenc_amd_sample_volume_tensors_device's.
  *
@@ -472,6 +473,86 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_lod_tensors_device(
 	const struct astcenc_amd_tensor_format* format,
 	const struct astcenc_amd_lod_sampler* sampler,
 	const struct astcenc_amd_lod_grid* grids, unsigned int grid_count,
+	void* hip_stream);
+
+/* The gradients of astcenc_amd_sample_lod_tensors_device with respect to its inputs: the backward pass of a differentiable
+ * rasteriser or a neural-texture trainer over mip chains that stay compressed.  The texels are compressed and fixed, so the
+ * gradients that exist are those for the coordinates and the level of detail; bilinear sampling is piecewise linear in (u, v)
+ * and the blend is piecewise linear in lambda, so they have an exact form.  For every point of every grid the call takes an
+ * upstream gradient -- d loss / d out, in the forward call's format and layout -- and writes d loss / d (u, v) and, when wanted,
+ * d loss / d lod: the vector-Jacobian product.  With level_count = 1 it is the gradient of astcenc_amd_sample_tensors_device at
+ * (u W, v H). */
+struct astcenc_amd_lod_grad_grid {
+	unsigned int first_entry, level_count;  /* the forward grid's fields, with its meanings and limits ... */
+	unsigned int z;
+	unsigned int out_x, out_y;
+	const float* coords;
+	size_t coord_row_pitch;
+	const float* lod;
+	size_t lod_row_pitch;
+	float lod_bias;
+	const void* grad_out;                   /* device pointer: the upstream gradient, element (c = 0, j = 0, i = 0): a tensor of the format's
+	                                           type and layout, placed as the forward call places `out` */
+	size_t row_pitch, plane_pitch;          /* ... of grad_out, in ELEMENTS of the format's type; 0 = tightly packed */
+	float* grad_coords;                     /* device pointer: point (i, j) is the pair at grad_coords[j * grad_coord_row_pitch + 2 * i],
+	                                           d loss / du then d loss / dv */
+	size_t grad_coord_row_pitch;            /* in floats, even; 0 = 2 * out_x */
+	float* grad_lod;                        /* device pointer: point (i, j) has grad_lod[j * grad_lod_row_pitch + i]; NULL: not wanted */
+	size_t grad_lod_row_pitch;              /* in floats; 0 = out_x */
+};
+
+/* The gradients of grids[0 .. grid_count).  `format` and `sampler` are the forward call's; format->scale is used and
+ * format->bias is not (a shift has no derivative).  For point (i, j) of a grid, with (u, v), lod and lod_bias as in the forward
+ * call (reals are IEEE binary64 below unless said otherwise; "one operation" is one IEEE operation, round to nearest even, never
+ * fused; any sum starts as its first product -- nothing is added to a zero):
+ *
+ *   Validity, lambda', lambda_c, l0, g.  Those of astcenc_amd_sample_lod_tensors_device.  An invalid point writes +0.0 to all
+ *     three gradients.
+ *   Upstream.  a[c] = (double)grad_out[c] * (double)scale[c], one product, for c < format->channels; the element of grad_out is
+ *     where the forward call places out[c] of the point, and is widened exactly (F32, F16, BF16).  Upstream values are data: a NaN
+ *     or an infinity there is not an error.
+ *   Per level l that is part of the point (below), with x = (double)u * (double)W_l and y = (double)v * (double)H_l (exact):
+ *     s_l[c] is the forward call's level sample, binary32.  S_l = the sum over c < channels, in order, of a[c] * (double)s_l[c].
+ *     Under NEAREST, Dx_l = Dy_l = +0.0.
+ *     Under BILINEAR, ix0 = floor(x - 0.5) and iy0 = floor(y - 0.5), wx and wy the forward call's weights.  The difference along
+ *     x always uses both indices ix0 and ix0 + 1, each through the forward call's "Addressing" -- kx0 and kx1; a BORDER tap
+ *     outside is +0.0 -- even where the forward call's tap 1 has weight 0; along y likewise with ky0 and ky1.
+ *       d(ky) = v(kx1, ky)[c] - v(kx0, ky)[c] (one subtraction of the widened texels) for every forward y tap, in tap order, taps
+ *         of weight zero left out as in the forward call: dsdx[c] = wy0 * d(ky0) [+ wy1 * d(ky1)].
+ *       e(kx) = v(kx, ky1)[c] - v(kx, ky0)[c] over the forward x taps: dsdy[c] = wx0 * e(kx0) [+ wx1 * e(kx1)].
+ *       Dx_l = (the sum over c < channels, in order, of a[c] * dsdx[c]) * (double)W_l, and Dy_l likewise with dsdy and H_l.
+ *     A texel that is in none of these sums may or may not be read; a NaN there does not reach a result.
+ *   grad_coords.  One level (g = 0, or MIP_NEAREST): (float)Dx_l0 and (float)Dy_l0.  Two levels (g != 0):
+ *     (float)((1.0 - g) * Dx_l0 + g * Dx_l1) -- two products, one sum, one rounding to binary32 -- and likewise for v.
+ *   grad_lod.  The derivative is not zero only under MIP_LINEAR where 0 <= lambda' < level_count - 1, that is where lambda' is not
+ *     clamped: there it is (float)(S_(l0+1) - S_l0), one subtraction and one rounding -- at an integer lambda' the right
+ *     derivative.  This case samples level l0 + 1 for S alone even when g = 0.  Everywhere else -- MIP_NEAREST, a clamped lambda',
+ *     a chain of one level -- grad_lod is +0.0.  When grad_lod is NULL a level of weight zero is not read.
+ *   Storage.  A gradient that is a NaN is stored as the canonical quiet NaN 0x7FC00000.
+ *   Placement and pitches.  grad_coords as `coords`, grad_lod as `lod`.  No other element is written.
+ *
+ *   Consequences: under CLAMP a point more than half a texel outside the image has a zero gradient along that axis, because
+ *   both taps clamp to one texel.  The same formula is the derivative under REPEAT, MIRROR and BORDER, because addressing acts
+ *   on tap indices.  At a texel centre (f = 0) the gradient is the right-hand difference.  Away from cell boundaries and integer
+ *   lambda the gradients agree with central differences of the forward call to within its own rounding.
+ *
+ *   Out of scope: gradients with respect to texels; second derivatives; the cube and volume samplers.
+ *
+ *   - Everything astcenc_amd_sample_lod_tensors_device checks is checked here with its error codes, grad_out in the place of
+ *     `out`; the log callback names the index: "grid i of n".
+ *   - ASTCENC_ERR_BAD_CONTEXT: a null grad_out or grad_coords.  ASTCENC_ERR_BAD_PARAM: a grad_coords not aligned to 8 bytes; a
+ *     grad_out not aligned to its element; a grad_lod not aligned to 4 bytes; a gradient pitch below the tight one, or an odd
+ *     grad_coord_row_pitch; a grad_out, grad_coords or grad_lod that is not on the device of entry 0's blocks.  A null grad_lod is
+ *     legal.
+ *   - Everything is checked before anything is launched; a failure writes nothing.  An output that overlaps an input is the
+ *     caller's error and is not detected.
+ *   - A work item is the forward call's tile of 64 points; a tile runs one pass per distinct level its points need. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_lod_grad_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_lod_sampler* sampler,
+	const struct astcenc_amd_lod_grad_grid* grids, unsigned int grid_count,
 	void* hip_stream);
 
 /* Compressed cube maps sampled by direction at a level of detail per point straight into tensors: the environment lookup of a
