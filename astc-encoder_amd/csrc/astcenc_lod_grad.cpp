@@ -20,8 +20,9 @@ astcenc_error astcenc_amd_sample_lod_grad_device(astcenc_context* ctx, const ast
 	if (grid_count == 0) return ASTCENC_SUCCESS;
 	if (!ctx || !grids || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
 	DecodeTensorFormat fmt;
+	DecodeLodSampler smp;
 	std::vector<DecompressDeviceJob> jobs;
-	astcenc_error status = check_lod_call(fn, ctx, entries, entry_count, format, sampler, fmt, jobs);
+	astcenc_error status = check_lod_call(fn, ctx, entries, entry_count, format, sampler, false, fmt, smp, jobs);
 	if (status != ASTCENC_SUCCESS) return status;
 
 	std::vector<DecodeLodGradLaunch> launches(grid_count);
@@ -48,9 +49,6 @@ astcenc_error astcenc_amd_sample_lod_grad_device(astcenc_context* ctx, const ast
 		if (status != ASTCENC_SUCCESS) return status;
 	}
 
-	DecodeLodSampler smp;
-	smp.filter = (uint32_t)sampler->filter; smp.address_x = (uint32_t)sampler->address_x; smp.address_y = (uint32_t)sampler->address_y;
-	smp.mip_filter = (uint32_t)sampler->mip_filter;
 	DecompressLodGradJob job;
 	memset(&job, 0, sizeof(job));
 	job.format = &fmt;

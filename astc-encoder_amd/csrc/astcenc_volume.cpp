@@ -20,72 +20,34 @@ astcenc_error astcenc_amd_sample_volume_tensors_device(astcenc_context* ctx, con
 	const char* fn = "astcenc_amd_sample_volume_tensors_device";
 	if (grid_count == 0) return ASTCENC_SUCCESS;
 	if (!ctx || !grids || (!entries && entry_count != 0)) return ASTCENC_ERR_BAD_PARAM;
-	astcenc_error status = check_tensor_format(fn, format);
-	if (status != ASTCENC_SUCCESS) return status;
-	if (!sampler)
-	{
-		backend_log("%s: sampler is null", fn);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_volume_address_z(fn, (int)sampler->address_z);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_mip_level_filter(fn, (int)sampler->mip_filter);
-	if (status != ASTCENC_SUCCESS) return status;
-	// (every footprint is sampled here: no check_sample_footprint)
 	DecodeTensorFormat fmt;
-	status = check_tensor_factors(fn, format, fmt);
-	if (status != ASTCENC_SUCCESS) return status;
-
+	DecodeLodSampler smp;
 	std::vector<DecompressDeviceJob> jobs;
-	status = check_volume_entries(fn, ctx, entries, entry_count, jobs);
+	// (every footprint is sampled here)
+	astcenc_error status = check_lod_call(fn, ctx, entries, entry_count, format, sampler, true, fmt, smp, jobs);
 	if (status != ASTCENC_SUCCESS) return status;
 
-	std::vector<DecodeVolumeLaunch> launches(grid_count);
+	// (a volume has no layer to pick: the launches' stay 0)
+	std::vector<DecodeLodLaunch> launches(grid_count);
 	unsigned long long tiles = 0;
 	for (unsigned int i = 0; i < grid_count; i++)
 	{
 		const astcenc_amd_volume_grid& g = grids[i];
-		status = check_lod_chain(fn, i, grid_count, g.first_entry, g.level_count, entry_count);
-		if (status != ASTCENC_SUCCESS) return status;
-		for (unsigned int l = 0; l < g.level_count; l++)
-		{
-			const astcenc_amd_image_set_entry& en = entries[g.first_entry + l];
-			// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
-			if (en.dim_x > 65536 || en.dim_y > 65536 || en.dim_z > 65536)
+		SampleGridShape points = { g.out_x, g.out_y, g.coords, g.coord_row_pitch };
+		points.per_point = 3;
+		status = check_lod_grid(fn, i, grid_count, entries, entry_count, format, g, points, g.out, "out",
+			[&](const astcenc_amd_image_set_entry& en, unsigned int entry, unsigned int l)
 			{
-				backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u x %u texels: a level is at most 65536 along x, y and z", fn, i, grid_count, g.first_entry + l,
-				            l, en.dim_x, en.dim_y, en.dim_z);
+				// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
+				if (en.dim_x <= 65536 && en.dim_y <= 65536 && en.dim_z <= 65536) return ASTCENC_SUCCESS;
+				backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u x %u texels: a level is at most 65536 along x, y and z", fn, i, grid_count, entry, l, en.dim_x,
+				            en.dim_y, en.dim_z);
 				return ASTCENC_ERR_BAD_PARAM;
-			}
-		}
-		status = check_lod_pitch(fn, i, grid_count, g.lod_bias, g.lod_row_pitch, g.out_x);
+			}, launches[i], tiles);
 		if (status != ASTCENC_SUCCESS) return status;
-		CubeGridShape shape = { g.out_x, g.out_y, g.coords, g.coord_row_pitch, g.out, g.row_pitch, g.plane_pitch };
-		status = check_triple_grid(fn, i, grid_count, format, shape, "coords", "coord_row_pitch");
-		if (status != ASTCENC_SUCCESS) return status;
-		size_t lod_row_pitch = g.lod_row_pitch;
-		status = check_lod_buffer(fn, i, grid_count, g.lod, lod_row_pitch, g.out_x, g.out_y);
-		if (status != ASTCENC_SUCCESS) return status;
-		DecodeVolumeLaunch& l = launches[i];
-		l.first_entry = g.first_entry; l.level_count = g.level_count;
-		l.out_x = g.out_x; l.out_y = g.out_y;
-		l.d_coords = g.coords;
-		l.coord_row_pitch = shape.dir_row_pitch;
-		l.d_lod = g.lod;
-		l.lod_row_pitch = lod_row_pitch;
-		l.lod_bias = g.lod_bias;
-		l.d_out = g.out;
-		l.row_pitch = shape.row_pitch; l.plane_pitch = shape.plane_pitch;
-		if (!add_sample_tiles(fn, i, grid_count, g.out_x, g.out_y, tiles)) return ASTCENC_ERR_BAD_PARAM;
 	}
 
-	DecodeVolumeSampler smp;
-	smp.filter = (uint32_t)sampler->filter;
-	smp.address_x = (uint32_t)sampler->address_x; smp.address_y = (uint32_t)sampler->address_y; smp.address_z = (uint32_t)sampler->address_z;
-	smp.mip_filter = (uint32_t)sampler->mip_filter;
-	DecompressVolumeJob job;
+	DecompressLodJob job;
 	memset(&job, 0, sizeof(job));
 	job.format = &fmt;
 	job.sampler = &smp;

@@ -255,8 +255,8 @@ struct DecompressSampleJob {
 	void*    stream;
 };
 int backend_decompress_sample(Backend* b, const DecompressSampleJob& job);
-/* astcenc_amd_sample_lod_tensors_device: the same with the call's level-of-detail sampler and the grids as DecodeLodLaunch; a grid
- * uses the entries of all its levels. */
+/* astcenc_amd_sample_lod_tensors_device, astcenc_amd_sample_cube_tensors_device and astcenc_amd_sample_volume_tensors_device: the
+ * same with the call's level-of-detail sampler and the grids as DecodeLodLaunch; a grid uses the entries of all its levels. */
 struct DecodeLodSampler;
 struct DecodeLodLaunch;
 struct DecompressLodJob {
@@ -269,6 +269,8 @@ struct DecompressLodJob {
 	void*    stream;
 };
 int backend_decompress_lod(Backend* b, const DecompressLodJob& job);
+int backend_decompress_cube(Backend* b, const DecompressLodJob& job);
+int backend_decompress_volume(Backend* b, const DecompressLodJob& job);
 /* astcenc_amd_sample_lod_grad_device: the same with the grids as DecodeLodGradLaunch. */
 struct DecodeLodGradLaunch;
 struct DecompressLodGradJob {
@@ -281,32 +283,6 @@ struct DecompressLodGradJob {
 	void*    stream;
 };
 int backend_decompress_lod_grad(Backend* b, const DecompressLodGradJob& job);
-/* astcenc_amd_sample_cube_tensors_device: the same with the cube sampler and the grids as DecodeCubeLaunch. */
-struct DecodeCubeSampler;
-struct DecodeCubeLaunch;
-struct DecompressCubeJob {
-	const DecompressDeviceJob* entries;
-	uint32_t entry_count;
-	const DecodeTensorFormat* format;
-	const DecodeCubeSampler* sampler;
-	const DecodeCubeLaunch* grids;
-	uint32_t grid_count;
-	void*    stream;
-};
-int backend_decompress_cube(Backend* b, const DecompressCubeJob& job);
-/* astcenc_amd_sample_volume_tensors_device: the same with the volume sampler and the grids as DecodeVolumeLaunch. */
-struct DecodeVolumeSampler;
-struct DecodeVolumeLaunch;
-struct DecompressVolumeJob {
-	const DecompressDeviceJob* entries;
-	uint32_t entry_count;
-	const DecodeTensorFormat* format;
-	const DecodeVolumeSampler* sampler;
-	const DecodeVolumeLaunch* grids;
-	uint32_t grid_count;
-	void*    stream;
-};
-int backend_decompress_volume(Backend* b, const DecompressVolumeJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -526,20 +502,23 @@ size_t astc_decode_sample_bytes(uint32_t count);
 uint32_t astc_decode_sample_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeSampler& sampler,
                                   const DecodeSampleLaunch* grids, uint32_t count);
 int astc_decode_sample_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
-/* Mip chains sampled at a level of detail per point (astcenc_amd_sample_lod_tensors_device; decode_lod.h, kernel_decode_lod.hip):
- * the call's format and sampler and one DecodeLodLaunch per grid, checked by the entry point -- as above, and: 1 .. 32 levels, all
- * of them entries of the call no larger than 65536 along x and y that hold slice z, lod (when given) aligned to a float, lod_bias
- * finite.  A work item is a tile of 64 points of a grid (astc_decode_sample_tiles of them); the table -- a record per grid, then a
- * record per level of every grid -- and the launch as above. */
+/* Mip chains sampled at a level of detail per point: the lod call (astcenc_amd_sample_lod_tensors_device; decode_lod.h,
+ * kernel_decode_lod.hip), the cube call and the volume call below share the sampler and the launch record -- the call's format
+ * and sampler and one DecodeLodLaunch per grid, checked by the entry point -- as above, and: 1 .. 32 levels, all of them entries of
+ * the call no larger than 65536 along x and y that hold slice `z`, lod (when given) aligned to a float, lod_bias finite.  A
+ * work item is a tile of 64 points of a grid (astc_decode_sample_tiles of them); the table -- a record per grid, then a record per
+ * level of every grid, written by decode_lod.h's decode_lod_table_build for all of them -- and the launch as above. */
 struct DecodeLodSampler {
 	uint32_t filter, address_x, address_y;    // astcenc_amd_sample_filter / _address
 	uint32_t mip_filter;                      // astcenc_amd_mip_level_filter
+	uint32_t address_z;                       // the volume call's; CLAMP (0) where the call has none, as are x and y for cubes
 };
 struct DecodeLodLaunch {
 	uint32_t first_entry, level_count;    // level l is entry first_entry + l
-	uint32_t z;                           // the slice, in every level
+	uint32_t z;                           // the call's layer selector, in every level -- lod: the slice; cube: the cube, layers 6 z .. 6 z + 5; volume: 0, unused
 	uint32_t out_x, out_y;                // points per row, rows of points
-	const float* d_coords;                // point (i, j): the pair at d_coords[j * coord_row_pitch + 2 i], u then v
+	const float* d_coords;                // point (i, j): lod: the pair at d_coords[j * coord_row_pitch + 2 i], u then v; cube: the triple at
+	                                      // [j * coord_row_pitch + 3 i], dx, dy, dz; volume: the triple there, u, v, w
 	size_t   coord_row_pitch;             // floats
 	const float* d_lod;                   // point (i, j): d_lod[j * lod_row_pitch + i]; null: 0 everywhere
 	size_t   lod_row_pitch;               // floats
@@ -562,57 +541,29 @@ struct DecodeLodGradLaunch {
 	float*   d_grad_lod;                  // point (i, j): d_grad_lod[j * grad_lod_row_pitch + i]; null: not wanted
 	size_t   grad_lod_row_pitch;          // floats
 };
+/* (the forward launch of either, for what serves both: the table writer and the backend's path) */
+inline const DecodeLodLaunch& decode_lod_launch_of(const DecodeLodLaunch& g) { return g; }
+inline const DecodeLodLaunch& decode_lod_launch_of(const DecodeLodGradLaunch& g) { return g.lod; }
 size_t astc_decode_lod_grad_bytes(const DecodeLodGradLaunch* grids, uint32_t count);
 uint32_t astc_decode_lod_grad_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
                                     const DecodeLodGradLaunch* grids, uint32_t count);
 int astc_decode_lod_grad_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* Cube maps sampled by direction at a level of detail per point (astcenc_amd_sample_cube_tensors_device; decode_cube.h,
- * kernel_decode_cube.hip): the call's format and sampler and one DecodeCubeLaunch per grid, checked by the entry point -- as the
- * lod call's, and: every level square, no larger than 65536, with layers 6 cube .. 6 cube + 5; the directions aligned to a float,
+ * kernel_decode_cube.hip): the lod call's sampler, without address modes, and launch, checked by the entry point -- as the lod
+ * call's, and: every level square, no larger than 65536, with layers 6 z .. 6 z + 5 (z: the cube); the directions aligned to a float,
  * their pitch at least 3 out_x.  Work items, table and launch as the lod call's. */
-struct DecodeCubeSampler {
-	uint32_t filter;                      // astcenc_amd_sample_filter
-	uint32_t mip_filter;                  // astcenc_amd_mip_level_filter
-};
-struct DecodeCubeLaunch {
-	uint32_t first_entry, level_count;    // level l is entry first_entry + l
-	uint32_t cube;                        // layers 6 cube .. 6 cube + 5 of every level
-	uint32_t out_x, out_y;                // points per row, rows of points
-	const float* d_dirs;                  // point (i, j): d_dirs[j * dir_row_pitch + 3 i], dx, dy, dz
-	size_t   dir_row_pitch;               // floats
-	const float* d_lod;                   // point (i, j): d_lod[j * lod_row_pitch + i]; null: 0 everywhere
-	size_t   lod_row_pitch;               // floats
-	float    lod_bias;
-	void*    d_out;                       // element (c = 0, j = 0, i = 0)
-	size_t   row_pitch, plane_pitch;
-};
-size_t astc_decode_cube_bytes(const DecodeCubeLaunch* grids, uint32_t count);
-uint32_t astc_decode_cube_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeCubeSampler& sampler,
-                                const DecodeCubeLaunch* grids, uint32_t count);
+size_t astc_decode_cube_bytes(const DecodeLodLaunch* grids, uint32_t count);
+uint32_t astc_decode_cube_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                const DecodeLodLaunch* grids, uint32_t count);
 int astc_decode_cube_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* Volumes sampled at (u, v, w) at a level of detail per point (astcenc_amd_sample_volume_tensors_device; decode_volume.h,
- * kernel_decode_volume.hip): the call's format and sampler and one DecodeVolumeLaunch per grid, checked by the entry point -- as
- * the lod call's without a slice, and: any footprint, 2D or 3D; every level no larger than 65536 along x, y and z and of fewer
- * than 2^32 - 1 blocks, layers of block_z slices counted; the triples aligned to a float, their pitch at least 3 out_x.  Work
- * items, table and launch as the lod call's. */
-struct DecodeVolumeSampler {
-	uint32_t filter, address_x, address_y, address_z;    // astcenc_amd_sample_filter / _address
-	uint32_t mip_filter;                                 // astcenc_amd_mip_level_filter
-};
-struct DecodeVolumeLaunch {
-	uint32_t first_entry, level_count;    // level l is entry first_entry + l
-	uint32_t out_x, out_y;                // points per row, rows of points
-	const float* d_coords;                // point (i, j): d_coords[j * coord_row_pitch + 3 i], u, v, w
-	size_t   coord_row_pitch;             // floats
-	const float* d_lod;                   // point (i, j): d_lod[j * lod_row_pitch + i]; null: 0 everywhere
-	size_t   lod_row_pitch;               // floats
-	float    lod_bias;
-	void*    d_out;                       // element (c = 0, j = 0, i = 0)
-	size_t   row_pitch, plane_pitch;
-};
-size_t astc_decode_volume_bytes(const DecodeVolumeLaunch* grids, uint32_t count);
-uint32_t astc_decode_volume_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeVolumeSampler& sampler,
-                                  const DecodeVolumeLaunch* grids, uint32_t count);
+ * kernel_decode_volume.hip): the lod call's sampler, with address_z, and launch, checked by the entry point -- as the lod call's
+ * without a slice, and: any footprint, 2D or 3D; every level no larger than 65536 along x, y and z and of fewer than 2^32 - 1
+ * blocks, layers of block_z slices counted; the triples aligned to a float, their pitch at least 3 out_x.  Work items, table and
+ * launch as the lod call's. */
+size_t astc_decode_volume_bytes(const DecodeLodLaunch* grids, uint32_t count);
+uint32_t astc_decode_volume_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                  const DecodeLodLaunch* grids, uint32_t count);
 int astc_decode_volume_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */

@@ -1689,84 +1689,60 @@ int backend_decompress_sample(Backend* b, const DecompressSampleJob& job)
 		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_sample_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 2u);
 }
 
-/* (a grid uses the entries of all its levels; its buffers are the output, the coordinates and, unless null, the levels of detail) */
+/* The level-of-detail samplers (the lod call, its gradient, the cube call, the volume call), `job` one of their jobs: a grid uses
+ * the entries of all its levels; its buffers are the output (the gradient's grad_out), the points and the levels of detail -- the
+ * output stands in for a null lod -- and the `extras` more that extra(grid, k) names.  bytes, build and launch: the call's table
+ * and kernel (backend.h). */
+template <class Job, class Grid>
+static int decompress_lod_grids(Backend* b, const Job& job, const char* what, size_t (*bytes)(const Grid*, uint32_t),
+                                uint32_t (*build)(void*, const DecodeLaunch*, uint32_t, const DecodeTensorFormat&, const DecodeLodSampler&, const Grid*, uint32_t),
+                                int (*launch)(const void*, uint32_t, uint32_t, uint32_t, void*), uint32_t extras = 0, const void* (*extra)(const Grid&, uint32_t) = nullptr)
+{
+	std::vector<uint8_t> used(job.entry_count, 0);
+	for (uint32_t i = 0; i < job.grid_count; i++)
+	{
+		const DecodeLodLaunch& g = decode_lod_launch_of(job.grids[i]);
+		for (uint32_t l = 0; l < g.level_count; l++) used[g.first_entry + l] = 1;
+	}
+	const uint32_t buffers = 3u + extras;
+	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, what,
+		[&](uint32_t i) -> const void*
+		{
+			const DecodeLodLaunch& g = decode_lod_launch_of(job.grids[i / buffers]);
+			const uint32_t k = i % buffers;
+			return k == 0u || (k == 2u && !g.d_lod) ? g.d_out : k == 1u ? g.d_coords : k == 2u ? g.d_lod : extra(job.grids[i / buffers], k - 3u);
+		},
+		[&](const DecodeLaunch* d, void* out) -> size_t
+		{
+			return out ? build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : bytes(job.grids, job.grid_count);
+		},
+		[&](const void* d_table, uint32_t tiles, void* stream) { return launch(d_table, tiles, job.format->type, job.format->layout, stream); }, buffers);
+}
+
 int backend_decompress_lod(Backend* b, const DecompressLodJob& job)
 {
-	std::vector<uint8_t> used(job.entry_count, 0);
-	for (uint32_t i = 0; i < job.grid_count; i++)
-		for (uint32_t l = 0; l < job.grids[i].level_count; l++) used[job.grids[i].first_entry + l] = 1;
-	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample lod tensors",
-		[&](uint32_t i)
-		{
-			const DecodeLodLaunch& g = job.grids[i / 3u];
-			return i % 3u == 0u || (i % 3u == 2u && !g.d_lod) ? static_cast<const void*>(g.d_out) : i % 3u == 1u ? static_cast<const void*>(g.d_coords) : static_cast<const void*>(g.d_lod);
-		},
-		[&](const DecodeLaunch* d, void* out) -> size_t
-		{
-			return out ? astc_decode_lod_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_lod_bytes(job.grids, job.grid_count);
-		},
-		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_lod_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
+	return decompress_lod_grids(b, job, "sample lod tensors", astc_decode_lod_bytes, astc_decode_lod_build, astc_decode_lod_launch);
 }
 
-/* (as backend_decompress_lod, with five buffers a grid: grad_out, the coordinates, the levels of detail, grad_coords and grad_lod;
- *  grad_out stands in for a null lod, grad_coords for a null grad_lod) */
+/* (the buffers that are written: grad_coords, and grad_lod, for which grad_coords stands in when it is null) */
+static const void* lod_grad_buffer(const DecodeLodGradLaunch& g, uint32_t k)
+{
+	return k == 0u || !g.d_grad_lod ? g.d_grad_coords : g.d_grad_lod;
+}
+
 int backend_decompress_lod_grad(Backend* b, const DecompressLodGradJob& job)
 {
-	std::vector<uint8_t> used(job.entry_count, 0);
-	for (uint32_t i = 0; i < job.grid_count; i++)
-		for (uint32_t l = 0; l < job.grids[i].lod.level_count; l++) used[job.grids[i].lod.first_entry + l] = 1;
-	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample lod grad",
-		[&](uint32_t i)
-		{
-			const DecodeLodGradLaunch& g = job.grids[i / 5u];
-			const void* const buffers[5] = { g.lod.d_out, g.lod.d_coords, g.lod.d_lod ? static_cast<const void*>(g.lod.d_lod) : g.lod.d_out, g.d_grad_coords,
-			                                 g.d_grad_lod ? g.d_grad_lod : g.d_grad_coords };
-			return buffers[i % 5u];
-		},
-		[&](const DecodeLaunch* d, void* out) -> size_t
-		{
-			return out ? astc_decode_lod_grad_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count)
-			           : astc_decode_lod_grad_bytes(job.grids, job.grid_count);
-		},
-		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_lod_grad_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 5u);
+	return decompress_lod_grids(b, job, "sample lod grad", astc_decode_lod_grad_bytes, astc_decode_lod_grad_build, astc_decode_lod_grad_launch, 2u, lod_grad_buffer);
 }
 
-/* (as backend_decompress_lod: a grid's buffers are the output, the directions and, unless null, the levels of detail) */
-int backend_decompress_cube(Backend* b, const DecompressCubeJob& job)
+int backend_decompress_cube(Backend* b, const DecompressLodJob& job)
 {
-	std::vector<uint8_t> used(job.entry_count, 0);
-	for (uint32_t i = 0; i < job.grid_count; i++)
-		for (uint32_t l = 0; l < job.grids[i].level_count; l++) used[job.grids[i].first_entry + l] = 1;
-	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample cube tensors",
-		[&](uint32_t i)
-		{
-			const DecodeCubeLaunch& g = job.grids[i / 3u];
-			return i % 3u == 0u || (i % 3u == 2u && !g.d_lod) ? static_cast<const void*>(g.d_out) : i % 3u == 1u ? static_cast<const void*>(g.d_dirs) : static_cast<const void*>(g.d_lod);
-		},
-		[&](const DecodeLaunch* d, void* out) -> size_t
-		{
-			return out ? astc_decode_cube_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_cube_bytes(job.grids, job.grid_count);
-		},
-		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_cube_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
+	return decompress_lod_grids(b, job, "sample cube tensors", astc_decode_cube_bytes, astc_decode_cube_build, astc_decode_cube_launch);
 }
 
-/* (as backend_decompress_lod: a grid's buffers are the output, the triples and, unless null, the levels of detail) */
-int backend_decompress_volume(Backend* b, const DecompressVolumeJob& job)
+int backend_decompress_volume(Backend* b, const DecompressLodJob& job)
 {
-	std::vector<uint8_t> used(job.entry_count, 0);
-	for (uint32_t i = 0; i < job.grid_count; i++)
-		for (uint32_t l = 0; l < job.grids[i].level_count; l++) used[job.grids[i].first_entry + l] = 1;
-	return decompress_windows_of(b, job.entries, job.entry_count, used, job.grid_count, job.stream, "sample volume tensors",
-		[&](uint32_t i)
-		{
-			const DecodeVolumeLaunch& g = job.grids[i / 3u];
-			return i % 3u == 0u || (i % 3u == 2u && !g.d_lod) ? static_cast<const void*>(g.d_out) : i % 3u == 1u ? static_cast<const void*>(g.d_coords) : static_cast<const void*>(g.d_lod);
-		},
-		[&](const DecodeLaunch* d, void* out) -> size_t
-		{
-			return out ? astc_decode_volume_build(out, d, job.entry_count, *job.format, *job.sampler, job.grids, job.grid_count) : astc_decode_volume_bytes(job.grids, job.grid_count);
-		},
-		[&](const void* d_table, uint32_t tiles, void* stream) { return astc_decode_volume_launch(d_table, tiles, job.format->type, job.format->layout, stream); }, 3u);
+	return decompress_lod_grids(b, job, "sample volume tensors", astc_decode_volume_bytes, astc_decode_volume_build, astc_decode_volume_launch);
 }
 
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial

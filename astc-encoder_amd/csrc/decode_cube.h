@@ -5,7 +5,8 @@
 // as the "Cube edges" rule of the mip filter names it (include/astcenc_amd.h has the definition, tests/sample_cube_model.py
 // spells it out in numpy).
 //
-// The work item, the level walk, the batches, the sums, the blend and the stores are decode_lod.h's (lod_walk_tile); this header
+// The work item, the level walk, the batches, the sums, the blend, the stores (lod_walk_tile) and the table writer
+// (decode_lod_table_build; the launch is the lod call's DecodeLodLaunch, its z the cube) are decode_lod.h's; this header
 // holds what differs: the record, the coordinate stage (validity, the face, sc / ma and tc / ma -- divided once per point: the
 // quotients do not depend on the level) and the taps of a level, whose layer is the tap's own: SamplePoint::blk counts blocks
 // from the stream's start, so one level pass decodes blocks of several faces and deduplicates them across faces.
@@ -40,60 +41,19 @@ struct DecodeCubeRecord {
 };
 static_assert(sizeof(DecodeCubeRecord) % 8 == 0, "records are read word by word and hold pointers");
 
-inline size_t decode_cube_levels_offset(uint32_t count)
-{
-	return decode_table_bytes<DecodeCubeRecord>(count);
-}
+inline size_t decode_cube_bytes(const DecodeLodLaunch* grids, uint32_t count) { return decode_lod_table_bytes<DecodeCubeRecord>(grids, count); }
 
-inline size_t decode_cube_bytes(const DecodeCubeLaunch* grids, uint32_t count)
+/* The cube call's table (decode_lod_table_build; 2D footprints): its own are the triples and the cube; no address modes. */
+inline uint32_t decode_cube_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                  const DecodeLodLaunch* grids, uint32_t count)
 {
-	size_t levels = 0;
-	for (uint32_t i = 0; i < count; i++) levels += grids[i].level_count;
-	return decode_cube_levels_offset(count) + levels * sizeof(DecodeLodLevel);
-}
-
-/* Writes the table of `count` grids over the images `images` (prepared, 2D footprints, `data` unused) and their streams;
- * returns the tiles of all grids (the caller has made sure they fit 32 bits). */
-inline uint32_t decode_cube_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeCubeSampler& sampler,
-                                  const DecodeCubeLaunch* grids, uint32_t count)
-{
-	uint8_t* t = static_cast<uint8_t*>(out);
-	uint32_t* first;
-	DecodeCubeRecord* rec = decode_table_begin<DecodeCubeRecord>(out, decode_cube_bytes(grids, count), count, first);
-	size_t level_at = decode_cube_levels_offset(count);
-	uint32_t tiles = 0;
-	for (uint32_t i = 0; i < count; i++)
+	return decode_lod_table_build<DecodeCubeRecord>(out, images, streams, format, sampler, grids, count, [](DecodeCubeRecord& r, const DecodeLodLaunch& g) -> DecodeCubeRecord&
 	{
-		const DecodeCubeLaunch& g = grids[i];
-		DecodeCubeRecord& r = rec[i];
-		r.dirs = g.d_dirs;
-		r.dir_row = g.dir_row_pitch;
-		r.lod = g.d_lod;
-		r.lod_row = g.lod_row_pitch;
-		r.out = g.d_out;
-		r.row = g.row_pitch;
-		r.levels = level_at;
-		r.level_count = g.level_count;
-		r.cube = g.cube;
-		r.out_x = g.out_x; r.out_y = g.out_y;
-		r.filter = sampler.filter; r.mip_filter = sampler.mip_filter;
-		r.tw_log2 = decode_sample_tw_log2(g.out_y);
-		r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
-		r.x_step = tensor_x_step(format);
-		r.lod_bias = g.lod_bias;
-		r.fmt = tensor_params(format, g.plane_pitch);
-		for (uint32_t l = 0; l < g.level_count; l++)
-		{
-			DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at);
-			lv.img = images[g.first_entry + l];
-			lv.img.data = nullptr;
-			lv.blocks = streams[g.first_entry + l];
-			level_at += sizeof(DecodeLodLevel);
-		}
-		first[i] = tiles;
-		tiles += (uint32_t)decode_sample_tiles(g.out_x, g.out_y);
-	}
-	return decode_table_finish(out, count, tiles);
+		r.dirs = g.d_coords;
+		r.dir_row = g.coord_row_pitch;
+		r.cube = g.z;
+		return r;
+	});
 }
 
 /* A point is valid when dx, dy and dz are finite, not all three are zero (of either sign) and lambda' is not a NaN. */

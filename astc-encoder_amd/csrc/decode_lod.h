@@ -12,7 +12,9 @@
 // rounding) and stores through TensorStore::put.  A level of weight zero is not among a lane's levels: none of its blocks is read.
 //
 // The level walk (lod_walk_tile) takes how a lane reads its point and forms its taps in a level as a parameter: decode_cube.h runs
-// it over directions and cube faces, decode_volume.h over triples and eight taps.
+// it over directions and cube faces, decode_volume.h over triples and eight taps.  The table writer (decode_lod_table_build) is
+// likewise one for the lod call, its gradient, the cube call and the volume call: it takes the record's type and a callable for the
+// few fields that are a call's own.
 //
 // Included by kernel_decode_lod.hip, decode_cube.h, decode_volume.h, decode_lod_grad.h and tests/harness/decode_lod_check.cpp only.
 //
@@ -52,67 +54,85 @@ struct DecodeLodLevel {
 };
 static_assert(sizeof(DecodeLodLevel) % 8 == 0, "records are read word by word and hold pointers");
 
+/* The table writer of every call of this family (the lod call below, decode_lod_grad.h, decode_cube.h, decode_volume.h), which
+ * differ in their records: Record is the call's, Grid its launch -- a DecodeLodLaunch, or the gradient's, which embeds one
+ * (decode_lod_launch_of, backend.h). */
+template <class Record = DecodeLodRecord>
 inline size_t decode_lod_levels_offset(uint32_t count)
 {
-	return decode_table_bytes<DecodeLodRecord>(count);
+	return decode_table_bytes<Record>(count);
 }
 
-inline size_t decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count)
+template <class Record, class Grid>
+inline size_t decode_lod_table_bytes(const Grid* grids, uint32_t count)
 {
 	size_t levels = 0;
-	for (uint32_t i = 0; i < count; i++) levels += grids[i].level_count;
-	return decode_lod_levels_offset(count) + levels * sizeof(DecodeLodLevel);
+	for (uint32_t i = 0; i < count; i++) levels += decode_lod_launch_of(grids[i]).level_count;
+	return decode_lod_levels_offset<Record>(count) + levels * sizeof(DecodeLodLevel);
 }
 
-/* The record of grid `g` and the records of its levels, which start `level_at` bytes into the table `t` (decode_lod_grad.h
- * fills the forward half of its records with this too). */
-inline void decode_lod_record(DecodeLodRecord& r, uint8_t* t, size_t level_at, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format,
-                              const DecodeLodSampler& sampler, const DecodeLodLaunch& g)
-{
-	r.coords = g.d_coords;
-	r.coord_row = g.coord_row_pitch;
-	r.lod = g.d_lod;
-	r.lod_row = g.lod_row_pitch;
-	r.out = g.d_out;
-	r.row = g.row_pitch;
-	r.levels = level_at;
-	r.level_count = g.level_count;
-	r.z = g.z;
-	r.out_x = g.out_x; r.out_y = g.out_y;
-	r.filter = sampler.filter; r.address_x = sampler.address_x; r.address_y = sampler.address_y; r.mip_filter = sampler.mip_filter;
-	r.tw_log2 = decode_sample_tw_log2(g.out_y);
-	r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
-	r.x_step = tensor_x_step(format);
-	r.lod_bias = g.lod_bias;
-	r.fmt = tensor_params(format, g.plane_pitch);
-	for (uint32_t l = 0; l < g.level_count; l++)
-	{
-		DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at + (size_t)l * sizeof(DecodeLodLevel));
-		lv.img = images[g.first_entry + l];
-		lv.img.data = nullptr;
-		lv.blocks = streams[g.first_entry + l];
-	}
-}
-
-/* Writes the table of `count` grids over the images `images` (prepared, 2D footprints, `data` unused) and their streams;
- * returns the tiles of all grids (the caller has made sure they fit 32 bits). */
-inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
-                                 const DecodeLodLaunch* grids, uint32_t count)
+/* Writes the table of `count` grids over the images `images` (prepared, `data` unused) and their streams: the frame, the level
+ * records, first[] and the tile count; returns the tiles of all grids (the caller has made sure they fit 32 bits).
+ * own(record, grid) fills what is the call's own -- the points and their pitch, the slice or the cube, the address modes -- and
+ * returns the part of the record that holds the fields every call has under one name, which are filled here. */
+template <class Record, class Grid, class Own>
+inline uint32_t decode_lod_table_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                       const Grid* grids, uint32_t count, Own own)
 {
 	uint8_t* t = static_cast<uint8_t*>(out);
 	uint32_t* first;
-	DecodeLodRecord* rec = decode_table_begin<DecodeLodRecord>(out, decode_lod_bytes(grids, count), count, first);
-	size_t level_at = decode_lod_levels_offset(count);
+	Record* rec = decode_table_begin<Record>(out, decode_lod_table_bytes<Record>(grids, count), count, first);
+	size_t level_at = decode_lod_levels_offset<Record>(count);
 	uint32_t tiles = 0;
 	for (uint32_t i = 0; i < count; i++)
 	{
-		const DecodeLodLaunch& g = grids[i];
-		decode_lod_record(rec[i], t, level_at, images, streams, format, sampler, g);
-		level_at += (size_t)g.level_count * sizeof(DecodeLodLevel);
+		const DecodeLodLaunch& g = decode_lod_launch_of(grids[i]);
+		auto& r = own(rec[i], grids[i]);
+		r.lod = g.d_lod;
+		r.lod_row = g.lod_row_pitch;
+		r.out = g.d_out;
+		r.row = g.row_pitch;
+		r.levels = level_at;
+		r.level_count = g.level_count;
+		r.out_x = g.out_x; r.out_y = g.out_y;
+		r.filter = sampler.filter; r.mip_filter = sampler.mip_filter;
+		r.tw_log2 = decode_sample_tw_log2(g.out_y);
+		r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
+		r.x_step = tensor_x_step(format);
+		r.lod_bias = g.lod_bias;
+		r.fmt = tensor_params(format, g.plane_pitch);
+		for (uint32_t l = 0; l < g.level_count; l++)
+		{
+			DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at);
+			lv.img = images[g.first_entry + l];
+			lv.img.data = nullptr;
+			lv.blocks = streams[g.first_entry + l];
+			level_at += sizeof(DecodeLodLevel);
+		}
 		first[i] = tiles;
 		tiles += (uint32_t)decode_sample_tiles(g.out_x, g.out_y);
 	}
 	return decode_table_finish(out, count, tiles);
+}
+
+/* What is the lod call's own in a record (its gradient's records begin with one): pairs, the slice, two address modes. */
+inline DecodeLodRecord& decode_lod_own(DecodeLodRecord& r, const DecodeLodSampler& sampler, const DecodeLodLaunch& g)
+{
+	r.coords = g.d_coords;
+	r.coord_row = g.coord_row_pitch;
+	r.z = g.z;
+	r.address_x = sampler.address_x; r.address_y = sampler.address_y;
+	return r;
+}
+
+inline size_t decode_lod_bytes(const DecodeLodLaunch* grids, uint32_t count) { return decode_lod_table_bytes<DecodeLodRecord>(grids, count); }
+
+/* The lod call's table: 2D footprints. */
+inline uint32_t decode_lod_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                 const DecodeLodLaunch* grids, uint32_t count)
+{
+	return decode_lod_table_build<DecodeLodRecord>(out, images, streams, format, sampler, grids, count,
+		[&](DecodeLodRecord& r, const DecodeLodLaunch& g) -> DecodeLodRecord& { return decode_lod_own(r, sampler, g); });
 }
 
 /* A point is valid when u and v are finite and no larger than 2^14 in magnitude and lambda' is not a NaN. */

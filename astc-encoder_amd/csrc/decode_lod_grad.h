@@ -31,41 +31,21 @@ struct DecodeLodGradRecord {
 };
 static_assert(sizeof(DecodeLodGradRecord) % 8 == 0, "records are read word by word and hold pointers");
 
-inline size_t decode_lod_grad_levels_offset(uint32_t count)
-{
-	return decode_table_bytes<DecodeLodGradRecord>(count);
-}
+inline size_t decode_lod_grad_levels_offset(uint32_t count) { return decode_lod_levels_offset<DecodeLodGradRecord>(count); }
+inline size_t decode_lod_grad_bytes(const DecodeLodGradLaunch* grids, uint32_t count) { return decode_lod_table_bytes<DecodeLodGradRecord>(grids, count); }
 
-inline size_t decode_lod_grad_bytes(const DecodeLodGradLaunch* grids, uint32_t count)
-{
-	size_t levels = 0;
-	for (uint32_t i = 0; i < count; i++) levels += grids[i].lod.level_count;
-	return decode_lod_grad_levels_offset(count) + levels * sizeof(DecodeLodLevel);
-}
-
-/* Writes the table of `count` grids, as decode_lod_build does; returns the tiles of all grids. */
+/* The gradient call's table (decode_lod_table_build): the forward call's record and the two buffers that are written. */
 inline uint32_t decode_lod_grad_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
                                       const DecodeLodGradLaunch* grids, uint32_t count)
 {
-	uint8_t* t = static_cast<uint8_t*>(out);
-	uint32_t* first;
-	DecodeLodGradRecord* rec = decode_table_begin<DecodeLodGradRecord>(out, decode_lod_grad_bytes(grids, count), count, first);
-	size_t level_at = decode_lod_grad_levels_offset(count);
-	uint32_t tiles = 0;
-	for (uint32_t i = 0; i < count; i++)
+	return decode_lod_table_build<DecodeLodGradRecord>(out, images, streams, format, sampler, grids, count, [&](DecodeLodGradRecord& r, const DecodeLodGradLaunch& g) -> DecodeLodRecord&
 	{
-		const DecodeLodGradLaunch& g = grids[i];
-		DecodeLodGradRecord& r = rec[i];
-		decode_lod_record(r.lod, t, level_at, images, streams, format, sampler, g.lod);
-		level_at += (size_t)g.lod.level_count * sizeof(DecodeLodLevel);
 		r.grad_coords = g.d_grad_coords;
 		r.grad_coord_row = g.grad_coord_row_pitch;
 		r.grad_lod = g.d_grad_lod;
 		r.grad_lod_row = g.grad_lod_row_pitch;
-		first[i] = tiles;
-		tiles += (uint32_t)decode_sample_tiles(g.lod.out_x, g.lod.out_y);
-	}
-	return decode_table_finish(out, count, tiles);
+		return decode_lod_own(r.lod, sampler, g.lod);
+	});
 }
 
 /* Element `at` (+ c planes, or + c) of grad_out for the format's channels, widened exactly to binary32; the other components

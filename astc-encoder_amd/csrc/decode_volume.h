@@ -4,7 +4,8 @@
 // (MIP_LINEAR), each level sampled with the nearest texel or the trilinear blend of eight under an address mode per axis
 // (include/astcenc_amd.h has the definition, tests/sample_volume_model.py spells it out in numpy).
 //
-// The work item, the level walk, the blend and the stores are decode_lod.h's (lod_walk_tile); this header holds what differs: the
+// The work item, the level walk, the blend, the stores (lod_walk_tile) and the table writer (decode_lod_table_build; the launch is
+// the lod call's DecodeLodLaunch, its z unused) are decode_lod.h's; this header holds what differs: the
 // record, the eight-tap point, its taps -- (block, tx | ty << 8 | tz << 16), the block counted through layers of block_z slices,
 // one division per axis tap -- the batch loop over eight slots, which hands block_z and tz to decode_batch_texel, and the sums
 // (x taps, then y taps, then z taps).  A level pass may list 64 * 8 = 512 distinct blocks, 16 full batches; with a 3D footprint
@@ -43,60 +44,19 @@ struct DecodeVolumeRecord {
 };
 static_assert(sizeof(DecodeVolumeRecord) % 8 == 0, "records are read word by word and hold pointers");
 
-inline size_t decode_volume_levels_offset(uint32_t count)
-{
-	return decode_table_bytes<DecodeVolumeRecord>(count);
-}
+inline size_t decode_volume_bytes(const DecodeLodLaunch* grids, uint32_t count) { return decode_lod_table_bytes<DecodeVolumeRecord>(grids, count); }
 
-inline size_t decode_volume_bytes(const DecodeVolumeLaunch* grids, uint32_t count)
+/* The volume call's table (decode_lod_table_build; any footprint): its own are the triples and three address modes. */
+inline uint32_t decode_volume_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                    const DecodeLodLaunch* grids, uint32_t count)
 {
-	size_t levels = 0;
-	for (uint32_t i = 0; i < count; i++) levels += grids[i].level_count;
-	return decode_volume_levels_offset(count) + levels * sizeof(DecodeLodLevel);
-}
-
-/* Writes the table of `count` grids over the images `images` (prepared, any footprint, `data` unused) and their streams; returns
- * the tiles of all grids (the caller has made sure they fit 32 bits). */
-inline uint32_t decode_volume_build(void* out, const DecodeImage* images, const uint8_t* const* streams, const DecodeTensorFormat& format, const DecodeVolumeSampler& sampler,
-                                    const DecodeVolumeLaunch* grids, uint32_t count)
-{
-	uint8_t* t = static_cast<uint8_t*>(out);
-	uint32_t* first;
-	DecodeVolumeRecord* rec = decode_table_begin<DecodeVolumeRecord>(out, decode_volume_bytes(grids, count), count, first);
-	size_t level_at = decode_volume_levels_offset(count);
-	uint32_t tiles = 0;
-	for (uint32_t i = 0; i < count; i++)
+	return decode_lod_table_build<DecodeVolumeRecord>(out, images, streams, format, sampler, grids, count, [&](DecodeVolumeRecord& r, const DecodeLodLaunch& g) -> DecodeVolumeRecord&
 	{
-		const DecodeVolumeLaunch& g = grids[i];
-		DecodeVolumeRecord& r = rec[i];
 		r.coords = g.d_coords;
 		r.coord_row = g.coord_row_pitch;
-		r.lod = g.d_lod;
-		r.lod_row = g.lod_row_pitch;
-		r.out = g.d_out;
-		r.row = g.row_pitch;
-		r.levels = level_at;
-		r.level_count = g.level_count;
-		r.out_x = g.out_x; r.out_y = g.out_y;
-		r.filter = sampler.filter; r.address_x = sampler.address_x; r.address_y = sampler.address_y; r.address_z = sampler.address_z;
-		r.mip_filter = sampler.mip_filter;
-		r.tw_log2 = decode_sample_tw_log2(g.out_y);
-		r.tiles_x = (g.out_x + (1u << r.tw_log2) - 1u) >> r.tw_log2;
-		r.x_step = tensor_x_step(format);
-		r.lod_bias = g.lod_bias;
-		r.fmt = tensor_params(format, g.plane_pitch);
-		for (uint32_t l = 0; l < g.level_count; l++)
-		{
-			DecodeLodLevel& lv = *reinterpret_cast<DecodeLodLevel*>(t + level_at);
-			lv.img = images[g.first_entry + l];
-			lv.img.data = nullptr;
-			lv.blocks = streams[g.first_entry + l];
-			level_at += sizeof(DecodeLodLevel);
-		}
-		first[i] = tiles;
-		tiles += (uint32_t)decode_sample_tiles(g.out_x, g.out_y);
-	}
-	return decode_table_finish(out, count, tiles);
+		r.address_x = sampler.address_x; r.address_y = sampler.address_y; r.address_z = sampler.address_z;
+		return r;
+	});
 }
 
 /* A point is valid when u, v and w are finite and no larger than 2^14 in magnitude and lambda' is not a NaN. */

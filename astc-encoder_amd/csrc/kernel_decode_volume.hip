@@ -40,10 +40,10 @@ astc_volume_sample(const ImageSetTable* __restrict__ set, uint32_t tile0)
 	(void)decode_volume_tile<kType, kLayout>(rec, levels, local, batch, tile);
 }
 
-size_t astc_decode_volume_bytes(const DecodeVolumeLaunch* grids, uint32_t count) { return decode_volume_bytes(grids, count); }
+size_t astc_decode_volume_bytes(const DecodeLodLaunch* grids, uint32_t count) { return decode_volume_bytes(grids, count); }
 
-uint32_t astc_decode_volume_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeVolumeSampler& sampler,
-                                const DecodeVolumeLaunch* grids, uint32_t count)
+uint32_t astc_decode_volume_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                  const DecodeLodLaunch* grids, uint32_t count)
 {
 	const DecodeEntries of(entries, entry_count);
 	return decode_volume_build(out, of.images.data(), of.streams.data(), format, sampler, grids, count);

@@ -1,9 +1,10 @@
 // SPDX-License-Identifier: Apache-2.0
 // What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_lod_grad.cpp,
 // astcenc_cube.cpp, astcenc_volume.cpp): the
-// checks of the sampler's filter and address modes, of the footprint, of the entries' block counts, of a grid's points and
-// coordinates (or directions), of a chain and of the levels of detail, with the sample and lod calls' error codes and log lines;
-// the lod call's checks as a whole (check_lod_call, check_lod_grid), which its gradient repeats, and those of the gradients' buffers.
+// checks of the sampler's filter and address modes, of the footprint, of the entries' block counts, of a grid's points and their
+// pairs or triples (check_sample_grid), of a chain and of the levels of detail, with the sample and lod calls' error codes and log
+// lines; the checks of a call of the lod family as a whole (check_lod_call, check_lod_grid), to which the cube and volume calls
+// bring their per-level check and the gradient those of its buffers.
 // `fn` names the entry point in the log.
 #pragma once
 #include "regions_internal.h"
@@ -57,13 +58,18 @@ inline astcenc_error check_sample_entries(const char* fn, astcenc_context* ctx, 
 }
 
 /* The points, the coordinates and the output of grid i of grid_count; the pitches come back resolved (plane_pitch 0 for the
- * interleaved layout). */
+ * interleaved layout).  A point has `per_point` floats: 2, the pairs of the sample and lod calls -- aligned to 8 bytes, an even
+ * pitch of at least 2 out_x; or 3, the cube call's directions and the volume call's coordinates -- aligned to a float, any pitch
+ * of at least 3 out_x.  `name` and `pitch_name` are the buffer's and its pitch's in the log. */
 struct SampleGridShape {
 	unsigned int out_x, out_y;
 	const float* coords;
 	size_t coord_row_pitch;
 	void* out;
 	size_t row_pitch, plane_pitch;
+	unsigned int per_point = 2;
+	const char* name = "coords";
+	const char* pitch_name = "coord_row_pitch";
 };
 
 inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, SampleGridShape& g,
@@ -74,22 +80,25 @@ inline astcenc_error check_sample_grid(const char* fn, unsigned int i, unsigned 
 		backend_log("%s: grid %u of %u: %u x %u points: either size is 1 to 65535", fn, i, grid_count, g.out_x, g.out_y);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
-	if ((g.coord_row_pitch & 1u) != 0 || (g.coord_row_pitch != 0 && g.coord_row_pitch < 2u * (size_t)g.out_x))
+	const bool pairs = g.per_point == 2;
+	const size_t tight = (size_t)g.per_point * g.out_x;
+	if ((pairs && (g.coord_row_pitch & 1u) != 0) || (g.coord_row_pitch != 0 && g.coord_row_pitch < tight))
 	{
-		backend_log("%s: grid %u of %u: coord_row_pitch %zu: even and at least %zu floats", fn, i, grid_count, g.coord_row_pitch, 2u * (size_t)g.out_x);
+		if (pairs) backend_log("%s: grid %u of %u: %s %zu: even and at least %zu floats", fn, i, grid_count, g.pitch_name, g.coord_row_pitch, tight);
+		else backend_log("%s: grid %u of %u: %s %zu: at least %zu floats", fn, i, grid_count, g.pitch_name, g.coord_row_pitch, tight);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	// (the coordinates' extent in bytes fits 64 bits too: reported with the output's products)
 	bool overflow = false;
-	const size_t coord_row_pitch = g.coord_row_pitch ? g.coord_row_pitch : 2u * (size_t)g.out_x;
+	const size_t coord_row_pitch = g.coord_row_pitch ? g.coord_row_pitch : tight;
 	(void)mul_safe(mul_safe(coord_row_pitch, g.out_y, overflow), sizeof(float), overflow);
 	TensorPitches pitches = { g.row_pitch, 0, g.plane_pitch };
-	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.coords ? "coords" : nullptr,
-	                                                 out_name);
+	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.coords ? g.name : nullptr, out_name);
 	if (status != ASTCENC_SUCCESS) return status;
-	if (reinterpret_cast<uintptr_t>(g.coords) % 8 != 0)
+	if (reinterpret_cast<uintptr_t>(g.coords) % (pairs ? 8 : 4) != 0)
 	{
-		backend_log("%s: grid %u of %u: coords %p is not aligned to a pair of floats (8 bytes)", fn, i, grid_count, static_cast<const void*>(g.coords));
+		if (pairs) backend_log("%s: grid %u of %u: %s %p is not aligned to a pair of floats (8 bytes)", fn, i, grid_count, g.name, static_cast<const void*>(g.coords));
+		else backend_log("%s: grid %u of %u: %s %p is not aligned to a float (4 bytes)", fn, i, grid_count, g.name, static_cast<const void*>(g.coords));
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	g.coord_row_pitch = coord_row_pitch;
@@ -168,151 +177,6 @@ inline bool add_sample_tiles(const char* fn, unsigned int i, unsigned int grid_c
 	return false;
 }
 
-/* What the lod call and its gradient check before their grids (astcenc_lod.cpp, astcenc_lod_grad.cpp): the format, the sampler,
- * the footprint and the entries; `fmt` and `jobs` come back filled. */
-inline astcenc_error check_lod_call(const char* fn, astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
-                                    const astcenc_amd_tensor_format* format, const astcenc_amd_lod_sampler* sampler, DecodeTensorFormat& fmt,
-                                    std::vector<DecompressDeviceJob>& jobs)
-{
-	astcenc_error status = check_tensor_format(fn, format);
-	if (status != ASTCENC_SUCCESS) return status;
-	if (!sampler)
-	{
-		backend_log("%s: sampler is null", fn);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	status = check_sample_modes(fn, (int)sampler->filter, (int)sampler->address_x, (int)sampler->address_y);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_mip_level_filter(fn, (int)sampler->mip_filter);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_sample_footprint(fn, ctx);
-	if (status != ASTCENC_SUCCESS) return status;
-	status = check_tensor_factors(fn, format, fmt);
-	if (status != ASTCENC_SUCCESS) return status;
-	return check_sample_entries(fn, ctx, entries, entry_count, jobs);
-}
-
-/* ... and of grid i, an astcenc_amd_lod_grid or an astcenc_amd_lod_grad_grid: the chain, the slice and the size of every level,
- * the levels of detail, the points, the coordinates and the tensor `out` (the forward call's output or the gradient call's
- * grad_out, named `out_name` in the log); the launch comes back filled and the grid's tiles are added to `tiles`. */
-template <class Grid>
-inline astcenc_error check_lod_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
-                                    const astcenc_amd_tensor_format* format, const Grid& g, void* out, const char* out_name, DecodeLodLaunch& l, unsigned long long& tiles)
-{
-	astcenc_error status = check_lod_chain(fn, i, grid_count, g.first_entry, g.level_count, entry_count);
-	if (status != ASTCENC_SUCCESS) return status;
-	for (unsigned int lv = 0; lv < g.level_count; lv++)
-	{
-		const astcenc_amd_image_set_entry& en = entries[g.first_entry + lv];
-		if (g.z >= en.dim_z)
-		{
-			backend_log("%s: grid %u of %u: slice %u is not inside the %u x %u x %u image of entry %u (level %u)", fn, i, grid_count, g.z, en.dim_x, en.dim_y,
-			            en.dim_z, g.first_entry + lv, lv);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-		// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
-		if (en.dim_x > 65536 || en.dim_y > 65536)
-		{
-			backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u texels: a level is at most 65536 along x and y", fn, i, grid_count, g.first_entry + lv, lv,
-			            en.dim_x, en.dim_y);
-			return ASTCENC_ERR_BAD_PARAM;
-		}
-	}
-	status = check_lod_pitch(fn, i, grid_count, g.lod_bias, g.lod_row_pitch, g.out_x);
-	if (status != ASTCENC_SUCCESS) return status;
-	SampleGridShape shape = { g.out_x, g.out_y, g.coords, g.coord_row_pitch, out, g.row_pitch, g.plane_pitch };
-	status = check_sample_grid(fn, i, grid_count, format, shape, out_name);
-	if (status != ASTCENC_SUCCESS) return status;
-	size_t lod_row_pitch = g.lod_row_pitch;
-	status = check_lod_buffer(fn, i, grid_count, g.lod, lod_row_pitch, g.out_x, g.out_y);
-	if (status != ASTCENC_SUCCESS) return status;
-	l.first_entry = g.first_entry; l.level_count = g.level_count;
-	l.z = g.z;
-	l.out_x = g.out_x; l.out_y = g.out_y;
-	l.d_coords = g.coords;
-	l.coord_row_pitch = shape.coord_row_pitch;
-	l.d_lod = g.lod;
-	l.lod_row_pitch = lod_row_pitch;
-	l.lod_bias = g.lod_bias;
-	l.d_out = out;
-	l.row_pitch = shape.row_pitch; l.plane_pitch = shape.plane_pitch;
-	return add_sample_tiles(fn, i, grid_count, g.out_x, g.out_y, tiles) ? ASTCENC_SUCCESS : ASTCENC_ERR_BAD_PARAM;
-}
-
-/* A buffer of the gradient call that is written, `name` with its pitch `pitch_name`: `per_point` floats a point (2: grad_coords,
- * aligned to 8 bytes, an even pitch; 1: grad_lod, aligned to 4 bytes); the pitch comes back resolved. */
-inline astcenc_error check_grad_buffer(const char* fn, unsigned int i, unsigned int grid_count, const char* name, const char* pitch_name, const float* buffer,
-                                       size_t& row_pitch, unsigned int per_point, unsigned int out_x, unsigned int out_y)
-{
-	const size_t tight = (size_t)per_point * out_x;
-	if ((per_point == 2 && (row_pitch & 1u) != 0) || (row_pitch != 0 && row_pitch < tight))
-	{
-		backend_log("%s: grid %u of %u: %s %zu: %sat least %zu floats", fn, i, grid_count, pitch_name, row_pitch, per_point == 2 ? "even and " : "", tight);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	const size_t resolved = row_pitch ? row_pitch : tight;
-	bool overflow = false;
-	(void)mul_safe(mul_safe(resolved, out_y, overflow), sizeof(float), overflow);
-	if (overflow)
-	{
-		backend_log("%s: grid %u of %u: %s %zu: the gradients do not fit 64 bits", fn, i, grid_count, pitch_name, row_pitch);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if (reinterpret_cast<uintptr_t>(buffer) % (4u * per_point) != 0)
-	{
-		backend_log("%s: grid %u of %u: %s %p is not aligned to %u bytes", fn, i, grid_count, name, static_cast<const void*>(buffer), 4u * per_point);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	row_pitch = resolved;
-	return ASTCENC_SUCCESS;
-}
-
-/* The points, the triples of floats (the cube call's directions, the volume call's coordinates) and the output of grid i of
- * grid_count: check_sample_grid with triples in the place of pairs -- aligned to a float, any pitch of at least 3 out_x.  `what`
- * and `what_pitch` name the buffer and its pitch in the log. */
-struct CubeGridShape {
-	unsigned int out_x, out_y;
-	const float* dirs;
-	size_t dir_row_pitch;
-	void* out;
-	size_t row_pitch, plane_pitch;
-};
-
-inline astcenc_error check_triple_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, CubeGridShape& g, const char* what,
-                                       const char* what_pitch)
-{
-	if (g.out_x == 0 || g.out_y == 0 || g.out_x > 65535 || g.out_y > 65535)
-	{
-		backend_log("%s: grid %u of %u: %u x %u points: either size is 1 to 65535", fn, i, grid_count, g.out_x, g.out_y);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	if (g.dir_row_pitch != 0 && g.dir_row_pitch < 3u * (size_t)g.out_x)
-	{
-		backend_log("%s: grid %u of %u: %s %zu: at least %zu floats", fn, i, grid_count, what_pitch, g.dir_row_pitch, 3u * (size_t)g.out_x);
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	bool overflow = false;
-	const size_t dir_row_pitch = g.dir_row_pitch ? g.dir_row_pitch : 3u * (size_t)g.out_x;
-	(void)mul_safe(mul_safe(dir_row_pitch, g.out_y, overflow), sizeof(float), overflow);
-	TensorPitches pitches = { g.row_pitch, 0, g.plane_pitch };
-	const astcenc_error status = check_output_tensor(fn, "grid", i, grid_count, format, g.out_x, g.out_y, 0, pitches, g.out, overflow, !g.dirs ? what : nullptr);
-	if (status != ASTCENC_SUCCESS) return status;
-	if (reinterpret_cast<uintptr_t>(g.dirs) % 4 != 0)
-	{
-		backend_log("%s: grid %u of %u: %s %p is not aligned to a float (4 bytes)", fn, i, grid_count, what, static_cast<const void*>(g.dirs));
-		return ASTCENC_ERR_BAD_PARAM;
-	}
-	g.dir_row_pitch = dir_row_pitch;
-	g.row_pitch = pitches.row;
-	g.plane_pitch = pitches.plane;
-	return ASTCENC_SUCCESS;
-}
-
-inline astcenc_error check_cube_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_tensor_format* format, CubeGridShape& g)
-{
-	return check_triple_grid(fn, i, grid_count, format, g, "dirs", "dir_row_pitch");
-}
-
 /* The volume call's third address mode (astcenc_volume.cpp), after check_sample_modes has seen the other two. */
 inline astcenc_error check_volume_address_z(const char* fn, int address_z)
 {
@@ -340,6 +204,141 @@ inline astcenc_error check_volume_entries(const char* fn, astcenc_context* ctx, 
 			return ASTCENC_ERR_BAD_PARAM;
 		}
 	}
+	return ASTCENC_SUCCESS;
+}
+
+/* The sampler of a call of the lod family as the backend takes it; an address mode the call's sampler does not have is CLAMP. */
+inline DecodeLodSampler lod_sampler_of(const astcenc_amd_lod_sampler& s)
+{
+	return { (uint32_t)s.filter, (uint32_t)s.address_x, (uint32_t)s.address_y, (uint32_t)s.mip_filter, ASTCENC_AMD_ADDRESS_CLAMP };
+}
+// (a cube has no address modes: its edges are its neighbours')
+inline DecodeLodSampler lod_sampler_of(const astcenc_amd_cube_sampler& s)
+{
+	return { (uint32_t)s.filter, ASTCENC_AMD_ADDRESS_CLAMP, ASTCENC_AMD_ADDRESS_CLAMP, (uint32_t)s.mip_filter, ASTCENC_AMD_ADDRESS_CLAMP };
+}
+inline DecodeLodSampler lod_sampler_of(const astcenc_amd_volume_sampler& s)
+{
+	return { (uint32_t)s.filter, (uint32_t)s.address_x, (uint32_t)s.address_y, (uint32_t)s.mip_filter, (uint32_t)s.address_z };
+}
+
+/* What the lod call, its gradient, the cube call and the volume call check before their grids: the format, the sampler (the modes
+ * it has: lod_sampler_of), the footprint -- 2D unless the call samples `any_footprint`, whose entries' blocks are counted in
+ * layers -- and the entries; `fmt`, `smp` and `jobs` come back filled. */
+template <class Sampler>
+inline astcenc_error check_lod_call(const char* fn, astcenc_context* ctx, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                    const astcenc_amd_tensor_format* format, const Sampler* sampler, bool any_footprint, DecodeTensorFormat& fmt, DecodeLodSampler& smp,
+                                    std::vector<DecompressDeviceJob>& jobs)
+{
+	astcenc_error status = check_tensor_format(fn, format);
+	if (status != ASTCENC_SUCCESS) return status;
+	if (!sampler)
+	{
+		backend_log("%s: sampler is null", fn);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	smp = lod_sampler_of(*sampler);
+	status = check_sample_modes(fn, (int)smp.filter, (int)smp.address_x, (int)smp.address_y);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = check_volume_address_z(fn, (int)smp.address_z);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = check_mip_level_filter(fn, (int)smp.mip_filter);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = any_footprint ? ASTCENC_SUCCESS : check_sample_footprint(fn, ctx);
+	if (status != ASTCENC_SUCCESS) return status;
+	status = check_tensor_factors(fn, format, fmt);
+	if (status != ASTCENC_SUCCESS) return status;
+	return any_footprint ? check_volume_entries(fn, ctx, entries, entry_count, jobs) : check_sample_entries(fn, ctx, entries, entry_count, jobs);
+}
+
+/* ... and of grid i, any of the calls' grids: the chain, every level by level_check(entry, its index, level) -- which logs what it
+ * rejects -- the levels of detail, the points, their coordinates as `points` has them (out_x .. coord_row_pitch, per_point and the
+ * names; the rest is filled here) and the tensor `out` (a forward call's output or the gradient call's grad_out, named
+ * `out_name` in the log); the launch comes back filled but for its z (the slice or the cube: the caller's) and the grid's tiles are added to `tiles`. */
+template <class Grid, class LevelCheck>
+inline astcenc_error check_lod_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                    const astcenc_amd_tensor_format* format, const Grid& g, SampleGridShape points, void* out, const char* out_name, LevelCheck level_check,
+                                    DecodeLodLaunch& l, unsigned long long& tiles)
+{
+	astcenc_error status = check_lod_chain(fn, i, grid_count, g.first_entry, g.level_count, entry_count);
+	if (status != ASTCENC_SUCCESS) return status;
+	for (unsigned int lv = 0; lv < g.level_count; lv++)
+	{
+		status = level_check(entries[g.first_entry + lv], g.first_entry + lv, lv);
+		if (status != ASTCENC_SUCCESS) return status;
+	}
+	status = check_lod_pitch(fn, i, grid_count, g.lod_bias, g.lod_row_pitch, g.out_x);
+	if (status != ASTCENC_SUCCESS) return status;
+	points.out = out; points.row_pitch = g.row_pitch; points.plane_pitch = g.plane_pitch;
+	status = check_sample_grid(fn, i, grid_count, format, points, out_name);
+	if (status != ASTCENC_SUCCESS) return status;
+	size_t lod_row_pitch = g.lod_row_pitch;
+	status = check_lod_buffer(fn, i, grid_count, g.lod, lod_row_pitch, g.out_x, g.out_y);
+	if (status != ASTCENC_SUCCESS) return status;
+	l.first_entry = g.first_entry; l.level_count = g.level_count;
+	l.out_x = g.out_x; l.out_y = g.out_y;
+	l.d_coords = points.coords;
+	l.coord_row_pitch = points.coord_row_pitch;
+	l.d_lod = g.lod;
+	l.lod_row_pitch = lod_row_pitch;
+	l.lod_bias = g.lod_bias;
+	l.d_out = out;
+	l.row_pitch = points.row_pitch; l.plane_pitch = points.plane_pitch;
+	return add_sample_tiles(fn, i, grid_count, g.out_x, g.out_y, tiles) ? ASTCENC_SUCCESS : ASTCENC_ERR_BAD_PARAM;
+}
+
+/* The grid of the lod call or of its gradient (an astcenc_amd_lod_grid or an astcenc_amd_lod_grad_grid): pairs, and every level
+ * holds the slice and is no larger than 65536 along x and y. */
+template <class Grid>
+inline astcenc_error check_lod_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                    const astcenc_amd_tensor_format* format, const Grid& g, void* out, const char* out_name, DecodeLodLaunch& l, unsigned long long& tiles)
+{
+	l.z = g.z;
+	return check_lod_grid(fn, i, grid_count, entries, entry_count, format, g, { g.out_x, g.out_y, g.coords, g.coord_row_pitch }, out, out_name,
+		[&](const astcenc_amd_image_set_entry& en, unsigned int entry, unsigned int lv)
+		{
+			if (g.z >= en.dim_z)
+			{
+				backend_log("%s: grid %u of %u: slice %u is not inside the %u x %u x %u image of entry %u (level %u)", fn, i, grid_count, g.z, en.dim_x, en.dim_y,
+				            en.dim_z, entry, lv);
+				return ASTCENC_ERR_BAD_PARAM;
+			}
+			// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
+			if (en.dim_x > 65536 || en.dim_y > 65536)
+			{
+				backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u texels: a level is at most 65536 along x and y", fn, i, grid_count, entry, lv, en.dim_x,
+				            en.dim_y);
+				return ASTCENC_ERR_BAD_PARAM;
+			}
+			return ASTCENC_SUCCESS;
+		}, l, tiles);
+}
+
+/* A buffer of the gradient call that is written, `name` with its pitch `pitch_name`: `per_point` floats a point (2: grad_coords,
+ * aligned to 8 bytes, an even pitch; 1: grad_lod, aligned to 4 bytes); the pitch comes back resolved. */
+inline astcenc_error check_grad_buffer(const char* fn, unsigned int i, unsigned int grid_count, const char* name, const char* pitch_name, const float* buffer,
+                                       size_t& row_pitch, unsigned int per_point, unsigned int out_x, unsigned int out_y)
+{
+	const size_t tight = (size_t)per_point * out_x;
+	if ((per_point == 2 && (row_pitch & 1u) != 0) || (row_pitch != 0 && row_pitch < tight))
+	{
+		backend_log("%s: grid %u of %u: %s %zu: %sat least %zu floats", fn, i, grid_count, pitch_name, row_pitch, per_point == 2 ? "even and " : "", tight);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	const size_t resolved = row_pitch ? row_pitch : tight;
+	bool overflow = false;
+	(void)mul_safe(mul_safe(resolved, out_y, overflow), sizeof(float), overflow);
+	if (overflow)
+	{
+		backend_log("%s: grid %u of %u: %s %zu: the gradients do not fit 64 bits", fn, i, grid_count, pitch_name, row_pitch);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	if (reinterpret_cast<uintptr_t>(buffer) % (4u * per_point) != 0)
+	{
+		backend_log("%s: grid %u of %u: %s %p is not aligned to %u bytes", fn, i, grid_count, name, static_cast<const void*>(buffer), 4u * per_point);
+		return ASTCENC_ERR_BAD_PARAM;
+	}
+	row_pitch = resolved;
 	return ASTCENC_SUCCESS;
 }
 

@@ -451,6 +451,35 @@ def lod_grad_grid(first_entry, level_count, z, coords, lod, grad_out, grad_coord
                        gcptr, grad_coord_row_pitch, glptr, grad_lod_row_pitch)
 
 
+def _triple_grid(first_entry, level_count, name, points, lod, out_view, lod_bias, layout, type):
+    """What cube_grid and volume_grid share: the fields out_x .. plane_pitch of their grids from `points`, a float32 torch tensor
+    [H, W, 3] named `name` in the errors -- adjacent triples, rows apart -- an output of the same H x W and a lod buffer; or from
+    the explicit tuples.  ValueError as the two say."""
+    _check_chain(level_count, lod_bias)
+    if isinstance(points, tuple):
+        pptr, out_x, out_y, point_row_pitch = points
+        optr, row_pitch, plane_pitch = out_view
+        lptr, lod_row_pitch = lod if lod is not None else (None, 0)
+        return out_x, out_y, pptr, point_row_pitch, lptr, lod_row_pitch, lod_bias, optr, row_pitch, plane_pitch
+    import torch
+    if points.dtype != torch.float32:
+        raise ValueError("%s is %s: float32 triples" % (name, points.dtype))
+    shape, st = tuple(points.shape), tuple(points.stride())
+    if points.dim() != 3 or shape[2] != 3:
+        raise ValueError("%s has shape %r: [H, W, 3]" % (name, shape))
+    if st[2] != 1 or (st[1] != 3 and shape[1] > 1) or st[0] < 0 or (st[0] == 0 and shape[0] > 1):
+        raise ValueError("the triples of %s must be adjacent floats, three floats apart, its rows apart (strides %r)" % (name, st))
+    point_row_pitch = st[0] if shape[0] > 1 else 0
+    if point_row_pitch != 0 and point_row_pitch < 3 * shape[1]:
+        raise ValueError("the rows of %s overlap (strides %r)" % (name, st))
+    # (the output's checks are scaled_region's: a window of 1 x 1 stands in for the one this call does not have)
+    r = scaled_region(first_entry, (0, 0, 0), (1, 1), out_view, layout=layout, type=type)
+    if (r.out_x, r.out_y) != (shape[1], shape[0]):
+        raise ValueError("out_view is %u x %u points, %s %u x %u" % (r.out_x, r.out_y, name, shape[1], shape[0]))
+    lptr, lod_row_pitch = _lod_buffer(lod, r.out_x, r.out_y, points.device, name)
+    return r.out_x, r.out_y, points.data_ptr(), point_row_pitch, lptr, lod_row_pitch, lod_bias, r.out, r.row_pitch, r.plane_pitch
+
+
 class CubeSampler(C.Structure):
     """struct astcenc_amd_cube_sampler (include/astcenc_amd.h): SAMPLE_* filter within a level, MIP_NEAREST / MIP_LINEAR between
     levels."""
@@ -471,29 +500,7 @@ def cube_grid(first_entry, level_count, cube, dirs, lod, out_view, lod_bias=0.0,
     cannot express: directions that are not float32, not [H, W, 3], whose triples are not adjacent or not three floats apart or
     whose rows overlap; everything lod_grid rejects of `lod`, `out_view`, level_count and lod_bias.  Or explicit tuples: dirs =
     (ptr, out_x, out_y, dir_row_pitch), lod = (ptr, lod_row_pitch) or None, out_view = (ptr, row_pitch, plane_pitch)."""
-    _check_chain(level_count, lod_bias)
-    if isinstance(dirs, tuple):
-        dptr, out_x, out_y, dir_row_pitch = dirs
-        optr, row_pitch, plane_pitch = out_view
-        lptr, lod_row_pitch = lod if lod is not None else (None, 0)
-        return CubeGrid(first_entry, level_count, cube, out_x, out_y, dptr, dir_row_pitch, lptr, lod_row_pitch, lod_bias, optr, row_pitch, plane_pitch)
-    import torch
-    if dirs.dtype != torch.float32:
-        raise ValueError("dirs is %s: float32 triples" % dirs.dtype)
-    dshape, dst = tuple(dirs.shape), tuple(dirs.stride())
-    if dirs.dim() != 3 or dshape[2] != 3:
-        raise ValueError("dirs has shape %r: [H, W, 3]" % (dshape,))
-    if dst[2] != 1 or (dst[1] != 3 and dshape[1] > 1) or dst[0] < 0 or (dst[0] == 0 and dshape[0] > 1):
-        raise ValueError("the triples of dirs must be adjacent floats, three floats apart, its rows apart (strides %r)" % (dst,))
-    dir_row_pitch = dst[0] if dshape[0] > 1 else 0
-    if dir_row_pitch != 0 and dir_row_pitch < 3 * dshape[1]:
-        raise ValueError("the rows of dirs overlap (strides %r)" % (dst,))
-    # (the output's checks are scaled_region's: a window of 1 x 1 stands in for the one this call does not have)
-    r = scaled_region(first_entry, (0, 0, 0), (1, 1), out_view, layout=layout, type=type)
-    if (r.out_x, r.out_y) != (dshape[1], dshape[0]):
-        raise ValueError("out_view is %u x %u points, dirs %u x %u" % (r.out_x, r.out_y, dshape[1], dshape[0]))
-    lptr, lod_row_pitch = _lod_buffer(lod, r.out_x, r.out_y, dirs.device, "dirs")
-    return CubeGrid(first_entry, level_count, cube, r.out_x, r.out_y, dirs.data_ptr(), dir_row_pitch, lptr, lod_row_pitch, lod_bias, r.out, r.row_pitch, r.plane_pitch)
+    return CubeGrid(first_entry, level_count, cube, *_triple_grid(first_entry, level_count, "dirs", dirs, lod, out_view, lod_bias, layout, type))
 
 
 class VolumeSampler(C.Structure):
@@ -517,29 +524,7 @@ def volume_grid(first_entry, level_count, coords, lod, out_view, lod_bias=0.0, l
     adjacent or not three floats apart or whose rows overlap; everything lod_grid rejects of `lod`, `out_view`, level_count and
     lod_bias.  Or explicit tuples: coords = (ptr, out_x, out_y, coord_row_pitch), lod = (ptr, lod_row_pitch) or None, out_view =
     (ptr, row_pitch, plane_pitch)."""
-    _check_chain(level_count, lod_bias)
-    if isinstance(coords, tuple):
-        cptr, out_x, out_y, coord_row_pitch = coords
-        optr, row_pitch, plane_pitch = out_view
-        lptr, lod_row_pitch = lod if lod is not None else (None, 0)
-        return VolumeGrid(first_entry, level_count, out_x, out_y, cptr, coord_row_pitch, lptr, lod_row_pitch, lod_bias, optr, row_pitch, plane_pitch)
-    import torch
-    if coords.dtype != torch.float32:
-        raise ValueError("coords is %s: float32 triples" % coords.dtype)
-    cshape, cst = tuple(coords.shape), tuple(coords.stride())
-    if coords.dim() != 3 or cshape[2] != 3:
-        raise ValueError("coords has shape %r: [H, W, 3]" % (cshape,))
-    if cst[2] != 1 or (cst[1] != 3 and cshape[1] > 1) or cst[0] < 0 or (cst[0] == 0 and cshape[0] > 1):
-        raise ValueError("the triples of coords must be adjacent floats, three floats apart, its rows apart (strides %r)" % (cst,))
-    coord_row_pitch = cst[0] if cshape[0] > 1 else 0
-    if coord_row_pitch != 0 and coord_row_pitch < 3 * cshape[1]:
-        raise ValueError("the rows of coords overlap (strides %r)" % (cst,))
-    # (the output's checks are scaled_region's: a window of 1 x 1 stands in for the one this call does not have)
-    r = scaled_region(first_entry, (0, 0, 0), (1, 1), out_view, layout=layout, type=type)
-    if (r.out_x, r.out_y) != (cshape[1], cshape[0]):
-        raise ValueError("out_view is %u x %u points, coords %u x %u" % (r.out_x, r.out_y, cshape[1], cshape[0]))
-    lptr, lod_row_pitch = _lod_buffer(lod, r.out_x, r.out_y, coords.device, "coords")
-    return VolumeGrid(first_entry, level_count, r.out_x, r.out_y, coords.data_ptr(), coord_row_pitch, lptr, lod_row_pitch, lod_bias, r.out, r.row_pitch, r.plane_pitch)
+    return VolumeGrid(first_entry, level_count, *_triple_grid(first_entry, level_count, "coords", coords, lod, out_view, lod_bias, layout, type))
 
 
 class ErrorSums(C.Structure):

@@ -1,14 +1,19 @@
 // SPDX-License-Identifier: Apache-2.0
 // Test infrastructure: what the harnesses of the windowed and the sampled decoders share (decode_region_check.cpp,
-// decode_tensor_check.cpp, decode_scaled_check.cpp, decode_sample_check.cpp, decode_lod_check.cpp): the random numbers, the count
-// of checks and mismatches, a prepared DecodeImage, and the pieces of the tensor model (include/astcenc_amd.h) that every tensor
-// call ends in -- a stored texel's component widened, and the scaled, shifted value's bits by integer arithmetic.
+// decode_tensor_check.cpp, decode_scaled_check.cpp, decode_sample_check.cpp and, through decode_lod_check_common.h, those of the
+// level-of-detail samplers): the random numbers, the count of checks and mismatches, a prepared DecodeImage, the pieces of the
+// tensor model (include/astcenc_amd.h) that every tensor call ends in -- a stored texel's component widened, and the scaled,
+// shifted value's bits by integer arithmetic -- and what the samplers' harnesses are made of: the dispatch on a tensor type and
+// layout, random streams, an image decoded whole, files of floats read and of bytes written.
 // Included after the harness has defined ASTC_VARIANT and included the decode_*.h it checks; DECODE_CHECK_ITEM, defined before,
 // names what a mismatch is counted in ("region" unless a harness says "grid").
 #pragma once
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
 
 using namespace astcd;
 
@@ -102,3 +107,70 @@ inline uint32_t model_bits(float s, float scale, float bias, uint32_t type)
 }
 
 struct Format { uint32_t type, layout, channels; };
+
+/* fn(type, layout) with the tensor type and layout as constants: the kernels' one build per type and layout. */
+template <class Fn>
+static auto with_build(uint32_t type, uint32_t layout, Fn fn)
+{
+	switch (type * 2u + layout)
+	{
+	case 0: return fn(std::integral_constant<uint32_t, 0>(), std::integral_constant<uint32_t, 0>());
+	case 1: return fn(std::integral_constant<uint32_t, 0>(), std::integral_constant<uint32_t, 1>());
+	case 2: return fn(std::integral_constant<uint32_t, 1>(), std::integral_constant<uint32_t, 0>());
+	case 3: return fn(std::integral_constant<uint32_t, 1>(), std::integral_constant<uint32_t, 1>());
+	case 4: return fn(std::integral_constant<uint32_t, 2>(), std::integral_constant<uint32_t, 0>());
+	default: return fn(std::integral_constant<uint32_t, 2>(), std::integral_constant<uint32_t, 1>());
+	}
+}
+
+/* Random 16-byte patterns with constant-colour blocks (UNORM16 and FP16) and reserved-mode blocks among them; only_reserved:
+ * reserved-mode blocks only. */
+inline void random_blocks(std::vector<uint8_t>& blocks, size_t nblocks, int only_reserved = 0)
+{
+	blocks.resize(nblocks * 16);
+	for (size_t b = 0; b < nblocks; b++)
+	{
+		uint8_t* p = blocks.data() + b * 16;
+		for (int i = 0; i < 16; i++) p[i] = (uint8_t)rnd();
+		const uint32_t kind = only_reserved ? 3u : rnd() % 16u;
+		if (kind < 3)
+		{
+			// constant colour without an extent: 0x1FC, the FP16 flag, the reserved bits and the extent all ones
+			p[0] = 0xFC; p[1] = kind == 2 ? 0xFF : 0xFD;
+			for (int i = 2; i < 8; i++) p[i] = 0xFF;
+			if (kind == 2) for (int i = 0; i < 4; i++) { const uint16_t h = (uint16_t)(rnd() % 0x7C00u); memcpy(p + 8 + 2 * i, &h, 2); }
+		}
+		else if (kind == 3) memset(p, 0, 16);       // a reserved block mode: an error block
+	}
+}
+
+/* The whole image, as the decoder writes it. */
+inline void decode_whole(DecodeImage& img, const std::vector<uint8_t>& blocks, std::vector<uint8_t>& whole, DecodeBatch& batch)
+{
+	const size_t tb = img.data_type == 0 ? 4 : img.data_type == 1 ? 8 : 16;
+	whole.assign((size_t)img.dim_x * img.dim_y * img.dim_z * tb, 0x5A);
+	img.data = whole.data();
+	for (uint32_t z = 0; z < img.blocks_z; z++)
+		for (uint32_t y = 0; y < img.blocks_y; y++)
+			for (uint32_t x0 = 0; x0 < img.blocks_x; x0 += DECODE_BATCH)
+				decode_row_batch(img, blocks.data(), x0, y, z, i_min(DECODE_BATCH, (int)(img.blocks_x - x0)), batch);
+	img.data = nullptr;
+}
+
+/* A file of binary32 values into v (its size says how many), and bytes out to a file. */
+inline bool read_floats(const char* path, std::vector<float>& v)
+{
+	FILE* fp = fopen(path, "rb");
+	if (!fp) return false;
+	const bool ok = fread(v.data(), sizeof(float), v.size(), fp) == v.size();
+	fclose(fp);
+	return ok;
+}
+
+inline bool write_bytes(const std::string& path, const std::vector<uint8_t>& v)
+{
+	FILE* fp = fopen(path.c_str(), "wb");
+	if (!fp) return false;
+	const bool ok = fwrite(v.data(), 1, v.size(), fp) == v.size();
+	return fclose(fp) == 0 && ok;
+}

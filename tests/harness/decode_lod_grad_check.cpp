@@ -23,7 +23,7 @@
 #include "backend.h"
 #include "decode_lod_grad.h"
 #define DECODE_CHECK_ITEM "grid"
-#include "decode_check_common.h"
+#include "decode_lod_check_common.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
@@ -199,29 +199,6 @@ static void model_point(const Chain& ch, const DecodeLodSampler& smp, uint32_t z
 
 struct Grid { uint32_t z, ox, oy; std::vector<float> uv; std::vector<float> lod; bool has_lod; float bias; bool want_lod; };       // uv: ox * oy pairs, row by row
 
-template <class Fn>
-static auto with_build(uint32_t type, uint32_t layout, Fn fn)
-{
-	switch (type * 2u + layout)
-	{
-	case 0: return fn(std::integral_constant<uint32_t, 0>(), std::integral_constant<uint32_t, 0>());
-	case 1: return fn(std::integral_constant<uint32_t, 0>(), std::integral_constant<uint32_t, 1>());
-	case 2: return fn(std::integral_constant<uint32_t, 1>(), std::integral_constant<uint32_t, 0>());
-	case 3: return fn(std::integral_constant<uint32_t, 1>(), std::integral_constant<uint32_t, 1>());
-	case 4: return fn(std::integral_constant<uint32_t, 2>(), std::integral_constant<uint32_t, 0>());
-	default: return fn(std::integral_constant<uint32_t, 2>(), std::integral_constant<uint32_t, 1>());
-	}
-}
-
-/* The level records of a grid as the kernel finds them: at the record's offset in the table. */
-struct LevelsOfGrid {
-	const uint8_t* at;
-	DecodeLodLevel operator()(uint32_t l) const
-	{
-		return image_set_record<DecodeLodLevel>(reinterpret_cast<const uint32_t*>(at + (size_t)l * sizeof(DecodeLodLevel)));
-	}
-};
-
 /* An upstream value the tensor type holds: its bits and its widening to binary32. */
 static float upstream_value(uint32_t type, uint32_t kind, uint8_t* bits)
 {
@@ -394,38 +371,6 @@ static void check_table(const char* chain_tag, const Chain& ch, const std::vecto
 			fail(!w.want_lod ? "grad_lod was written though it is not wanted" : "grad_lod differs from the model (or padding or a guard was written)", tag, i, (long)at - (long)guard);
 		}
 	}
-}
-
-static void random_blocks(std::vector<uint8_t>& blocks, size_t nblocks)
-{
-	blocks.resize(nblocks * 16);
-	for (size_t b = 0; b < nblocks; b++)
-	{
-		uint8_t* p = blocks.data() + b * 16;
-		for (int i = 0; i < 16; i++) p[i] = (uint8_t)rnd();
-		const uint32_t kind = rnd() % 16u;
-		if (kind < 3)
-		{
-			// constant colour without an extent: 0x1FC, the FP16 flag, the reserved bits and the extent all ones
-			p[0] = 0xFC; p[1] = kind == 2 ? 0xFF : 0xFD;
-			for (int i = 2; i < 8; i++) p[i] = 0xFF;
-			if (kind == 2) for (int i = 0; i < 4; i++) { const uint16_t h = (uint16_t)(rnd() % 0x7C00u); memcpy(p + 8 + 2 * i, &h, 2); }
-		}
-		else if (kind == 3) memset(p, 0, 16);       // a reserved block mode: an error block
-	}
-}
-
-/* The whole image, as the decoder writes it. */
-static void decode_whole(DecodeImage& img, const std::vector<uint8_t>& blocks, std::vector<uint8_t>& whole, DecodeBatch& batch)
-{
-	const size_t tb = img.data_type == 0 ? 4 : img.data_type == 1 ? 8 : 16;
-	whole.assign((size_t)img.dim_x * img.dim_y * img.dim_z * tb, 0x5A);
-	img.data = whole.data();
-	for (uint32_t z = 0; z < img.blocks_z; z++)
-		for (uint32_t y = 0; y < img.blocks_y; y++)
-			for (uint32_t x0 = 0; x0 < img.blocks_x; x0 += DECODE_BATCH)
-				decode_row_batch(img, blocks.data(), x0, y, z, i_min(DECODE_BATCH, (int)(img.blocks_x - x0)), batch);
-	img.data = nullptr;
 }
 
 /* The full chain of a dim_x x dim_y x dim_z image; dtype 3: levels of U8, F16, F32 in turn. */

@@ -26,7 +26,7 @@
 #include "backend.h"
 #include "decode_volume.h"
 #define DECODE_CHECK_ITEM "grid"
-#include "decode_check_common.h"
+#include "decode_lod_check_common.h"
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
@@ -35,45 +35,6 @@
 #include <vector>
 
 static_assert(VOLUME_TILE_BLOCKS == 512, "the listed-block trap of sample_batches (eight slots) bounds a pass at 512 blocks");
-
-struct LevelsOfGrid {
-	const uint8_t* at;
-	DecodeLodLevel operator()(uint32_t l) const
-	{
-		return image_set_record<DecodeLodLevel>(reinterpret_cast<const uint32_t*>(at + (size_t)l * sizeof(DecodeLodLevel)));
-	}
-};
-
-template <class Fn>
-static auto with_build(uint32_t type, uint32_t layout, Fn fn)
-{
-	switch (type * 2u + layout)
-	{
-	case 0: return fn(std::integral_constant<uint32_t, 0>(), std::integral_constant<uint32_t, 0>());
-	case 1: return fn(std::integral_constant<uint32_t, 0>(), std::integral_constant<uint32_t, 1>());
-	case 2: return fn(std::integral_constant<uint32_t, 1>(), std::integral_constant<uint32_t, 0>());
-	case 3: return fn(std::integral_constant<uint32_t, 1>(), std::integral_constant<uint32_t, 1>());
-	case 4: return fn(std::integral_constant<uint32_t, 2>(), std::integral_constant<uint32_t, 0>());
-	default: return fn(std::integral_constant<uint32_t, 2>(), std::integral_constant<uint32_t, 1>());
-	}
-}
-
-static bool read_floats(const char* path, std::vector<float>& v)
-{
-	FILE* fp = fopen(path, "rb");
-	if (!fp) return false;
-	const bool ok = fread(v.data(), sizeof(float), v.size(), fp) == v.size();
-	fclose(fp);
-	return ok;
-}
-
-static bool write_bytes(const std::string& path, const std::vector<uint8_t>& v)
-{
-	FILE* fp = fopen(path.c_str(), "wb");
-	if (!fp) return false;
-	const bool ok = fwrite(v.data(), 1, v.size(), fp) == v.size();
-	return fclose(fp) == 0 && ok;
-}
 
 static const uint32_t RGBA[4] = { 0, 1, 2, 3 };
 
@@ -124,37 +85,6 @@ static int points_mode(char** a)
 			}
 	}
 	return 0;
-}
-
-/* Random 16-byte patterns mixed with constant-colour blocks (UNORM16 and FP16) and reserved-mode blocks. */
-static void random_blocks(std::vector<uint8_t>& blocks, size_t nblocks)
-{
-	blocks.resize(nblocks * 16);
-	for (size_t b = 0; b < nblocks; b++)
-	{
-		uint8_t* p = blocks.data() + b * 16;
-		for (int i = 0; i < 16; i++) p[i] = (uint8_t)rnd();
-		const uint32_t kind = rnd() % 16u;
-		if (kind < 3)
-		{
-			p[0] = 0xFC; p[1] = kind == 2 ? 0xFF : 0xFD;
-			for (int i = 2; i < 8; i++) p[i] = 0xFF;
-			if (kind == 2) for (int i = 0; i < 4; i++) { const uint16_t h = (uint16_t)(rnd() % 0x7C00u); memcpy(p + 8 + 2 * i, &h, 2); }
-		}
-		else if (kind == 3) memset(p, 0, 16);
-	}
-}
-
-static void decode_whole(DecodeImage& img, const std::vector<uint8_t>& blocks, std::vector<uint8_t>& whole, DecodeBatch& batch)
-{
-	const size_t tb = img.data_type == 0 ? 4 : img.data_type == 1 ? 8 : 16;
-	whole.assign((size_t)img.dim_x * img.dim_y * img.dim_z * tb, 0x5A);
-	img.data = whole.data();
-	for (uint32_t z = 0; z < img.blocks_z; z++)
-		for (uint32_t y = 0; y < img.blocks_y; y++)
-			for (uint32_t x0 = 0; x0 < img.blocks_x; x0 += DECODE_BATCH)
-				decode_row_batch(img, blocks.data(), x0, y, z, i_min(DECODE_BATCH, (int)(img.blocks_x - x0)), batch);
-	img.data = nullptr;
 }
 
 static int tiles_mode(char** a)
@@ -218,13 +148,13 @@ static int tiles_mode(char** a)
 		memcpy(cheld.data() + j * crow, coords.data() + (size_t)j * 3u * ox, 3u * (size_t)ox * sizeof(float));
 		memcpy(lheld.data() + j * lrow, lod.data() + (size_t)j * ox, (size_t)ox * sizeof(float));
 	}
-	DecodeVolumeLaunch g;
+	DecodeLodLaunch g;
 	memset(&g, 0, sizeof(g));
 	g.first_entry = 1; g.level_count = levels; g.out_x = ox; g.out_y = oy;
 	g.d_coords = cheld.data(); g.coord_row_pitch = crow;
 	g.d_lod = has_lod ? lheld.data() : nullptr; g.lod_row_pitch = lrow; g.lod_bias = bias;
 	g.d_out = out.data() + guard; g.row_pitch = row; g.plane_pitch = plane;
-	const DecodeVolumeSampler smp = { filter, ax, ay, az, mip };
+	const DecodeLodSampler smp = { filter, ax, ay, mip, az };
 	std::vector<uint8_t> table(decode_volume_bytes(&g, 1));
 	const uint32_t tiles = decode_volume_build(table.data(), images.data(), streams.data(), format, smp, &g, 1);
 	const std::vector<uint8_t> table_before = table;
@@ -281,13 +211,13 @@ static int blocks_mode(char** a)
 	memset(&format, 0, sizeof(format));
 	format.type = 1; format.layout = 0; format.channels = 3;
 	for (int c = 0; c < 3; c++) format.scale[c] = 1.0f;
-	DecodeVolumeLaunch g;
+	DecodeLodLaunch g;
 	memset(&g, 0, sizeof(g));
 	g.first_entry = 0; g.level_count = levels; g.out_x = ox; g.out_y = oy;
 	g.d_coords = coords.data(); g.coord_row_pitch = 3u * (size_t)ox;
 	g.d_lod = has_lod ? lod.data() : nullptr; g.lod_row_pitch = ox;
 	g.d_out = out.data(); g.row_pitch = ox; g.plane_pitch = (size_t)ox * oy;
-	const DecodeVolumeSampler smp = { filter, 0, 0, 0, mip };
+	const DecodeLodSampler smp = { filter, 0, 0, mip };
 	std::vector<uint8_t> table(decode_volume_bytes(&g, 1));
 	const uint32_t tiles = decode_volume_build(table.data(), images.data(), streams.data(), format, smp, &g, 1);
 	DecodeVolumeRecord rec;

@@ -18,7 +18,7 @@ import sample_model as S
 import tensor_model as M
 from test_decode_scaled import GUARD, SCALE, BIAS, dev
 from test_decode_sample import contexts  # noqa: F401  (the fixture)
-from test_decode_lod import make_chain
+from test_decode_lod import grid_message, log_names, make_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -324,9 +324,9 @@ def test_bad_arguments_write_nothing_and_name_the_index(product, A, contexts, ch
             ("a cube beyond the layers of one level", grid(2, cube=1), A.ERR_BAD_PARAM, "grid 2 of 3", dict(entry_list=entry(3, dim_z=6))),
             ("a cube that wraps 32 bits", grid(0, cube=0x2AAAAAAB), A.ERR_BAD_PARAM, "grid 0 of 3", {}),
             ("a face above 65536 texels", good, A.ERR_BAD_PARAM, "grid 0 of 3", dict(entry_list=entry(1, dim_x=65537, dim_y=65537, dim_z=6, blocks_len=1 << 40))),
-            ("directions not aligned to 4 bytes", grid(1, dirs=dptr + 2), A.ERR_BAD_PARAM, "grid 1 of 3", {}),
-            ("a dir_row_pitch below 3 out_x", grid(0, dir_row_pitch=89), A.ERR_BAD_PARAM, "grid 0 of 3", {}),
-            ("null directions", grid(2, dirs=None), A.ERR_BAD_CONTEXT, "grid 2 of 3", {}),
+            ("directions not aligned to 4 bytes", grid(1, dirs=dptr + 2), A.ERR_BAD_PARAM, grid_message(1, 3, "dirs 0x... is not aligned to a float (4 bytes)"), {}),
+            ("a dir_row_pitch below 3 out_x", grid(0, dir_row_pitch=89), A.ERR_BAD_PARAM, grid_message(0, 3, "dir_row_pitch 89: at least 90 floats"), {}),
+            ("null directions", grid(2, dirs=None), A.ERR_BAD_CONTEXT, grid_message(2, 3, "dirs is null"), {}),
             # shared with the lod call
             ("a null sampler", good, A.ERR_BAD_PARAM, "sampler", dict(sampler=None)),
             ("an unknown mip filter", good, A.ERR_BAD_PARAM, "mip_filter", dict(sampler=A.CubeSampler(1, 2))),
@@ -345,7 +345,7 @@ def test_bad_arguments_write_nothing_and_name_the_index(product, A, contexts, ch
             assert call(fmt, grids, **kw) == code, what
             torch.cuda.synchronize()
             assert bool((out == GUARD).all()), what
-            assert any(named in m for m in logged), (what, logged)
+            assert any(log_names(named, m) for m in logged), (what, logged)
         # a context whose footprint is 3D
         del logged[:]
         assert call(fmt, good, context=contexts((3, 3, 3), A.PRF_LDR)) == A.ERR_BAD_PARAM
