@@ -856,12 +856,10 @@ class Library:
     def _set_args(entries, stream):
         """ctypes array of the entries (ImageSetEntry, or (image, blocks[, swizzle]) tuples of torch tensors) and the stream:
         a torch stream, a raw hipStream_t, or None for torch's current stream."""
+        device = next((e[1].device for e in entries if not isinstance(e, ImageSetEntry)), None)
         entries = [e if isinstance(e, ImageSetEntry) else image_set_entry(*e) for e in entries]
         arr = (ImageSetEntry * len(entries))(*entries) if entries else None
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream()
-        return arr, len(entries), getattr(stream, "cuda_stream", stream)
+        return arr, len(entries), torch_stream(stream, device)
 
     def compress_images_device(self, ctx, entries, stream=None):
         """astcenc_amd_compress_images_device over `entries` (see _set_args); returns the astcenc_error, the kernel time of the
@@ -988,13 +986,11 @@ class Library:
         assert image.is_contiguous() and blocks.is_contiguous() and image.dim() in (3, 4) and image.shape[-1] == 4
         assert block_errors is None or (block_errors.is_contiguous() and block_errors.dtype == torch.float64)
         d = image.shape[0] if image.dim() == 4 else 1
-        if stream is None:
-            stream = torch.cuda.current_stream()
         image_type = types[image.dtype]
         return [blocks.data_ptr(), blocks.numel(), image.data_ptr(), image.shape[-2], image.shape[-3], d, image_type,
                 image_type if decode_type is None else decode_type, C.byref(Swizzle(*swizzle)),
                 None if block_errors is None else block_errors.data_ptr(), 0 if block_errors is None else block_errors.numel() * 8], \
-            getattr(stream, "cuda_stream", stream)
+            torch_stream(stream, image.device)
 
     def compare_blocks_device(self, ctx, blocks, image, decode_type=None, swizzle=SWZ_RGBA, block_errors=None, stream=None):
         """astcenc_amd_compare_blocks_device: the blocks decoded to decode_type (default: the image's type) through `swizzle` against
@@ -1020,10 +1016,8 @@ class Library:
         import torch
         types = {torch.uint8: TYPE_U8, torch.float16: TYPE_F16, torch.float32: TYPE_F32}
         assert image.is_contiguous() and image.dim() in (3, 4) and image.shape[-1] == 4
-        if stream is None:
-            stream = torch.cuda.current_stream()
         d = image.shape[0] if image.dim() == 4 else 1
-        return [image.data_ptr(), image.shape[-2], image.shape[-3], d, types[image.dtype]], getattr(stream, "cuda_stream", stream)
+        return [image.data_ptr(), image.shape[-2], image.shape[-3], d, types[image.dtype]], torch_stream(stream, image.device)
 
     def compress_block_list_device(self, ctx, image, block_list, out, swizzle=SWZ_RGBA, list_count=None, data_len=None, stream=None):
         """astcenc_amd_compress_block_list_device: the blocks of `image` named in `block_list` (a device tensor of 32-bit raster block
@@ -1043,13 +1037,10 @@ class Library:
         """astcenc_amd_select_blocks_device: `block_errors` float64 [blocks, 4] on the device, dims (x, y, z) of the image,
         `criterion` a BlockCriterion, `block_list` a device tensor of 32-bit words, one per block.  Returns (error, count): the
         ascending indices of the selected blocks are block_list[:count]."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream()
         count = C.c_uint(0)
         err = self.lib.astcenc_amd_select_blocks_device(ctx, block_errors.data_ptr(), block_errors.numel() * 8, dims[0], dims[1], dims[2],
                                                         C.byref(criterion), block_list.data_ptr(), block_list.numel() * 4,
-                                                        getattr(stream, "cuda_stream", stream), C.byref(count))
+                                                        torch_stream(stream, block_errors.device), C.byref(count))
         return err, count.value
 
     def compress_image_adaptive_device(self, base_ctx, strong_ctx, image, criterion, out, swizzle=SWZ_RGBA, decode_swizzle=SWZ_RGBA,
@@ -1069,14 +1060,11 @@ class Library:
         """astcenc_amd_select_blocks_set_device: `dims` the (x, y, z) of every entry of the set, `block_errors` float64 [blocks of the
         set, 4] on the device, `block_list` a device tensor of 32-bit words.  Returns (error, candidates, selected): the ascending
         global indices of the selected blocks are block_list[:selected]."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream()
         entries = (ImageSetEntry * max(len(dims), 1))(*[ImageSetEntry(None, None, 0, d[0], d[1], d[2], TYPE_U8, Swizzle(*SWZ_RGBA)) for d in dims])
         candidates, selected = C.c_uint(0), C.c_uint(0)
         err = self.lib.astcenc_amd_select_blocks_set_device(ctx, entries, len(dims), block_errors.data_ptr(), block_errors.numel() * 8,
                                                             C.byref(criterion), max_blocks, block_list.data_ptr(), block_list.numel() * 4,
-                                                            getattr(stream, "cuda_stream", stream), C.byref(candidates), C.byref(selected))
+                                                            torch_stream(stream, block_errors.device), C.byref(candidates), C.byref(selected))
         return err, candidates.value, selected.value
 
     def compress_block_list_set_device(self, ctx, entries, block_list, list_count=None, stream=None):
@@ -1139,7 +1127,7 @@ class Library:
         """Levels of the [H, W, 4] device tensor `image` (astcenc_amd_generate_mip_chain_device): a list of torch views, one per
         level, level 0 being `image` itself and the others views of one buffer."""
         w, h, dtype, layout, store, tensors, _ = self._mip_chain_buffers(ctx, image, levels, False)
-        s = torch_stream(stream)
+        s = torch_stream(stream, image.device)
         err = self.lib.astcenc_amd_generate_mip_chain_device(ctx, image.data_ptr(), w, h, dtype, layout.level_count,
                                                              store.data_ptr(), layout.texels_len, s)
         if err:
@@ -1150,7 +1138,7 @@ class Library:
         """astcenc_amd_compress_mip_chain_device: returns (level tensors, per-level block tensors); the kernel time of the call
         (ms, generation included) in self.last_kernel_ms."""
         w, h, dtype, layout, store, tensors, out = self._mip_chain_buffers(ctx, image, levels, True)
-        s = torch_stream(stream)
+        s = torch_stream(stream, image.device)
         ms = C.c_float(0.0)
         err = self.lib.astcenc_amd_compress_mip_chain_device(ctx, image.data_ptr(), w, h, dtype, C.byref(Swizzle(*swizzle)),
                                                              layout.level_count, store.data_ptr(), layout.texels_len,
@@ -1193,7 +1181,7 @@ class Library:
         W_i, 4] torch views, level 0 being `image` itself."""
         (w, h, d), dtype, layout, store, tensors, _ = self._mip_chain_volume_buffers(ctx, image, kind, levels, False)
         err = self.lib.astcenc_amd_generate_mip_chain_volume_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
-                                                                    store.data_ptr(), layout.texels_len, torch_stream(stream))
+                                                                    store.data_ptr(), layout.texels_len, torch_stream(stream, image.device))
         if err:
             raise AstcError(err, "astcenc_amd_generate_mip_chain_volume_device")
         return tensors
@@ -1205,7 +1193,7 @@ class Library:
         ms = C.c_float(0.0)
         err = self.lib.astcenc_amd_compress_mip_chain_volume_device(ctx, image.data_ptr(), w, h, d, kind, dtype, C.byref(Swizzle(*swizzle)),
                                                                     layout.level_count, store.data_ptr(), layout.texels_len,
-                                                                    out.data_ptr(), layout.blocks_len, torch_stream(stream), C.byref(ms))
+                                                                    out.data_ptr(), layout.blocks_len, torch_stream(stream, image.device), C.byref(ms))
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_compress_mip_chain_volume_device")
@@ -1225,7 +1213,7 @@ class Library:
         (w, h, d), dtype, layout, store, tensors, _ = self._mip_chain_volume_buffers(ctx, image, kind, levels, False)
         err = self.lib.astcenc_amd_generate_mip_chain_ex_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
                                                                 self._mip_options(options), store.data_ptr(), layout.texels_len,
-                                                                torch_stream(stream))
+                                                                torch_stream(stream, image.device))
         if err:
             raise AstcError(err, "astcenc_amd_generate_mip_chain_ex_device")
         return tensors
@@ -1237,7 +1225,7 @@ class Library:
         ms = C.c_float(0.0)
         err = self.lib.astcenc_amd_compress_mip_chain_ex_device(ctx, image.data_ptr(), w, h, d, kind, dtype, C.byref(Swizzle(*swizzle)),
                                                                 layout.level_count, self._mip_options(options), store.data_ptr(),
-                                                                layout.texels_len, out.data_ptr(), layout.blocks_len, torch_stream(stream),
+                                                                layout.texels_len, out.data_ptr(), layout.blocks_len, torch_stream(stream, image.device),
                                                                 C.byref(ms))
         self.last_kernel_ms = ms.value
         if err:
@@ -1258,7 +1246,7 @@ class Library:
         (w, h, d), dtype, layout, store, tensors, _ = self._mip_chain_volume_buffers(ctx, image, kind, levels, False)
         err = self.lib.astcenc_amd_generate_mip_chain_filtered_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
                                                                       self._mip_options(options), self._mip_filter(mip_filter),
-                                                                      store.data_ptr(), layout.texels_len, torch_stream(stream))
+                                                                      store.data_ptr(), layout.texels_len, torch_stream(stream, image.device))
         if err:
             raise AstcError(err, "astcenc_amd_generate_mip_chain_filtered_device")
         return tensors
@@ -1272,7 +1260,7 @@ class Library:
         err = self.lib.astcenc_amd_compress_mip_chain_filtered_device(ctx, image.data_ptr(), w, h, d, kind, dtype, C.byref(Swizzle(*swizzle)),
                                                                       layout.level_count, self._mip_options(options),
                                                                       self._mip_filter(mip_filter), store.data_ptr(), layout.texels_len,
-                                                                      out.data_ptr(), layout.blocks_len, torch_stream(stream), C.byref(ms))
+                                                                      out.data_ptr(), layout.blocks_len, torch_stream(stream, image.device), C.byref(ms))
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_compress_mip_chain_filtered_device")
@@ -1295,7 +1283,7 @@ class Library:
         err = self.lib.astcenc_amd_generate_mip_chain_weighted_device(ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
                                                                       self._mip_options(options), self._mip_filter(mip_filter),
                                                                       self._mip_weighting(weighting), store.data_ptr(), layout.texels_len,
-                                                                      torch_stream(stream))
+                                                                      torch_stream(stream, image.device))
         if err:
             raise AstcError(err, "astcenc_amd_generate_mip_chain_weighted_device")
         return tensors
@@ -1310,7 +1298,7 @@ class Library:
                                                                       layout.level_count, self._mip_options(options),
                                                                       self._mip_filter(mip_filter), self._mip_weighting(weighting),
                                                                       store.data_ptr(), layout.texels_len, out.data_ptr(), layout.blocks_len,
-                                                                      torch_stream(stream), C.byref(ms))
+                                                                      torch_stream(stream, image.device), C.byref(ms))
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_compress_mip_chain_weighted_device")
@@ -1326,18 +1314,17 @@ class Library:
         astcenc_amd_compress_images_adaptive_device compresses the set.  Returns (level tensors, per-level block tensors,
         AdaptiveSetStats)."""
         (w, h, d), dtype, layout, store, tensors, out = self._mip_chain_volume_buffers(base_ctx, image, kind, levels, True)
+        s = torch_stream(stream, image.device)
         err = self.lib.astcenc_amd_generate_mip_chain_weighted_device(base_ctx, image.data_ptr(), w, h, d, kind, dtype, layout.level_count,
                                                                       self._mip_options(options), self._mip_filter(mip_filter),
-                                                                      self._mip_weighting(weighting), store.data_ptr(), layout.texels_len,
-                                                                      torch_stream(stream))
+                                                                      self._mip_weighting(weighting), store.data_ptr(), layout.texels_len, s)
         if err:
             raise AstcError(err, "astcenc_amd_generate_mip_chain_weighted_device")
         n = layout.level_count
         ends = [layout.blocks_offset[i] for i in range(1, n)] + [layout.blocks_len]
         blocks = [out[layout.blocks_offset[i]:ends[i]] for i in range(n)]
         entries = [image_set_entry(tensors[i], blocks[i], swizzle) for i in range(n)]
-        err, stats = self.compress_images_adaptive_device(base_ctx, strong_ctx, entries, criterion, max_blocks, decode_swizzle, block_errors,
-                                                          torch_stream(stream))
+        err, stats = self.compress_images_adaptive_device(base_ctx, strong_ctx, entries, criterion, max_blocks, decode_swizzle, block_errors, s)
         if err:
             raise AstcError(err, "astcenc_amd_compress_images_adaptive_device")
         return tensors, blocks, stats
@@ -1363,7 +1350,7 @@ class Library:
         ms = C.c_float(0.0)
         err = self.lib.astcenc_amd_resize_image_device(ctx, image.data_ptr(), w, h, d, kind, types[image.dtype],
                                                        C.byref(Resize(ow, oh, od, flt, wt)), out.data_ptr(),
-                                                       out.numel() * out.element_size(), torch_stream(stream), C.byref(ms))
+                                                       out.numel() * out.element_size(), torch_stream(stream, image.device), C.byref(ms))
         self.last_kernel_ms = ms.value
         if err:
             raise AstcError(err, "astcenc_amd_resize_image_device")
@@ -1439,12 +1426,21 @@ def _sample_lod_function():
     return SampleLod
 
 
-def torch_stream(stream):
-    """A raw hipStream_t of a torch stream, a raw handle, or torch's current stream for None."""
+def torch_stream(stream=None, device=None):
+    """The hip_stream argument of a device call: the raw hipStream_t of a torch stream, a raw handle as it is, or that of
+    torch's current stream on `device` (None: torch's current device) for None.  Handle 0 is torch's default stream, the legacy
+    null stream, but a NULL hip_stream is the context's own non-blocking stream (include/astcenc_amd.h), which waits for nothing
+    queued on the null stream: the default stream of `device` is synchronised here first, so that what torch queued before the
+    call -- the call's inputs, fills of its outputs -- is done when the call starts.  Every call synchronises its stream before it
+    returns, so the host would have waited for that work either way."""
     if stream is None:
         import torch
-        stream = torch.cuda.current_stream()
-    return getattr(stream, "cuda_stream", stream)
+        stream = torch.cuda.current_stream(device)
+    handle = getattr(stream, "cuda_stream", stream)
+    if not handle:
+        import torch
+        torch.cuda.default_stream(getattr(stream, "device", device)).synchronize()
+    return handle
 
 
 def synthetic_image(width, height, seed=0x9E3779B1):

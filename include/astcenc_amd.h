@@ -18,7 +18,11 @@
  *   device_out   : device pointer, receives 16 bytes per block in raster block order
  *   data_len     : bytes available at device_out (>= 16 * blocks, else ASTCENC_ERR_OUT_OF_MEM)
  *   hip_stream   : hipStream_t to launch on (NULL = the context's own stream); the call returns
- *                  after the work on that stream has completed
+ *                  after the work on that stream has completed.  The context's own stream is a
+ *                  non-blocking stream (hipStreamNonBlocking), NOT the legacy null stream: work
+ *                  queued on the null stream -- a kernel that produces device_image, a fill of
+ *                  device_out -- is not waited for.  A caller whose work is on the null stream
+ *                  synchronises it before the call.  This holds for every hip_stream below.
  *   kernel_ms    : optional; receives the elapsed time of the compression kernel(s) measured with
  *                  HIP events recorded on that stream around the launches
  *

@@ -66,7 +66,7 @@ def _single(lib, A, ctx, img, nblocks, swz):
     h, w = img.shape[-3], img.shape[-2]
     types = {torch.uint8: A.TYPE_U8, torch.float16: A.TYPE_F16, torch.float32: A.TYPE_F32}
     err = lib.lib.astcenc_amd_compress_volume_device(ctx, img.data_ptr(), w, h, d, types[img.dtype], C.byref(A.Swizzle(*swz)),
-                                                     out.data_ptr(), out.numel(), torch.cuda.current_stream().cuda_stream, None)
+                                                     out.data_ptr(), out.numel(), A.torch_stream(), None)
     return err, out
 
 

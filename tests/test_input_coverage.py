@@ -159,11 +159,6 @@ def _fresh(blocks):
     return torch.full((blocks * 16,), CANARY, dtype=torch.uint8, device="cuda")
 
 
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 @gpu
 @pytest.mark.parametrize("ctx", ENTRY_CONTEXTS, ids=I.ctx_id)
 def test_device_image_entry_point(product, want, ctx):
@@ -173,7 +168,7 @@ def test_device_image_entry_point(product, want, ctx):
             t_img, out = _dev(img), _fresh(len(expect))
             err = product.lib.astcenc_amd_compress_image_device(handle, t_img.data_ptr(), img.shape[1], img.shape[0], TYPES[img.dtype],
                                                                 C.byref(A.Swizzle(*I.SWIZZLES[case.swizzle])), out.data_ptr(), out.numel(),
-                                                                _stream(), None)
+                                                                A.torch_stream(), None)
             assert err == 0, product.error_string(err)
             assert I.differing(expect, out.cpu().numpy()) == 0, I.case_id(case)
 
@@ -189,7 +184,7 @@ def test_device_volume_entry_point(product, ref, ctx):
             t_vol, out = _dev(vol), _fresh(len(expect))
             err = product.lib.astcenc_amd_compress_volume_device(handle, t_vol.data_ptr(), vol.shape[2], vol.shape[1], vol.shape[0],
                                                                  TYPES[vol.dtype], C.byref(A.Swizzle(*I.SWIZZLES[case.swizzle])),
-                                                                 out.data_ptr(), out.numel(), _stream(), None)
+                                                                 out.data_ptr(), out.numel(), A.torch_stream(), None)
             assert err == 0, product.error_string(err)
             assert I.differing(expect, out.cpu().numpy()) == 0, I.case_id(case)
 

@@ -70,7 +70,7 @@ def _single(lib, A, ctx, img, nbytes, swz):
     out = torch.full((nbytes,), 0xAB, dtype=torch.uint8, device="cuda")
     types = {torch.uint8: A.TYPE_U8, torch.float16: A.TYPE_F16, torch.float32: A.TYPE_F32}
     err = lib.lib.astcenc_amd_compress_image_device(ctx, img.data_ptr(), img.shape[1], img.shape[0], types[img.dtype], C.byref(A.Swizzle(*swz)),
-                                                    out.data_ptr(), out.numel(), torch.cuda.current_stream().cuda_stream, None)
+                                                    out.data_ptr(), out.numel(), A.torch_stream(), None)
     assert err == A.SUCCESS
     return out
 

@@ -124,7 +124,7 @@ def _single_volume(lib, A, ctx, img, nbytes, swz):
     types = {torch.uint8: A.TYPE_U8, torch.float16: A.TYPE_F16, torch.float32: A.TYPE_F32}
     err = lib.lib.astcenc_amd_compress_volume_device(ctx, img.data_ptr(), img.shape[2], img.shape[1], img.shape[0], types[img.dtype],
                                                      C.byref(A.Swizzle(*swz)), out.data_ptr(), out.numel(),
-                                                     torch.cuda.current_stream().cuda_stream, None)
+                                                     A.torch_stream(), None)
     assert err == A.SUCCESS
     return out
 

@@ -143,7 +143,7 @@ def _single_volume(lib, A, ctx, img, nbytes):
     out = torch.full((nbytes,), 0xAB, dtype=torch.uint8, device="cuda")
     err = lib.lib.astcenc_amd_compress_volume_device(ctx, img.data_ptr(), img.shape[2], img.shape[1], img.shape[0], A.TYPE_U8,
                                                      C.byref(A.Swizzle(*A.SWZ_RGBA)), out.data_ptr(), out.numel(),
-                                                     torch.cuda.current_stream().cuda_stream, None)
+                                                     A.torch_stream(), None)
     assert err == A.SUCCESS
     return out
 

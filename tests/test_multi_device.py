@@ -97,7 +97,7 @@ def test_device_buffers_follow_their_device_and_restore_the_callers(product, A):
         out = torch.zeros(nb * 16, dtype=torch.uint8, device="cuda")
         swz = A.Swizzle(*A.SWZ_RGBA)
         e = product.lib.astcenc_amd_compress_image_device(ctx, img.data_ptr(), 512, 512, A.TYPE_U8, ctypes.byref(swz), out.data_ptr(), out.numel(),
-                                                          torch.cuda.current_stream().cuda_stream, None)
+                                                          A.torch_stream(), None)
         assert e == A.SUCCESS
         assert torch.cuda.current_device() == before
         assert np.array_equal(out.cpu().numpy(), product.compress(img.cpu().numpy(), (6, 6), A.PRE_FAST))

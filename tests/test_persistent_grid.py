@@ -91,7 +91,7 @@ def device_stream(product, A, ctx, image, block):
     t_image = torch.from_numpy(np.ascontiguousarray(image)).cuda()
     out = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
     err = product.lib.astcenc_amd_compress_image_device(ctx, t_image.data_ptr(), w, h, 0, C.byref(A.Swizzle(*A.SWZ_RGBA)), out.data_ptr(), out.numel(),
-                                                        torch.cuda.current_stream().cuda_stream, None)
+                                                        A.torch_stream(), None)
     assert err == 0, product.error_string(err)
     return out.cpu().numpy()
 

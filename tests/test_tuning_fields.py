@@ -199,14 +199,13 @@ def test_every_entry_point_of_a_context(product, want, ctx):
         assert product.compress_raw(handle, np.ascontiguousarray(img), host) == 0
         outs["host pointer"] = host
         t_img = torch.from_numpy(np.array(img)).cuda()
-        stream = torch.cuda.current_stream().cuda_stream
         swz = A.Swizzle(*A.SWZ_RGBA)
 
         def fresh():
             return torch.full((36 * 16,), 0xA5, dtype=torch.uint8, device="cuda")
         out = fresh()
         err = product.lib.astcenc_amd_compress_image_device(handle, t_img.data_ptr(), img.shape[1], img.shape[0], A.TYPE_U8, C.byref(swz),
-                                                            out.data_ptr(), out.numel(), stream, None)
+                                                            out.data_ptr(), out.numel(), A.torch_stream(), None)
         assert err == 0, product.error_string(err)
         outs["device pointer"] = out.cpu().numpy()
         out = fresh()

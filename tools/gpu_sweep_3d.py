@@ -56,7 +56,7 @@ for block in ((3, 3, 3), (4, 4, 4), (6, 6, 6)):
     best = 1e9
     for i in range(3):
         e = gpu.lib.astcenc_amd_compress_volume_device(ctx, d_vol.data_ptr(), N, N, N, 0, ctypes.byref(swz), out.data_ptr(), out.numel(),
-                                                       torch.cuda.current_stream().cuda_stream, ctypes.byref(ms))
+                                                       A.torch_stream(), ctypes.byref(ms))
         assert e == 0
         if i: best = min(best, ms.value)
     print("%d^3 RGBA8 %dx%dx%d -medium: kernel %.1f ms -> %.1f Mtexels/s" % ((N,) + block + (best, N ** 3 / best / 1e3)), flush=True)

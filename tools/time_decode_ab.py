@@ -66,6 +66,7 @@ for name, profile, b, quality, img, n, ttype, tdtype in CASES[:int(os.environ.ge
             err, pctx = plib.context_alloc(pcfg, 1); assert err == 0
             blocks = torch.zeros(nb * 16, dtype=torch.uint8, device="cuda")
             ms = ctypes.c_float()
+            torch.cuda.synchronize()        # the image and the fill above come from torch's default stream; a NULL hip_stream does not wait for it
             assert plib.lib.astcenc_amd_compress_image_device(pctx, img.data_ptr(), n, n, 0 if img.dtype == torch.uint8 else 1, ctypes.byref(swz),
                                                               blocks.data_ptr(), blocks.numel(), None, ctypes.byref(ms)) == 0
             plib.context_free(pctx)

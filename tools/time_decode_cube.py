@@ -136,6 +136,7 @@ NEEDED = 5                                                                  # la
 def whole_level(l):
     n = DIMS[l]
     out = torch.zeros((6, n, n, 4), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()                                               # as whole_level of tools/time_decode_volume.py
     e = lib.decompress_tensors_device(ctx, entries, A.tensor_format(A.TENSOR_F32, A.TENSOR_INTERLEAVED, 4), [(l, (0, 0, 0), (n, n, 6), out)], stream=stream.cuda_stream)
     assert e == 0, e
     torch.cuda.synchronize()
@@ -225,6 +226,7 @@ for name, dirs, lod, uv in workloads:
             e = lib.lib.astcenc_amd_sample_lod_tensors_device(ctx, entry_arr, LEVELS, C.byref(fmt), C.byref(lod_sampler), lod_prepared, 1, stream.cuda_stream)
             assert e == 0, e
         ways["lod_call_on_layer_4"] = lod_call
+    torch.cuda.synchronize()                                               # the fills above are on torch's default stream, which the calls' own stream does not wait for
     for fn in ways.values():                                               # warm-up of every way, and the results the check reads
         fn()
     torch.cuda.synchronize()

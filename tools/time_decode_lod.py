@@ -159,6 +159,7 @@ dims_t = torch.tensor(DIMS, dtype=torch.float32, device="cuda")
 def decode_level(l):
     n = DIMS[l]
     scratch = torch.zeros((n, n, 4), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                                               # the fills above are on torch's default stream, which the calls' own stream does not wait for
     e = lib.lib.astcenc_amd_decompress_image_device(ctx, C.c_void_p(streams[l].data_ptr()), streams[l].numel(), C.c_void_p(scratch.data_ptr()), n, n, 1,
                                                     A.TYPE_U8, C.byref(A.Swizzle(*A.SWZ_RGBA)), stream.cuda_stream)
     assert e == 0, e
@@ -240,6 +241,7 @@ for name, levels, coords, lod in workloads:
             ways["sample_call_of_parent_build"] = lambda: sample_one(parent, parent_ctx, one_parent)
     else:
         ways["sample_call_per_level_and_torch"] = lambda: per_level(levels, duv, dlod, out["other"])
+    torch.cuda.synchronize()                                               # the fills above are on torch's default stream, which the calls' own stream does not wait for
     for fn in ways.values():                                               # warm-up of every way
         fn()
     torch.cuda.synchronize()

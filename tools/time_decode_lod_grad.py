@@ -154,6 +154,7 @@ def stats(t):
 
 
 ways = {"grad": way_grad, "forward": way_forward, "torch": way_torch}
+torch.cuda.synchronize()                                               # the fills above are on torch's default stream, which the calls' own stream does not wait for
 for fn in ways.values():                                                   # warm-up of every way
     fn()
 torch.cuda.synchronize()

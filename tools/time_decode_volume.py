@@ -174,6 +174,9 @@ for footprint in FOOTPRINTS:
     def whole_level(l):
         n = DIMS[l]
         out = torch.zeros((n, n, n, 4), dtype=torch.float32, device="cuda")
+        # (the fill is on torch's default stream, handle 0, which as hip_stream means the context's own stream; the wrapper's
+        # resolver, A.torch_stream, would synchronise for handle 0 as well -- this decode feeds the model, so it is said here too)
+        torch.cuda.synchronize()
         e = lib.decompress_tensors_device(ctx, entries, A.tensor_format(A.TENSOR_F32, A.TENSOR_INTERLEAVED, 4), [(l, (0, 0, 0), (n, n, n), out)], stream=stream.cuda_stream)
         assert e == 0, e
         torch.cuda.synchronize()
@@ -222,6 +225,7 @@ for footprint in FOOTPRINTS:
                 e = lib.lib.astcenc_amd_sample_lod_tensors_device(ctx, entry_arr, LEVELS, C.byref(fmt), C.byref(lod_sampler), lod_prepared, 1, stream.cuda_stream)
                 assert e == 0, e
             ways["lod_call_on_slice_100"] = lod_call
+        torch.cuda.synchronize()                                               # the fills above are on torch's default stream, which the calls' own stream does not wait for
         for fn in ways.values():                                           # warm-up of every way, and the results the check reads
             fn()
         torch.cuda.synchronize()

@@ -16,7 +16,7 @@ nb = ((size + 5) // 6) ** 2
 out = torch.zeros(nb * 16, dtype=torch.uint8, device="cuda")
 swz = A.Swizzle(*A.SWZ_RGBA); ms = ctypes.c_float(); best = 1e9
 for i in range(3):
-    e = lib.lib.astcenc_amd_compress_image_device(ctx, img.data_ptr(), size, size, A.TYPE_F16, ctypes.byref(swz), out.data_ptr(), out.numel(), torch.cuda.current_stream().cuda_stream, ctypes.byref(ms))
+    e = lib.lib.astcenc_amd_compress_image_device(ctx, img.data_ptr(), size, size, A.TYPE_F16, ctypes.byref(swz), out.data_ptr(), out.numel(), A.torch_stream(), ctypes.byref(ms))
     assert e == 0
     if i: best = min(best, ms.value)
 print("HDR %dx%d RGBA16F 6x6 medium: kernel %.2f ms -> %.2f Mtexels/s" % (size, size, best, size * size / best / 1e3))

@@ -20,7 +20,7 @@ out = torch.zeros(nb * 16, dtype=torch.uint8, device="cuda")
 swz = A.Swizzle(*A.SWZ_RGBA); ms = ctypes.c_float()
 best = 1e9
 for i in range(steps + 1):
-    e = lib.lib.astcenc_amd_compress_image_device(ctx, img.data_ptr(), size, size, 0, ctypes.byref(swz), out.data_ptr(), out.numel(), torch.cuda.current_stream().cuda_stream, ctypes.byref(ms))
+    e = lib.lib.astcenc_amd_compress_image_device(ctx, img.data_ptr(), size, size, 0, ctypes.byref(swz), out.data_ptr(), out.numel(), A.torch_stream(), ctypes.byref(ms))
     assert e == 0
     if i > 0: best = min(best, ms.value)
 print("%s [%s]: %dx%d %dx%d q=%.0f kernel %.2f ms -> %.2f Mtexels/s" % (os.path.basename(sys.argv[1]), lib.lib.astcenc_amd_context_kernel_name(ctx).decode(), size, size, b, b, q, best, size * size / best / 1e3))
