@@ -32,18 +32,7 @@ astcenc_error astcenc_amd_sample_volume_tensors_device(astcenc_context* ctx, con
 	unsigned long long tiles = 0;
 	for (unsigned int i = 0; i < grid_count; i++)
 	{
-		const astcenc_amd_volume_grid& g = grids[i];
-		SampleGridShape points = { g.out_x, g.out_y, g.coords, g.coord_row_pitch };
-		points.per_point = 3;
-		status = check_lod_grid(fn, i, grid_count, entries, entry_count, format, g, points, g.out, "out",
-			[&](const astcenc_amd_image_set_entry& en, unsigned int entry, unsigned int l)
-			{
-				// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
-				if (en.dim_x <= 65536 && en.dim_y <= 65536 && en.dim_z <= 65536) return ASTCENC_SUCCESS;
-				backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u x %u texels: a level is at most 65536 along x, y and z", fn, i, grid_count, entry, l, en.dim_x,
-				            en.dim_y, en.dim_z);
-				return ASTCENC_ERR_BAD_PARAM;
-			}, launches[i], tiles);
+		status = check_volume_grid(fn, i, grid_count, entries, entry_count, format, grids[i], grids[i].out, "out", launches[i], tiles);
 		if (status != ASTCENC_SUCCESS) return status;
 	}
 

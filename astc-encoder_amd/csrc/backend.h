@@ -283,6 +283,8 @@ struct DecompressLodGradJob {
 	void*    stream;
 };
 int backend_decompress_lod_grad(Backend* b, const DecompressLodGradJob& job);
+/* astcenc_amd_sample_volume_grad_device: the same job, the grids' coordinates triples and the sampler with its address_z. */
+int backend_decompress_volume_grad(Backend* b, const DecompressLodGradJob& job);
 int backend_compare_blocks_set(Backend* b, const QualitySetJob& job);
 /* Block selection and the adaptive driver (astcenc_adaptive.cpp, kernel_select.hip).  backend_select_blocks: the ascending list of
  * the blocks whose record meets the criterion, synchronous, *count on the host; runs on the device that owns the records.
@@ -536,7 +538,7 @@ int astc_decode_lod_launch(const void* d_table, uint32_t tiles, uint32_t type, u
  * pitches resolved and at least the tight ones.  Work items, table and launch as the lod call's. */
 struct DecodeLodGradLaunch {
 	DecodeLodLaunch lod;                  // d_out, row_pitch, plane_pitch: grad_out's
-	float*   d_grad_coords;               // point (i, j): the pair at d_grad_coords[j * grad_coord_row_pitch + 2 i]
+	float*   d_grad_coords;               // point (i, j): the pair at d_grad_coords[j * grad_coord_row_pitch + 2 i]; volume: the triple at [... + 3 i]
 	size_t   grad_coord_row_pitch;        // floats
 	float*   d_grad_lod;                  // point (i, j): d_grad_lod[j * grad_lod_row_pitch + i]; null: not wanted
 	size_t   grad_lod_row_pitch;          // floats
@@ -565,6 +567,14 @@ size_t astc_decode_volume_bytes(const DecodeLodLaunch* grids, uint32_t count);
 uint32_t astc_decode_volume_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
                                   const DecodeLodLaunch* grids, uint32_t count);
 int astc_decode_volume_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
+/* The gradients of that call (astcenc_amd_sample_volume_grad_device; decode_volume_grad.h, kernel_decode_volume_grad.hip): the
+ * volume call's sampler and the lod gradient's launch, its z unused, checked by the entry point: the volume call's checks with
+ * grad_out in the place of the output -- it is read -- grad_coords aligned to a float and triples, its pitch at least 3 out_x,
+ * grad_lod (when given) aligned to a float, the pitches resolved.  Work items, table and launch as the volume call's. */
+size_t astc_decode_volume_grad_bytes(const DecodeLodGradLaunch* grids, uint32_t count);
+uint32_t astc_decode_volume_grad_build(void* out, const DecodeLaunch* entries, uint32_t entry_count, const DecodeTensorFormat& format, const DecodeLodSampler& sampler,
+                                       const DecodeLodGradLaunch* grids, uint32_t count);
+int astc_decode_volume_grad_launch(const void* d_table, uint32_t tiles, uint32_t type, uint32_t layout, void* stream);
 /* The per-footprint tables of the decoder (block mode field -> weight grid, bit budget -> colour quant level): built on
  * the host once per context into astc_decode_tables_bytes() bytes, uploaded with the context's other tables. */
 size_t astc_decode_tables_bytes();

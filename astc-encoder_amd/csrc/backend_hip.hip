@@ -1745,6 +1745,11 @@ int backend_decompress_volume(Backend* b, const DecompressLodJob& job)
 	return decompress_lod_grids(b, job, "sample volume tensors", astc_decode_volume_bytes, astc_decode_volume_build, astc_decode_volume_launch);
 }
 
+int backend_decompress_volume_grad(Backend* b, const DecompressLodGradJob& job)
+{
+	return decompress_lod_grids(b, job, "sample volume grad", astc_decode_volume_grad_bytes, astc_decode_volume_grad_build, astc_decode_volume_grad_launch, 2u, lod_grad_buffer);
+}
+
 /* astcenc_amd_compare_blocks_device and its kin: the set's table is uploaded like the decoder's, the scratch for the partial
  * sums has a fixed size (rc 1 when it cannot be had, nothing launched), the totals come back once the stream has run. */
 static int compare_blocks_on_slot(Backend* b, DeviceSlot* s, hipStream_t stream, const QualitySetJob& job)

@@ -13,7 +13,8 @@
 // values it keeps of the level: Dx, Dy and S.  After the last pass the lane blends (two products and a sum, one rounding) and
 // stores the pair with one 8-byte store and the level-of-detail gradient with one 4-byte store.
 //
-// Included by kernel_decode_lod_grad.hip and tests/harness/decode_lod_grad_check.cpp only.
+// Included by kernel_decode_lod_grad.hip, decode_volume_grad.h (the launch's table writer and lod_grad_upstream) and
+// tests/harness/decode_lod_grad_check.cpp only.
 //
 // Layout: decode_lod.h's with DecodeLodGradRecord in the place of DecodeLodRecord: ImageSetTable (count = grids, total = tiles),
 // first[count], padding, DecodeLodGradRecord[count], then the DecodeLodLevel records of grid 0's levels, of grid 1's ...

@@ -1,6 +1,6 @@
 // SPDX-License-Identifier: Apache-2.0
 // What the samplers' entry points share beyond regions_internal.h (astcenc_sample.cpp, astcenc_lod.cpp, astcenc_lod_grad.cpp,
-// astcenc_cube.cpp, astcenc_volume.cpp): the
+// astcenc_cube.cpp, astcenc_volume.cpp, astcenc_volume_grad.cpp): the
 // checks of the sampler's filter and address modes, of the footprint, of the entries' block counts, of a grid's points and their
 // pairs or triples (check_sample_grid), of a chain and of the levels of detail, with the sample and lod calls' error codes and log
 // lines; the checks of a call of the lod family as a whole (check_lod_call, check_lod_grid), to which the cube and volume calls
@@ -314,11 +314,32 @@ inline astcenc_error check_lod_grid(const char* fn, unsigned int i, unsigned int
 		}, l, tiles);
 }
 
-/* A buffer of the gradient call that is written, `name` with its pitch `pitch_name`: `per_point` floats a point (2: grad_coords,
- * aligned to 8 bytes, an even pitch; 1: grad_lod, aligned to 4 bytes); the pitch comes back resolved. */
+/* The grid of the volume call or of its gradient (an astcenc_amd_volume_grid or an astcenc_amd_volume_grad_grid): triples, no
+ * slice to pick (the launch's z stays 0), and every level is no larger than 65536 along x, y and z. */
+template <class Grid>
+inline astcenc_error check_volume_grid(const char* fn, unsigned int i, unsigned int grid_count, const astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+                                       const astcenc_amd_tensor_format* format, const Grid& g, void* out, const char* out_name, DecodeLodLaunch& l, unsigned long long& tiles)
+{
+	SampleGridShape points = { g.out_x, g.out_y, g.coords, g.coord_row_pitch };
+	points.per_point = 3;
+	return check_lod_grid(fn, i, grid_count, entries, entry_count, format, g, points, out, out_name,
+		[&](const astcenc_amd_image_set_entry& en, unsigned int entry, unsigned int lv)
+		{
+			// (a level coordinate is u W: within 2^30 for |u| <= 2^14)
+			if (en.dim_x <= 65536 && en.dim_y <= 65536 && en.dim_z <= 65536) return ASTCENC_SUCCESS;
+			backend_log("%s: grid %u of %u: entry %u (level %u) is %u x %u x %u texels: a level is at most 65536 along x, y and z", fn, i, grid_count, entry, lv, en.dim_x,
+			            en.dim_y, en.dim_z);
+			return ASTCENC_ERR_BAD_PARAM;
+		}, l, tiles);
+}
+
+/* A buffer of a gradient call that is written, `name` with its pitch `pitch_name`: `per_point` floats a point (2: the lod
+ * gradient's grad_coords, aligned to 8 bytes, an even pitch; 3: the volume gradient's, aligned to 4 bytes, any pitch; 1: grad_lod,
+ * aligned to 4 bytes); the pitch comes back resolved. */
 inline astcenc_error check_grad_buffer(const char* fn, unsigned int i, unsigned int grid_count, const char* name, const char* pitch_name, const float* buffer,
                                        size_t& row_pitch, unsigned int per_point, unsigned int out_x, unsigned int out_y)
 {
+	const unsigned int align = per_point == 2 ? 8u : 4u;
 	const size_t tight = (size_t)per_point * out_x;
 	if ((per_point == 2 && (row_pitch & 1u) != 0) || (row_pitch != 0 && row_pitch < tight))
 	{
@@ -333,9 +354,9 @@ inline astcenc_error check_grad_buffer(const char* fn, unsigned int i, unsigned 
 		backend_log("%s: grid %u of %u: %s %zu: the gradients do not fit 64 bits", fn, i, grid_count, pitch_name, row_pitch);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
-	if (reinterpret_cast<uintptr_t>(buffer) % (4u * per_point) != 0)
+	if (reinterpret_cast<uintptr_t>(buffer) % align != 0)
 	{
-		backend_log("%s: grid %u of %u: %s %p is not aligned to %u bytes", fn, i, grid_count, name, static_cast<const void*>(buffer), 4u * per_point);
+		backend_log("%s: grid %u of %u: %s %p is not aligned to %u bytes", fn, i, grid_count, name, static_cast<const void*>(buffer), align);
 		return ASTCENC_ERR_BAD_PARAM;
 	}
 	row_pitch = resolved;

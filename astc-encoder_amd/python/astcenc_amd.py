@@ -106,7 +106,8 @@ EXPORTS_AMD = ["astcenc_amd_compress_image_device", "astcenc_amd_compress_volume
                "astcenc_amd_decompress_regions_device", "astcenc_amd_decompress_tensors_device",
                "astcenc_amd_decompress_scaled_tensors_device", "astcenc_amd_sample_tensors_device",
                "astcenc_amd_sample_lod_tensors_device", "astcenc_amd_sample_cube_tensors_device",
-               "astcenc_amd_sample_volume_tensors_device", "astcenc_amd_sample_lod_grad_device"]
+               "astcenc_amd_sample_volume_tensors_device", "astcenc_amd_sample_lod_grad_device",
+               "astcenc_amd_sample_volume_grad_device"]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 TENSOR_FLIP_X, TENSOR_FLIP_Y = 0x1, 0x2
@@ -527,6 +528,35 @@ def volume_grid(first_entry, level_count, coords, lod, out_view, lod_bias=0.0, l
     return VolumeGrid(first_entry, level_count, *_triple_grid(first_entry, level_count, "coords", coords, lod, out_view, lod_bias, layout, type))
 
 
+class VolumeGradGrid(C.Structure):
+    """struct astcenc_amd_volume_grad_grid (include/astcenc_amd.h)."""
+    _fields_ = [("first_entry", C.c_uint), ("level_count", C.c_uint), ("out_x", C.c_uint), ("out_y", C.c_uint),
+                ("coords", C.c_void_p), ("coord_row_pitch", C.c_size_t), ("lod", C.c_void_p), ("lod_row_pitch", C.c_size_t), ("lod_bias", C.c_float),
+                ("grad_out", C.c_void_p), ("row_pitch", C.c_size_t), ("plane_pitch", C.c_size_t),
+                ("grad_coords", C.c_void_p), ("grad_coord_row_pitch", C.c_size_t), ("grad_lod", C.c_void_p), ("grad_lod_row_pitch", C.c_size_t)]
+
+
+def volume_grad_grid(first_entry, level_count, coords, lod, grad_out, grad_coords, grad_lod=None, lod_bias=0.0, layout=TENSOR_PLANAR, type=None):
+    """VolumeGradGrid of the forward grid volume_grid(first_entry, level_count, coords, lod, <out>): `grad_out` is the torch view of
+    the upstream gradient, of the forward output's shape and type ([C, H, W] or [H, W, C]); `grad_coords` a float32 torch tensor
+    [H, W, 3] and `grad_lod` a float32 torch tensor [H, W] or None (not wanted), which are written.  ValueError for everything
+    volume_grid rejects -- of `grad_out` what it rejects of the output, of `grad_coords` what it rejects of `coords`, of `grad_lod`
+    what it rejects of `lod` -- and for a `grad_coords` of another H, W or on another device than `coords`.  Or explicit tuples:
+    coords = (ptr, out_x, out_y, coord_row_pitch), lod = (ptr, lod_row_pitch) or None, grad_out = (ptr, row_pitch, plane_pitch),
+    grad_coords = (ptr, grad_coord_row_pitch), grad_lod = (ptr, grad_lod_row_pitch) or None."""
+    g = _triple_grid(first_entry, level_count, "coords", coords, lod, grad_out, lod_bias, layout, type)
+    if isinstance(coords, tuple):
+        gcptr, grad_coord_row_pitch = grad_coords
+        glptr, grad_lod_row_pitch = grad_lod if grad_lod is not None else (None, 0)
+    else:
+        # (the triples of gradients are laid out as the triples of coordinates are: the same checks, grad_lod in the place of lod)
+        w = _triple_grid(first_entry, level_count, "grad_coords", grad_coords, grad_lod, grad_out, lod_bias, layout, type)
+        if grad_coords.device != coords.device:
+            raise ValueError("grad_coords is on %s, coords on %s" % (grad_coords.device, coords.device))
+        gcptr, grad_coord_row_pitch, glptr, grad_lod_row_pitch = w[2], w[3], w[4], w[5]
+    return VolumeGradGrid(first_entry, level_count, *(g + (gcptr, grad_coord_row_pitch, glptr, grad_lod_row_pitch)))
+
+
 class ErrorSums(C.Structure):
     """struct astcenc_amd_error_sums (include/astcenc_amd.h)."""
     _fields_ = [("squared_error", C.c_double * 4), ("alpha_scaled_squared_error", C.c_double * 4),
@@ -684,6 +714,10 @@ class Library:
             L.astcenc_amd_sample_volume_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(VolumeSampler),
                                                                    C.POINTER(VolumeGrid), C.c_uint, C.c_void_p]
             L.astcenc_amd_sample_volume_tensors_device.restype = C.c_int
+        if hasattr(L, "astcenc_amd_sample_volume_grad_device"):
+            L.astcenc_amd_sample_volume_grad_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(VolumeSampler),
+                                                                C.POINTER(VolumeGradGrid), C.c_uint, C.c_void_p]
+            L.astcenc_amd_sample_volume_grad_device.restype = C.c_int
         if hasattr(L, "astcenc_amd_sample_tensors_device"):
             L.astcenc_amd_sample_tensors_device.argtypes = [C.c_void_p, C.POINTER(ImageSetEntry), C.c_uint, C.POINTER(TensorFormat), C.POINTER(Sampler),
                                                             C.POINTER(SampleGrid), C.c_uint, C.c_void_p]
@@ -976,6 +1010,32 @@ class Library:
         garr = (VolumeGrid * len(grids))(*grids) if grids else None
         return self.lib.astcenc_amd_sample_volume_tensors_device(ctx, arr, n, C.byref(format) if format is not None else None,
                                                                  C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_volume_grad(self, ctx, entries, format, sampler, grids):
+        """astcenc_amd_sample_volume_grad_device: the gradients of sample_volume_tensors_device with respect to the coordinates and
+        the levels of detail, for upstream gradients of `format`'s type and layout.  sampler as there.  grids: VolumeGradGrid, or
+        (first_entry, level_count, coords, lod, grad_out, grad_coords[, grad_lod[, lod_bias]]) tuples (see volume_grad_grid).
+        The call runs on torch's current stream (torch_stream()) and is complete on return; there is no stream argument, and the
+        name has no _device suffix: the table of tests/test_stream_order.py lists every method of this class that has either, row
+        by row, and this one's ordering is tested in tests/test_decode_volume_grad.py instead.  A caller who wants another stream
+        makes it current: `with torch.cuda.stream(s): lib.sample_volume_grad(...)`."""
+        arr, n, s = self._set_args(entries, None)
+        if sampler is not None and not isinstance(sampler, VolumeSampler):
+            sampler = VolumeSampler(*sampler)
+        grids = [g if isinstance(g, VolumeGradGrid) else volume_grad_grid(*g, layout=format.layout, type=format.type) for g in grids]
+        garr = (VolumeGradGrid * len(grids))(*grids) if grids else None
+        return self.lib.astcenc_amd_sample_volume_grad_device(ctx, arr, n, C.byref(format) if format is not None else None,
+                                                              C.byref(sampler) if sampler is not None else None, garr, len(grids), s)
+
+    def sample_volume(self, ctx, entries, format, sampler, first_entry, level_count, coords, lod=None, lod_bias=0.0):
+        """The volume call as a differentiable torch operation: samples the chain entries[first_entry : first_entry + level_count]
+        at `coords` (float32 [H, W, 3]) and `lod` (float32 [H, W] or None) into a new tensor of `format` -- [C, H, W] or
+        [H, W, C] -- on torch's current stream; its backward is sample_volume_grad and returns gradients for `coords` and `lod`
+        only (the texels are compressed and fixed).  AstcError when either call fails."""
+        entries = [e if isinstance(e, ImageSetEntry) else image_set_entry(*e) for e in entries]
+        if not isinstance(sampler, VolumeSampler):
+            sampler = VolumeSampler(*sampler)
+        return _sample_volume_function().apply(coords, lod, self, ctx, entries, format, sampler, first_entry, level_count, lod_bias)
 
     @staticmethod
     def _blocks_args(blocks, image, decode_type, swizzle, block_errors, stream):
@@ -1424,6 +1484,49 @@ def _sample_lod_function():
 
     _SAMPLE_LOD_FUNCTION = SampleLod
     return SampleLod
+
+
+_SAMPLE_VOLUME_FUNCTION = None
+
+
+def _sample_volume_function():
+    """The torch.autograd.Function behind Library.sample_volume, made on first use like _sample_lod_function."""
+    global _SAMPLE_VOLUME_FUNCTION
+    if _SAMPLE_VOLUME_FUNCTION is not None:
+        return _SAMPLE_VOLUME_FUNCTION
+    import torch
+    dtypes = {TENSOR_F32: torch.float32, TENSOR_F16: torch.float16, TENSOR_BF16: torch.bfloat16}
+
+    class SampleVolume(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coords, lod, lib, ctx, entries, format, sampler, first_entry, level_count, lod_bias):
+            coords = coords.detach().contiguous()
+            lod = lod.detach().contiguous() if lod is not None else None
+            h, w = coords.shape[0], coords.shape[1]
+            shape = (format.channels, h, w) if format.layout == TENSOR_PLANAR else (h, w, format.channels)
+            out = torch.empty(shape, dtype=dtypes[format.type], device=coords.device)
+            err = lib.sample_volume_tensors_device(ctx, entries, format, sampler, [(first_entry, level_count, coords, lod, out, lod_bias)])
+            if err != SUCCESS:
+                raise AstcError(err, "astcenc_amd_sample_volume_tensors_device")
+            fctx.save_for_backward(coords, *([lod] if lod is not None else []))
+            fctx.call = (lib, ctx, entries, format, sampler, first_entry, level_count, lod_bias)
+            return out
+
+        @staticmethod
+        def backward(fctx, grad_out):
+            lib, ctx, entries, format, sampler, first_entry, level_count, lod_bias = fctx.call
+            saved = fctx.saved_tensors
+            coords, lod = saved[0], saved[1] if len(saved) > 1 else None
+            grad_out = grad_out.contiguous()
+            grad_coords = torch.empty_like(coords)
+            grad_lod = torch.empty_like(lod) if lod is not None and fctx.needs_input_grad[1] else None
+            err = lib.sample_volume_grad(ctx, entries, format, sampler, [(first_entry, level_count, coords, lod, grad_out, grad_coords, grad_lod, lod_bias)])
+            if err != SUCCESS:
+                raise AstcError(err, "astcenc_amd_sample_volume_grad_device")
+            return (grad_coords, grad_lod) + (None,) * 8
+
+    _SAMPLE_VOLUME_FUNCTION = SampleVolume
+    return SampleVolume
 
 
 def torch_stream(stream=None, device=None):

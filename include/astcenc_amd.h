@@ -540,7 +540,8 @@ struct astcenc_amd_lod_grad_grid {
  *   on tap indices.  At a texel centre (f = 0) the gradient is the right-hand difference.  Away from cell boundaries and integer
  *   lambda the gradients agree with central differences of the forward call to within its own rounding.
  *
- *   Out of scope: gradients with respect to texels; second derivatives; the cube and volume samplers.
+ *   Out of scope: gradients with respect to texels; second derivatives; the cube sampler.  The volume sampler's gradients are
+ *   astcenc_amd_sample_volume_grad_device's, further down.
  *
  *   - Everything astcenc_amd_sample_lod_tensors_device checks is checked here with its error codes, grad_out in the place of
  *     `out`; the log callback names the index: "grid i of n".
@@ -714,7 +715,8 @@ struct astcenc_amd_volume_grid {
  *   two, the texel centres ((kx + 0.5) / W_l, (ky + 0.5) / H_l, (kz + 0.5) / D_l) of a level selected with weight 1 reproduce,
  *   with either filter and any address modes, what astcenc_amd_decompress_tensors_device writes for those texels.
  *
- *   Out of scope: level selection from derivatives; anisotropy; gradients.
+ *   Out of scope: level selection from derivatives; anisotropy.  Gradients with respect to the coordinates and the level of detail are
+ *   astcenc_amd_sample_volume_grad_device's, below; gradients with respect to texels are out of scope (the texels are compressed).
  *
  *   - Everything astcenc_amd_sample_lod_tensors_device checks is checked here with its error codes -- the entries, the format,
  *     the filters and address_x / address_y, out_x and out_y, the chain, lod, lod_bias and their pitch, `out` and its pitches,
@@ -733,6 +735,99 @@ ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_volume_tensors_device(
 	const struct astcenc_amd_tensor_format* format,
 	const struct astcenc_amd_volume_sampler* sampler,
 	const struct astcenc_amd_volume_grid* grids, unsigned int grid_count,
+	void* hip_stream);
+
+/* The gradients of astcenc_amd_sample_volume_tensors_device with respect to its inputs: the backward pass of whatever optimises
+ * coordinates through a volume lookup -- the parameters of the rays of a ray marcher, a deformation field, a camera pose, the
+ * positions fed to the feature grid of a neural field -- over volumes that stay compressed.  The texels are compressed and fixed,
+ * so the gradients that exist are those for the coordinates and the level of detail; trilinear sampling is linear in each of
+ * u, v and w within a texel cell and the blend is piecewise linear in lambda, so they have an exact form in the eight texels the
+ * forward call addresses.  For every point of every grid the call takes an upstream gradient -- d loss / d out, in the forward
+ * call's format and layout -- and writes d loss / d (u, v, w) and, when wanted, d loss / d lod: the vector-Jacobian product. */
+struct astcenc_amd_volume_grad_grid {
+	unsigned int first_entry, level_count;  /* the forward grid's fields, with its meanings and limits ... */
+	unsigned int out_x, out_y;
+	const float* coords;
+	size_t coord_row_pitch;
+	const float* lod;
+	size_t lod_row_pitch;
+	float lod_bias;
+	const void* grad_out;                   /* device pointer: the upstream gradient, element (c = 0, j = 0, i = 0): a tensor of the format's
+	                                           type and layout, placed as the forward call places `out` */
+	size_t row_pitch, plane_pitch;          /* ... of grad_out, in ELEMENTS of the format's type; 0 = tightly packed */
+	float* grad_coords;                     /* device pointer: point (i, j) is the triple at grad_coords[j * grad_coord_row_pitch + 3 * i],
+	                                           d loss / du, d loss / dv, then d loss / dw; 4-byte aligned, like `coords` */
+	size_t grad_coord_row_pitch;            /* in floats; 0 = 3 * out_x; otherwise >= 3 * out_x */
+	float* grad_lod;                        /* device pointer: point (i, j) has grad_lod[j * grad_lod_row_pitch + i]; NULL: not wanted */
+	size_t grad_lod_row_pitch;              /* in floats; 0 = out_x */
+};
+
+/* The gradients of grids[0 .. grid_count).  `format` and `sampler` are the forward call's; format->scale is used and
+ * format->bias is not (a shift has no derivative).  For point (i, j) of a grid, with (u, v, w), lod and lod_bias as in the
+ * forward call (reals are IEEE binary64 below unless said otherwise; "one operation" is one IEEE operation, round to nearest
+ * even, never fused; any sum starts as its first product -- nothing is added to a zero):
+ *
+ *   Validity, lambda', lambda_c, l0, g.  Those of astcenc_amd_sample_volume_tensors_device.  An invalid point writes +0.0 to all
+ *     four gradients.
+ *   Upstream.  a[c] = (double)grad_out[c] * (double)scale[c], one product, for c < format->channels; the element of grad_out is
+ *     where the forward call places out[c] of the point, and is widened exactly (F32, F16, BF16).  format->bias is not used.
+ *     Upstream values are data: a NaN or an infinity there is not an error.
+ *   Per level l that is part of the point (below), with x = (double)u * (double)W_l, y = (double)v * (double)H_l and
+ *     z = (double)w * (double)D_l, the forward call's exact products:
+ *     s_l[c] is the forward call's level sample, binary32.  S_l = the sum over c < channels, in order, of a[c] * (double)s_l[c].
+ *     Under NEAREST, Dx_l = Dy_l = Dz_l = +0.0.
+ *     Under BILINEAR, on every axis i0 = floor(t) with t = x - 0.5 (y - 0.5, z - 0.5), and the weights and the tap counts are
+ *     the forward call's.  On every axis both indices i0 and i0 + 1 are always addressed, each through the forward call's
+ *     "Addressing" with that axis's mode and size -- kx0 and kx1, ky0 and ky1, kz0 and kz1 -- even where the forward call's
+ *     tap 1 has weight 0.  A BORDER tap outside on any of the three axes is +0.0.  The sums mirror the forward order: the
+ *     innermost runs over the first remaining axis, the outer over the next; a bracketed term is there when the forward call
+ *     has two taps on that axis, and the taps are the forward call's, in tap order.
+ *       dsdx[c]: d(ky, kz) = v(kx1, ky, kz)[c] - v(kx0, ky, kz)[c], one subtraction of the widened texels.  For every forward z
+ *         tap: q(kz) = wy0 * d(ky0, kz) [+ wy1 * d(ky1, kz)].  dsdx[c] = wz0 * q(kz0) [+ wz1 * q(kz1)].
+ *       dsdy[c]: e(kx, kz) = v(kx, ky1, kz)[c] - v(kx, ky0, kz)[c].  r(kz) = wx0 * e(kx0, kz) [+ wx1 * e(kx1, kz)].
+ *         dsdy[c] = wz0 * r(kz0) [+ wz1 * r(kz1)].
+ *       dsdz[c]: f(kx, ky) = v(kx, ky, kz1)[c] - v(kx, ky, kz0)[c].  r(ky) = wx0 * f(kx0, ky) [+ wx1 * f(kx1, ky)].
+ *         dsdz[c] = wy0 * r(ky0) [+ wy1 * r(ky1)].
+ *       Dx_l = (the sum over c < channels, in order, of a[c] * dsdx[c]) * (double)W_l; Dy_l likewise with dsdy and H_l, Dz_l with
+ *         dsdz and D_l.
+ *     A texel that is in none of these sums may or may not be read; a NaN there does not reach a result.
+ *   grad_coords.  One level (g = 0, or MIP_NEAREST): (float)Dx_l0, (float)Dy_l0 and (float)Dz_l0.  Two levels (g != 0):
+ *     (float)((1.0 - g) * Dx_l0 + g * Dx_l1) -- two products, one sum, one rounding to binary32 -- and likewise for v and w.
+ *   grad_lod.  astcenc_amd_sample_lod_grad_device's rule: the derivative is not zero only under MIP_LINEAR where
+ *     0 <= lambda' < level_count - 1, that is where lambda' is not clamped: there it is (float)(S_(l0+1) - S_l0), one subtraction
+ *     and one rounding -- at an integer lambda' the right derivative.  This case samples level l0 + 1 for S alone even when
+ *     g = 0.  Everywhere else -- MIP_NEAREST, a clamped lambda', a chain of one level -- grad_lod is +0.0.  When grad_lod is NULL
+ *     a level of weight zero is not read.
+ *   Storage.  A gradient that is a NaN is stored as the canonical quiet NaN 0x7FC00000.
+ *   Placement and pitches.  grad_coords as `coords`, grad_lod as `lod`.  No other element is written.
+ *
+ *   Consequences: where the z axis has one tap, wz0 is exactly 1.0 and 1.0 * q is q; so on a context of a 2D footprint, a grid
+ *   all of whose points have one z tap of the same kz in every level they use gets d loss / du, d loss / dv and grad_lod bit
+ *   for bit equal to what astcenc_amd_sample_lod_grad_device writes for z = kz (and d loss / dw is the difference towards slice
+ *   kz + 1 as addressed).  Under CLAMP a point more than half a texel outside the volume along an axis has a zero gradient
+ *   along it, because both taps clamp to one texel.  The same formula is the derivative under REPEAT, MIRROR and BORDER,
+ *   because addressing acts on tap indices.  At a texel centre on an axis the gradient along it is the right-hand difference.
+ *   Away from cell boundaries and integer lambda the gradients agree with central differences of the forward call to within
+ *   its own rounding.
+ *
+ *   Out of scope: gradients with respect to texels; second derivatives; the cube sampler.
+ *
+ *   - Everything astcenc_amd_sample_volume_tensors_device checks is checked here with its error codes, grad_out in the place
+ *     of `out`; the log callback names the index: "grid i of n".
+ *   - ASTCENC_ERR_BAD_CONTEXT: a null grad_out or grad_coords.  ASTCENC_ERR_BAD_PARAM: a grad_coords or a grad_lod not aligned to
+ *     4 bytes; a grad_out not aligned to its element; a non-zero gradient pitch below the tight one (3 * out_x, out_x; the pitch
+ *     of grad_coords need not be even); a grad_out, grad_coords or grad_lod that is not on the device of entry 0's blocks.  A
+ *     null grad_lod is legal.
+ *   - Everything is checked before anything is launched; a failure writes nothing.  An output that overlaps an input is the
+ *     caller's error and is not detected.
+ *   - A work item is the forward call's tile of 64 points; a tile runs one pass per distinct level its points need, and a pass
+ *     decodes every block the eight addressed taps of its points reach once. */
+ASTCENC_PUBLIC enum astcenc_error astcenc_amd_sample_volume_grad_device(
+	struct astcenc_context* context,
+	const struct astcenc_amd_image_set_entry* entries, unsigned int entry_count,
+	const struct astcenc_amd_tensor_format* format,
+	const struct astcenc_amd_volume_sampler* sampler,
+	const struct astcenc_amd_volume_grad_grid* grids, unsigned int grid_count,
 	void* hip_stream);
 
 /* Mip chains: the levels of a 2D device image made on the device, and compressed with it in one call.
